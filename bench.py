@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- pose hypotheses/sec of the MI355X correlative scan matcher.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the metric line needs and nothing else: inputs, W untimed steps, K timed steps, the line.
+`--full` adds everything else this script measures or checks (the self-check of the timed path against single calls,
+the roofline pass, the other cfg2x forms, the production legs, cfg1/3/4/5 and the CPU baselines); `--only` and `--legs`
+select among what `--full` runs and imply it, the `--no-*` switches leave parts of it out.  `--dump-outputs DIR`
+writes what the last timed step computed (rank 0's per-item results and the best records of its enqueues) as
+DIR/<name>.npy, float64.
 
 With N > 1 and no WORLD_SIZE in the environment the script starts its own N ranks
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...`, as a child process, before anything here
@@ -15,7 +22,7 @@ issued as enqueues of `--launch-batch` problems, all inputs resident in HBM.  Wi
 batch per step (weak scaling) and the ranks exchange their best (response, pose) records with one RCCL all-gather
 per step.  `value` = lattice points scored by all ranks / wall time of K steps.
 
-`config.by_config` carries the other BASELINE configs measured in the same run: cfg1 (CPU oracle), cfg2 as ONE
+With `--full`, `config.by_config` carries the other BASELINE configs measured in the same run: cfg1 (CPU oracle), cfg2 as ONE
 unbatched match_scan call, cfg3 (2000-scan sequential mapping), cfg4 (1 query vs 4096 distinct chains, the chains
 sharded over the ranks = strong scaling, RCCL arg-max), cfg5 (stress lattice) -- and what production would see of the
 metric workload: `cfg2x_batch_sweep` (1 query x N chains per enqueue, N = 8 ... 4096), `cfg2x_fresh_query` (a NEW query
@@ -23,7 +30,7 @@ every enqueue: descriptor copy, query projection and the query's pair lists insi
 (every chain re-posed before every enqueue: the point cache misses on every scan).  A leg that raised is listed under
 `leg_errors` and makes the exit code non-zero.
 
-`roofline`: `bound` = the resource of the dominant kernel with the highest measured utilisation, `frac` <= 1 against that
+`roofline` (`--full`): `bound` = the resource of the dominant kernel with the highest measured utilisation, `frac` <= 1 against that
 resource's peak.  The kernel's duration is measured in this run (HIP events on the launch stream); the counters behind
 the utilisations (VALU / LDS / HBM, `rocprofv3 --pmc`) are replayed from the committed `profiles/*.json` of the same
 kernel and say so (`replayed_from`).  `algorithmic_frac` keeps SURVEY.md 8(d)'s figure (one grid byte per beam and
@@ -73,7 +80,14 @@ def parse_args(argv=None):
     ap.add_argument("--corr-region", type=int, default=0, help="development: 1 = direct correlate on batches too")
     ap.add_argument("--corr-region-na", type=int, default=0, help="development: jobs per wave of the gather correlate")
     ap.add_argument("--corr-pad-lds", type=int, default=0, help="development: extra LDS bytes per correlate block")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also run every check, leg and baseline beyond the metric line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.only or args.legs:  # (they select among the legs of a --full run)
+        args.full = True
+    return args
 
 
 def self_launch(args):
@@ -167,6 +181,25 @@ def replayed_roofline(workload, kernel, kernel_s, valu_peak_key="region_correlat
                           "issuing": k.get("SQ_ACTIVE_INST_ANY", 0.0) / wc} if wc else None,
             "l2_hit_rate": k["TCC_HIT_sum"] / (k["TCC_HIT_sum"] + k["TCC_MISS_sum"]) if k.get("TCC_HIT_sum") else None,
             "replayed_from": "profiles/counters.json (%s, workload %s: %s)" % (ctr.get("tag"), workload, ctr["workloads"][workload]["command"])}
+
+
+def write_outputs(out_dir, arrays, limit_bytes=64 << 20):
+    """--dump-outputs: every array as out_dir/<name>.npy, float64.  Should the per-item arrays exceed `limit_bytes` in all, a fixed
+    sample of the items (seed 0, ascending) is written instead, its indices in item_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k_: np.ascontiguousarray(v_, dtype=np.float64) for k_, v_ in arrays.items()}
+    n = arrays["response"].shape[0]
+    per_item = [k_ for k_, v_ in arrays.items() if v_.shape[:1] == (n,)]
+    other = sum(arrays[k_].nbytes for k_ in arrays if k_ not in per_item) + 256 * (len(arrays) + 1)  # (+ the .npy headers)
+    item_bytes = sum(arrays[k_].nbytes for k_ in per_item) // max(1, n) + 8
+    if other + item_bytes * n > limit_bytes:
+        keep = max(1, (limit_bytes - other) // item_bytes)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        for k_ in per_item:
+            arrays[k_] = np.ascontiguousarray(arrays[k_][idx])
+        arrays["item_index"] = idx.astype(np.float64)
+    for k_, v_ in arrays.items():
+        np.save(os.path.join(out_dir, k_ + ".npy"), v_)
 
 
 def cpu_model():
@@ -264,7 +297,12 @@ def generate_inputs(args, rank, world, legs):
     from yag_slam_amd import dist as ymdist
     from yag_slam_amd import synth
     scene = synth.Scene()
-    workers = max(1, min(32, (os.cpu_count() or 1) // max(1, world)))
+    try:
+        ncpu = len(os.sched_getaffinity(0))
+    except AttributeError:
+        ncpu = os.cpu_count() or 1
+    ncpu = min(ncpu, int(os.environ.get("OMP_NUM_THREADS") or ncpu))  # (a cpu quota the affinity mask does not show)
+    workers = max(1, min(32, ncpu // max(1, world)))
     out = {"scene": scene}
     if "cfg2x" in legs or "single" in legs:
         base_poses, q_truth, q_prior = synth.single_match_poses()
@@ -281,7 +319,7 @@ def generate_inputs(args, rank, world, legs):
             dq_truth = np.array(q_truth) + np.concatenate([rng.uniform(-0.05, 0.05, size=(n, 2)), rng.uniform(-0.03, 0.03, size=(n, 1))], axis=1)
             dq_prior = np.array(q_prior) + np.concatenate([rng.uniform(-0.02, 0.02, size=(n, 2)), rng.uniform(-0.01, 0.01, size=(n, 1))], axis=1)
             out["cfg2_queries"] = (synth.scan_ranges_many([(tuple(dq_truth[c]), 200000 + c) for c in range(n)], scene, workers), dq_prior)
-    if "cfg2x" in legs and not args.only_headline and not args.no_distinct_queries:
+    if "cfg2x" in legs and args.full and not args.only_headline and not args.no_distinct_queries:
         # cfg2x_trajectory: batch (query, chain) pairs along the cfg3 trajectory -- heterogeneous poses and headings
         out["traj"] = synth.scan_ranges_many(synth.trajectory_jobs(args.batch + 10), scene, workers)
     if "cfg3" in legs and rank == 0:
@@ -575,6 +613,8 @@ def main():
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     legs = set(args.only.split(",")) if args.only else {"cfg2x", "single", "cfg3", "cfg4", "cfg5", "cpu"}
+    if not args.full:
+        legs = {"cfg2x"}
     if args.no_cpu_baseline:
         legs.discard("cpu")
     args.batch = max(args.launch_batch, args.batch // args.launch_batch * args.launch_batch)
@@ -675,7 +715,8 @@ def main():
         for lm, ls in zip(lanes[1:], lane_streams[1:]):
             lm.set_stream(ls.cuda_stream)
         NL = len(lanes)
-        batches = [lanes[e % NL].make_batch(query, chains[e * LB:(e + 1) * LB]) for e in range(E)]
+        one_query_needed = args.full or args.headline == "one_query" or args.no_distinct_queries
+        batches = [lanes[e % NL].make_batch(query, chains[e * LB:(e + 1) * LB]) for e in range(E)] if one_query_needed else None
         # the same chains, every item with its OWN query (own readings, own prior): ym_pairs_create
         pbatches = dqueries = None
         if "cfg2_queries" in gen:
@@ -691,9 +732,11 @@ def main():
         works = [None] * nbuf
         used = [[None] * nslots for _ in lanes]  # per lane: which batch object a slot's call belongs to
         counter = [0] * NL
+        last_step = []  # (enqueue, lane, slot) of the latest step
 
         def step(i, bs, one_at_a_time=False, marks=None):
             b = i % nbuf
+            del last_step[:]
             if works[b] is not None:
                 works[b].wait()  # its gathered records are about to be overwritten
                 works[b] = None
@@ -706,6 +749,7 @@ def main():
                 bs[e].run_async(True, True, slot=s, chain_id_base=rank * args.batch + e * LB,
                                 dev_best_out=records[b, e].data_ptr())
                 used[ln][s] = bs[e]
+                last_step.append((e, ln, s))
                 if one_at_a_time:  # (the profiling pass: a kernel's duration means something only while nothing runs beside it)
                     bs[e].wait(s, per_chain=False)
                     used[ln][s] = None
@@ -732,9 +776,10 @@ def main():
                     works[b].wait()
                     works[b] = None
 
-        def timed_steps(bs, steps, warmup):
+        def timed_steps(bs, steps, warmup, outputs=None):
             """`warmup` untimed steps, then `steps` steps between two barriers; returns (seconds, max over the ranks; per-step
-            completion intervals in ms on this rank, from HIP events on the lanes' streams)"""
+            completion intervals in ms on this rank, from HIP events on the lanes' streams).  outputs: a dict that receives
+            what the last timed step computed (after the timed region)"""
             import gc
             for i in range(warmup):
                 step(i, bs)
@@ -756,6 +801,8 @@ def main():
                 works[b_last].wait()
                 got = gathered[b_last].view(world, E, ymdist.RECORD)[rank]
                 assert torch.equal(got, records[b_last])
+            if outputs is not None:
+                outputs.update(last_step_outputs(bs, records[(steps - 1) % nbuf]))
             drain()
             t = torch.tensor([dt_], dtype=torch.float64, device="cuda")
             if dist is not None:
@@ -764,48 +811,51 @@ def main():
             per_step = [b_ - a_ for a_, b_ in zip([0.0] + ends[:-1], ends)]
             return float(t.item()), per_step
 
+        def last_step_outputs(bs, recs):
+            """the results of the latest step, as its caller receives them: per item (items in enqueue order) and per enqueue"""
+            per_e = {}
+            for e, ln, s in last_step:
+                per_e[e] = bs[e].wait(s, per_chain=True)
+                used[ln][s] = None
+            a = np.concatenate([per_e[e][0].array for e in range(E)])
+            out = {k_: np.asarray(a[k_], dtype=np.float64) for k_ in ("response", "pose", "cov", "coarse_response", "hypotheses",
+                                                                         "coarse_dims", "fine_dims", "n_query_points", "expansions", "status")}
+            out["best_index"] = np.array([per_e[e][2] for e in range(E)], dtype=np.float64)
+            out["best_records"] = recs.cpu().numpy().astype(np.float64)  # (the device records of the enqueues: what the ranks exchange)
+            return out
+
         def spread(per_step):
             v = sorted(per_step)
             return {"min": v[0], "median": v[len(v) // 2] if len(v) % 2 else 0.5 * (v[len(v) // 2 - 1] + v[len(v) // 2]), "max": v[-1],
                     "what": "ms between the completion of consecutive steps on the device (HIP events on the lanes' streams; the steps are "
                             "enqueued back to back, so the first one also carries the pipeline's fill)"}
 
-        # correctness of what is timed: first enqueue against the single-call path
-        per, best, bi = (batches[0].run_async(True, True, slot=0) or batches[0].wait(0))
-        hyp_per_match = per[0].meta["hypotheses"]
-        assert all(p.meta["hypotheses"] == hyp_per_match for p in per)
-        hyp_step = hyp_per_match * args.batch
-        ref = m.match_scan(query, chains[0], True, True)
-        checked = not os.environ.get("YM_BENCH_SKIP_CHECK")  # (development: timing-only builds of the library give wrong sums)
-        assert not checked or (ref.response == per[0].response and ref.covariance == per[0].covariance)
-        if pbatches is not None and checked:  # ... and of the distinct-query form: three of its items against their single calls
-            pper, _, _ = (pbatches[0].run_async(True, True, slot=0) or pbatches[0].wait(0))
-            assert all(p.meta["hypotheses"] == hyp_per_match for p in pper)
-            for i_ in (0, LB // 2, LB - 1):
-                ref = m.match_scan(dqueries[i_], chains[i_], True, True)
-                assert ref.response == pper[i_].response and ref.covariance == pper[i_].covariance, i_
-
         hb = pbatches if headline_distinct else batches
-        dt, per_step = timed_steps(hb, args.steps, args.warmup)
+        checked = not os.environ.get("YM_BENCH_SKIP_CHECK")  # (development: timing-only builds of the library give wrong sums)
+        if args.full:
+            # correctness of what is timed: first enqueue against the single-call path
+            per, best, bi = (batches[0].run_async(True, True, slot=0) or batches[0].wait(0))
+            hyp_per_match = per[0].meta["hypotheses"]
+            assert all(p.meta["hypotheses"] == hyp_per_match for p in per)
+            hyp_step = hyp_per_match * args.batch
+            ref = m.match_scan(query, chains[0], True, True)
+            assert not checked or (ref.response == per[0].response and ref.covariance == per[0].covariance)
+            if pbatches is not None and checked:  # ... and of the distinct-query form: three of its items against their single calls
+                pper, _, _ = (pbatches[0].run_async(True, True, slot=0) or pbatches[0].wait(0))
+                assert all(p.meta["hypotheses"] == hyp_per_match for p in pper)
+                for i_ in (0, LB // 2, LB - 1):
+                    ref = m.match_scan(dqueries[i_], chains[i_], True, True)
+                    assert ref.response == pper[i_].response and ref.covariance == pper[i_].covariance, i_
+        else:
+            per, _, _ = (hb[0].run_async(True, True, slot=0) or hb[0].wait(0))
+            hyp_per_match = per[0].meta["hypotheses"]
+            assert all(p.meta["hypotheses"] == hyp_per_match for p in per)
+            hyp_step = hyp_per_match * args.batch
+        outputs = {} if args.dump_outputs and rank == 0 else None
+        dt, per_step = timed_steps(hb, args.steps, args.warmup, outputs=outputs)
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
 
-        # roofline of the dominant kernel (coarse correlate): HIP events on the launch stream, second pass
-        for lm in lanes:
-            lm.profile(True)
-        for i in range(min(args.steps, 4)):
-            step(i, hb, one_at_a_time=NL > 1)
-        drain()
-        corr_ms = corr_n = call_ms = call_n = 0
-        for lm in lanes:
-            a_, b_ = lm.profile_read(0)
-            c_, d_ = lm.profile_read(2)
-            corr_ms, corr_n, call_ms, call_n = corr_ms + a_, corr_n + b_, call_ms + c_, call_n + d_
-            lm.profile(False)
-
-        nq = per[0].meta["n_query_points"]
-        cd = per[0].meta["coarse_dims"]
-        alg_bytes = LB * cd[0] * cd[1] * cd[2] * nq  # 1 grid byte per valid beam per coarse hypothesis
-        corr_s = corr_ms / max(corr_n, 1) * 1e-3
-        achieved = alg_bytes / corr_s / 1e9
         ms_per_step = dt / args.steps * 1e3
         line["value"] = hyp_step * world * args.steps / dt
         line["ms_per_step"] = ms_per_step
@@ -823,93 +873,113 @@ def main():
             "timed_seconds": dt,
             "collective": "all_gather of %d 64-byte best records per rank per step" % E if dist is not None else "none",
         }
-        # the other form of the workload, same lanes, same step function, fewer steps
-        if pbatches is not None and not args.only_headline:
-            ob = batches if headline_distinct else pbatches
-            odt, oper = timed_steps(ob, max(4, args.steps // 2), 2)
-            osteps = max(4, args.steps // 2)
-            by_config["cfg2x_one_query" if headline_distinct else "cfg2x_distinct_queries"] = {
-                "what": ("every item against the SAME query object" if headline_distinct else
-                         "every item its OWN query (own readings, own prior): %d distinct queries per enqueue, ym_pairs_create" % LB) +
-                        "; same chains, lanes and step function as the metric line",
-                "queries_per_enqueue": 1 if headline_distinct else LB, "steps": osteps, "ms_per_step": odt / osteps * 1e3,
-                "ms_per_step_spread": spread(oper), "hypotheses_per_s": hyp_step * world * osteps / odt,
-                "scan_matches_per_s": args.batch * world * osteps / odt,
-                "ratio_to_metric_line": (hyp_step * world * osteps / odt) / line["value"]}
-        # the same step function on HETEROGENEOUS problems: (query, chain) pairs along the cfg3 trajectory -- query i = scan 10 + i at its
-        # odometry prior, chain i = the ten scans before it at their true poses: every item its own pose, heading, window contents,
-        # region lists and patch counts (the metric's items all sit within 5 cm of ONE pose, as SURVEY 8(d) specifies them)
-        if "traj" in gen and pbatches is not None:
-            t_truth, t_prior = synth.loop_trajectory(args.batch + 10)
-            tscans = [synth.resident_scan(r_, p_) for r_, p_ in zip(gen["traj"], t_truth)]
-            tq = [synth.resident_scan(gen["traj"][10 + i_], t_prior[10 + i_]) for i_ in range(args.batch)]
-            native_many(tscans + tq, local_rank)
-            tb = [lanes[e % NL].make_pairs_batch(tq[e * LB:(e + 1) * LB], [tscans[i_:i_ + 10] for i_ in range(e * LB, (e + 1) * LB)]) for e in range(E)]
-            tper, _, _ = (tb[0].run_async(True, True, slot=0) or tb[0].wait(0))
-            for i_ in (0, LB // 3, LB - 1):  # (what is timed is right: three items against their single calls)
-                ref = m.match_scan(tq[i_], tscans[i_:i_ + 10], True, True)
-                assert not checked or (ref.response == tper[i_].response and ref.covariance == tper[i_].covariance), i_
-            tsteps = max(4, args.steps // 2)
-            tdt, tps = timed_steps(tb, tsteps, 2)
-            thyp = float(tper.array["hypotheses"].sum()) / LB * args.batch
+        # everything below, up to the production legs, is --full's: the measurements beside the metric line
+        if args.full:
+            # roofline of the dominant kernel (coarse correlate): HIP events on the launch stream, second pass
             for lm in lanes:
                 lm.profile(True)
-            for i in range(2):
-                step(i, tb, one_at_a_time=NL > 1)
+            for i in range(min(args.steps, 4)):
+                step(i, hb, one_at_a_time=NL > 1)
             drain()
-            tk = [0.0] * 6
+            corr_ms = corr_n = call_ms = call_n = 0
             for lm in lanes:
-                for w_ in range(3):
-                    a_, b_ = lm.profile_read(w_)
-                    tk[2 * w_] += a_
-                    tk[2 * w_ + 1] += b_
+                a_, b_ = lm.profile_read(0)
+                c_, d_ = lm.profile_read(2)
+                corr_ms, corr_n, call_ms, call_n = corr_ms + a_, corr_n + b_, call_ms + c_, call_n + d_
                 lm.profile(False)
-            by_config["cfg2x_trajectory"] = {
-                "what": "%d (query, chain) pairs per step along the cfg3 trajectory (query i = scan 10 + i at its odometry prior against the ten scans "
-                        "before it at their true poses): heterogeneous poses, headings and windows; same lanes and step function as the metric line" % args.batch,
-                "steps": tsteps, "ms_per_step": tdt / tsteps * 1e3, "ms_per_step_spread": spread(tps), "hypotheses_per_s": thyp * world * tsteps / tdt,
-                "scan_matches_per_s": args.batch * world * tsteps / tdt, "ratio_to_metric_line": (thyp * world * tsteps / tdt) / line["value"],
-                "region_correlate_us": tk[0] / max(tk[1], 1) * 1e3, "raster_us": tk[2] / max(tk[3], 1) * 1e3, "call_us_gpu": tk[4] / max(tk[5], 1) * 1e3,
-                "metric_line_region_correlate_us": corr_s * 1e6, "metric_line_call_us_gpu": call_ms / max(call_n, 1) * 1e3,
-                "mean_response": float(tper.array["response"].mean())}
-            del tb
-        region = LB >= 8 and args.corr_region != 1
-        # (the default region correlate of a large batch stages from the row-major window: template argument WIN = true)
-        kernel = "ym::correlate_region_kernel<8, true>" if region else "ym::correlate_kernel<2, 16, 4>"
-        if region and any(o_ == 39 and v_ for o_, v_ in dev_opts):
-            kernel = "ym::correlate_region_kernel<8>"
-        step_alg = hyp_step * nq  # coarse + fine lattice points x one byte per valid beam
-        rl = replayed_roofline("cfg2x", kernel, corr_s) if LB == 4096 else None
-        if rl is None:
-            rl = {"bound": "hbm", "kernel": kernel, "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
-                  "kernel_us": corr_s * 1e6, "replayed_from": None}
-        rl.update({
-            "call_us_gpu": call_ms / max(call_n, 1) * 1e3,
-            # one grid byte per valid beam and hypothesis, against the HBM peak.  Not a roofline fraction:
-            # the bytes are gathered from LDS, where a staged byte is read ~19 times
-            "algorithmic_bytes_per_launch": alg_bytes, "algorithmic_GBps": achieved, "algorithmic_frac": achieved / HBM_PEAK_GBS,
-            # the whole step against the same figure: every kernel of the call, launch gaps and host work included
-            "algorithmic_frac_step": step_alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-        })
-        # the other kernels of an enqueue, from the same counter passes (durations: the kernel-trace pass of the profiled run, one
-        # enqueue at a time -- these kernels are not timed live): what each is bound by, at a glance
-        ctr = profile_json("counters.json")
-        try:
-            others = {}
-            for kn, kv in ctr["workloads"]["cfg2x"]["kernels"].items():
-                if not kn.startswith("ym::") or kn == kernel or kv.get("us", 0.0) < 30.0 or "structure_kernel" in kn or "points_kernel" in kn:
-                    continue
-                us = kv["us"] if "raster" not in kn else min(kv["us"], kv.get("min_us", kv["us"]) * 1.05)  # (the raster's mean holds a first-call outlier)
-                clk = us * 1e-6 * DEVICE["clock_hz"] * DEVICE["cus"]
-                hb = kv.get("FETCH_SIZE", 0.0) * 2048.0 + kv.get("WRITE_SIZE", 0.0) * 1024.0
-                others[kn] = {"us_in_the_profiled_run": us, "valu_per_cu_clk": kv.get("SQ_INSTS_VALU", 0.0) / clk, "lds_busy": kv.get("SQ_LDS_IDX_ACTIVE", 0.0) / clk,
-                              "vector_l1_line_visits_per_cu_clk": kv.get("TCP_TOTAL_CACHE_ACCESSES_sum", 0.0) / clk, "hbm_GBps": hb / (us * 1e-6) / 1e9,
-                              "hbm_frac": hb / (us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                              "waiting_share_of_wave_time": kv.get("SQ_WAIT_ANY", 0.0) / kv["SQ_WAVE_CYCLES"] if kv.get("SQ_WAVE_CYCLES") else None}
-            rl["other_kernels_of_an_enqueue"] = others
-        except (KeyError, TypeError):
-            pass
-        line["roofline"] = rl
+
+            nq = per[0].meta["n_query_points"]
+            cd = per[0].meta["coarse_dims"]
+            alg_bytes = LB * cd[0] * cd[1] * cd[2] * nq  # 1 grid byte per valid beam per coarse hypothesis
+            corr_s = corr_ms / max(corr_n, 1) * 1e-3
+            achieved = alg_bytes / corr_s / 1e9
+            # the other form of the workload, same lanes, same step function, fewer steps
+            if pbatches is not None and not args.only_headline:
+                ob = batches if headline_distinct else pbatches
+                odt, oper = timed_steps(ob, max(4, args.steps // 2), 2)
+                osteps = max(4, args.steps // 2)
+                by_config["cfg2x_one_query" if headline_distinct else "cfg2x_distinct_queries"] = {
+                    "what": ("every item against the SAME query object" if headline_distinct else
+                             "every item its OWN query (own readings, own prior): %d distinct queries per enqueue, ym_pairs_create" % LB) +
+                            "; same chains, lanes and step function as the metric line",
+                    "queries_per_enqueue": 1 if headline_distinct else LB, "steps": osteps, "ms_per_step": odt / osteps * 1e3,
+                    "ms_per_step_spread": spread(oper), "hypotheses_per_s": hyp_step * world * osteps / odt,
+                    "scan_matches_per_s": args.batch * world * osteps / odt,
+                    "ratio_to_metric_line": (hyp_step * world * osteps / odt) / line["value"]}
+            # the same step function on HETEROGENEOUS problems: (query, chain) pairs along the cfg3 trajectory -- query i = scan 10 + i at its
+            # odometry prior, chain i = the ten scans before it at their true poses: every item its own pose, heading, window contents,
+            # region lists and patch counts (the metric's items all sit within 5 cm of ONE pose, as SURVEY 8(d) specifies them)
+            if "traj" in gen and pbatches is not None:
+                t_truth, t_prior = synth.loop_trajectory(args.batch + 10)
+                tscans = [synth.resident_scan(r_, p_) for r_, p_ in zip(gen["traj"], t_truth)]
+                tq = [synth.resident_scan(gen["traj"][10 + i_], t_prior[10 + i_]) for i_ in range(args.batch)]
+                native_many(tscans + tq, local_rank)
+                tb = [lanes[e % NL].make_pairs_batch(tq[e * LB:(e + 1) * LB], [tscans[i_:i_ + 10] for i_ in range(e * LB, (e + 1) * LB)]) for e in range(E)]
+                tper, _, _ = (tb[0].run_async(True, True, slot=0) or tb[0].wait(0))
+                for i_ in (0, LB // 3, LB - 1):  # (what is timed is right: three items against their single calls)
+                    ref = m.match_scan(tq[i_], tscans[i_:i_ + 10], True, True)
+                    assert not checked or (ref.response == tper[i_].response and ref.covariance == tper[i_].covariance), i_
+                tsteps = max(4, args.steps // 2)
+                tdt, tps = timed_steps(tb, tsteps, 2)
+                thyp = float(tper.array["hypotheses"].sum()) / LB * args.batch
+                for lm in lanes:
+                    lm.profile(True)
+                for i in range(2):
+                    step(i, tb, one_at_a_time=NL > 1)
+                drain()
+                tk = [0.0] * 6
+                for lm in lanes:
+                    for w_ in range(3):
+                        a_, b_ = lm.profile_read(w_)
+                        tk[2 * w_] += a_
+                        tk[2 * w_ + 1] += b_
+                    lm.profile(False)
+                by_config["cfg2x_trajectory"] = {
+                    "what": "%d (query, chain) pairs per step along the cfg3 trajectory (query i = scan 10 + i at its odometry prior against the ten scans "
+                            "before it at their true poses): heterogeneous poses, headings and windows; same lanes and step function as the metric line" % args.batch,
+                    "steps": tsteps, "ms_per_step": tdt / tsteps * 1e3, "ms_per_step_spread": spread(tps), "hypotheses_per_s": thyp * world * tsteps / tdt,
+                    "scan_matches_per_s": args.batch * world * tsteps / tdt, "ratio_to_metric_line": (thyp * world * tsteps / tdt) / line["value"],
+                    "region_correlate_us": tk[0] / max(tk[1], 1) * 1e3, "raster_us": tk[2] / max(tk[3], 1) * 1e3, "call_us_gpu": tk[4] / max(tk[5], 1) * 1e3,
+                    "metric_line_region_correlate_us": corr_s * 1e6, "metric_line_call_us_gpu": call_ms / max(call_n, 1) * 1e3,
+                    "mean_response": float(tper.array["response"].mean())}
+                del tb
+            region = LB >= 8 and args.corr_region != 1
+            # (the default region correlate of a large batch stages from the row-major window: template argument WIN = true)
+            kernel = "ym::correlate_region_kernel<8, true>" if region else "ym::correlate_kernel<2, 16, 4>"
+            if region and any(o_ == 39 and v_ for o_, v_ in dev_opts):
+                kernel = "ym::correlate_region_kernel<8>"
+            step_alg = hyp_step * nq  # coarse + fine lattice points x one byte per valid beam
+            rl = replayed_roofline("cfg2x", kernel, corr_s) if LB == 4096 else None
+            if rl is None:
+                rl = {"bound": "hbm", "kernel": kernel, "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
+                      "kernel_us": corr_s * 1e6, "replayed_from": None}
+            rl.update({
+                "call_us_gpu": call_ms / max(call_n, 1) * 1e3,
+                # one grid byte per valid beam and hypothesis, against the HBM peak.  Not a roofline fraction:
+                # the bytes are gathered from LDS, where a staged byte is read ~19 times
+                "algorithmic_bytes_per_launch": alg_bytes, "algorithmic_GBps": achieved, "algorithmic_frac": achieved / HBM_PEAK_GBS,
+                # the whole step against the same figure: every kernel of the call, launch gaps and host work included
+                "algorithmic_frac_step": step_alg / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            })
+            # the other kernels of an enqueue, from the same counter passes (durations: the kernel-trace pass of the profiled run, one
+            # enqueue at a time -- these kernels are not timed live): what each is bound by, at a glance
+            ctr = profile_json("counters.json")
+            try:
+                others = {}
+                for kn, kv in ctr["workloads"]["cfg2x"]["kernels"].items():
+                    if not kn.startswith("ym::") or kn == kernel or kv.get("us", 0.0) < 30.0 or "structure_kernel" in kn or "points_kernel" in kn:
+                        continue
+                    us = kv["us"] if "raster" not in kn else min(kv["us"], kv.get("min_us", kv["us"]) * 1.05)  # (the raster's mean holds a first-call outlier)
+                    clk = us * 1e-6 * DEVICE["clock_hz"] * DEVICE["cus"]
+                    hb = kv.get("FETCH_SIZE", 0.0) * 2048.0 + kv.get("WRITE_SIZE", 0.0) * 1024.0
+                    others[kn] = {"us_in_the_profiled_run": us, "valu_per_cu_clk": kv.get("SQ_INSTS_VALU", 0.0) / clk, "lds_busy": kv.get("SQ_LDS_IDX_ACTIVE", 0.0) / clk,
+                                  "vector_l1_line_visits_per_cu_clk": kv.get("TCP_TOTAL_CACHE_ACCESSES_sum", 0.0) / clk, "hbm_GBps": hb / (us * 1e-6) / 1e9,
+                                  "hbm_frac": hb / (us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                                  "waiting_share_of_wave_time": kv.get("SQ_WAIT_ANY", 0.0) / kv["SQ_WAVE_CYCLES"] if kv.get("SQ_WAVE_CYCLES") else None}
+                rl["other_kernels_of_an_enqueue"] = others
+            except (KeyError, TypeError):
+                pass
+            line["roofline"] = rl
         line["config"]["point_cache"] = dict(zip(("hits", "misses"), m.cache_stats()))
 
         # ---- what production would see of this workload (same run, after the timed region of the metric)
@@ -1133,7 +1203,7 @@ def main():
                     "scan_creation_us_per_enqueue_per_thread": float(np.mean(t_create)) * 1e6, "ratio_to_metric_line": hps / line["value"] * world,
                     "identical_to_the_resident_form": same}
 
-        if rank == 0 and not args.no_production_legs:
+        if rank == 0 and args.full and not args.no_production_legs:
             sweep_legs = [("cfg2x_batch_sweep", leg_sweep), ("cfg2x_fresh_query", leg_fresh_query), ("cfg2x_cold", leg_cold),
                           ("cfg2x_alternating", leg_alternating)]
             if dqueries is not None:

@@ -27,7 +27,7 @@ if __name__ == "__main__":
         h, m = l2.get(k, {}).get("TCC_HIT_sum", 0.0), l2.get(k, {}).get("TCC_MISS_sum", 0.0)
         rows.append((k, f, h, m))
     with open("profiles/%s_pmc_batch%d.csv" % (tag.replace("r01p", "r01_p"), batch), "w") as o:
-        o.write("# rocprofv3 --pmc FETCH_SIZE | --pmc TCC_HIT_sum TCC_MISS_sum (separate passes): python3 bench.py --steps 5 --warmup 1 --batch %d --no-cpu-baseline\n" % batch)
+        o.write("# rocprofv3 --pmc FETCH_SIZE | --pmc TCC_HIT_sum TCC_MISS_sum (separate passes): python3 bench.py --full --steps 5 --warmup 1 --batch %d --no-cpu-baseline\n" % batch)
         o.write("# FETCH_SIZE in KiB as reported; gfx950 counts half of a 16-B/lane stream (MI355X_MICROARCH.md): bytes ~= 2*1024*FETCH_SIZE\n")
         o.write("kernel,FETCH_SIZE_KiB_mean,TCC_HIT_sum_mean,TCC_MISS_sum_mean,l2_hit_rate\n")
         for k, f, h, m in rows:

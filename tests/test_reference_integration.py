@@ -1,16 +1,20 @@
-"""INTEGRATION.md section 1 as a test: the REFERENCE's own `GraphSlam` (/root/reference/yag_slam/graph_slam.py) drives this
+"""INTEGRATION.md section 1 as a test: the REFERENCE's own `GraphSlam` (yag_slam/graph_slam.py of yag-slam) drives this
 package's scan and pose classes -- process_scan, loop-closure bookkeeping, run_opt, serialize / binarize / unbinarize --
-without a line of yag-slam changed.  Build container only (needs /root/reference); the matcher is a stand-in (no GPU
-here), everything else is the reference's code on yag_slam_amd objects."""
+without a line of yag-slam changed.  The run is recorded in tests/golden/graphslam_run.{json,bin} by
+tests/golden/make_golden_graphslam.py, which imports the reference (tests/refstubs.py); the matcher is a stand-in (no GPU
+there), everything else in the run is the reference's code on yag_slam_amd objects.  The test checks the recording against
+this package's scans, poses and map-file reader; tests/test_oracle_golden.py's opt-in regeneration test runs the
+reference again and requires the same bytes."""
+import json
 import math
+import os
 from collections import namedtuple
 
 import numpy as np
 import pytest
 
-from tests import refstubs
-
-pytestmark = pytest.mark.skipif(not refstubs.available(), reason="needs /root/reference (build container)")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+N_SCANS = 40
 
 Result = namedtuple("Result", "response covariance best_pose meta")
 
@@ -46,48 +50,49 @@ def _scans(n):
 
 
 def test_reference_graphslam_runs_on_this_packages_objects():
-    refstubs.install()
-    from yag_slam.graph_slam import GraphSlam          # the reference
+    import zlib
+
+    import msgpack
     from yag_slam_amd import mapfile
-    from yag_slam_amd.transform import Transform
-    n = 40
-    truth, scans = _scans(n)
-    seq, loop = StandInMatcher(truth), StandInMatcher(truth, loop=True)
-    slam = GraphSlam(seq, loop, scan_buffer_len=5, loop_search_dist=1.0, loop_search_min_chain_size=3)
-    closed = []
-    for s in scans:
-        res, c = slam.process_scan(s)
-        if c:
-            closed.append(s.num)
+    with open(os.path.join(GOLDEN, "graphslam_run.json")) as f:
+        rec = json.load(f)
+    with open(os.path.join(GOLDEN, "graphslam_run.bin"), "rb") as f:
+        blob = f.read()
+    n = N_SCANS
+    assert rec["n_scans"] == n
+    truth, scans = _scans(n)  # the inputs of the recorded run, built again from this package's classes
+    seq_calls = [(q, b, p, f) for q, b, p, f in rec["seq_calls"]]
+    loop_calls = [(q, b, p, f) for q, b, p, f in rec["loop_calls"]]
+    closed = rec["closed"]
     # the reference's call pattern reached the plugin: sequential match with penalty + fine on the running chain
-    assert seq.calls[0] == (1, [0], True, True)
-    assert all(len(c[1]) <= 5 for c in seq.calls if c[2])
+    assert seq_calls[0] == (1, [0], True, True)
+    assert all(len(c[1]) <= 5 for c in seq_calls if c[2])
     assert closed and min(closed) >= 24, closed              # second lap closes against the first
-    assert any(c[2:] == (False, False) for c in loop.calls)  # coarse loop stage (graph_slam.py:220)
-    assert any(c[2:] == (False, True) for c in seq.calls)    # fine stage on the moved copy (graph_slam.py:233-236)
-    assert slam.opt.computes == len(closed) and len(slam.opt.nodes) == n
-    for s, t in zip(scans, truth):
-        assert isinstance(s.corrected_pose, Transform)       # run_opt rebuilt every pose through tiny_tf.tf.Transform
-        assert abs(s.corrected_pose.x - t[0]) < 1e-12 and abs(s.corrected_pose.euler[-1] - t[2]) < 1e-12
-    # ---- the reference serialises this package's scans / poses / config, and reads them back
-    d = slam.serialize()
+    assert any(c[2:] == (False, False) for c in loop_calls)  # coarse loop stage (graph_slam.py:220)
+    assert any(c[2:] == (False, True) for c in seq_calls)    # fine stage on the moved copy (graph_slam.py:233-236)
+    assert rec["opt_computes"] == len(closed) and rec["opt_nodes"] == n
+    # run_opt rebuilt every pose through tiny_tf.tf.Transform
+    assert rec["corrected_pose_classes"] == ["yag_slam_amd.transform.Transform"]
+    for p, t in zip(rec["corrected_poses"], truth):
+        assert abs(p[0] - t[0]) < 1e-12 and abs(p[2] - t[2]) < 1e-12
+    # ---- the reference serialised this package's scans / poses / config, and read them back
+    d = msgpack.unpackb(zlib.decompress(blob))
     assert d["scans"][3]["___name"] == "LocalizedRangeScan" and d["scans"][3]["corrected_pose"]["___name"] == "Transform"
     assert d["seq_matcher_config"]["___name"] == "ScanMatcherConfig" and d["seq_matcher_config"]["search_size"] == 0.5
-    blob = slam.binarize()
-    back = GraphSlam.unbinarize(blob)                       # the reference's reader (its own scan class)
-    assert len(back.graph.vertices) == n and len(back.graph.edges) == len(slam.graph.edges)
-    for v, s in zip(back.graph.vertices, scans):
-        assert np.array_equal(np.asarray(v.obj.ranges), s.ranges)
-        assert abs(v.obj.corrected_pose.x - s.corrected_pose.x) < 1e-12
-        dth = v.obj.corrected_pose.euler[-1] - s.corrected_pose.euler[-1]   # a quaternion keeps the heading modulo 2 pi
+    back = rec["unbinarized"]                                # the reference's reader (its own scan class)
+    assert back["vertices"] == n and back["edges"] == rec["edges"]
+    for r, p, s, q in zip(back["ranges"], back["corrected_poses"], scans, rec["corrected_poses"]):
+        assert np.array_equal(np.asarray(r), s.ranges)
+        assert abs(p[0] - q[0]) < 1e-12
+        dth = p[2] - q[2]                                    # a quaternion keeps the heading modulo 2 pi
         assert abs(math.sin(dth)) < 1e-12 and math.cos(dth) > 0
     # ---- and this package's map-file reader agrees with the reference's on the same bytes
     mine = mapfile.loads(blob, matcher_factory=lambda cfg, loop: StandInMatcher(truth, loop))
-    assert len(mine.scans) == n and len(mine.constraints) == len(slam.graph.edges)
-    assert [s.num for s in mine.running_scans] == [s.num for s in slam.running_scans]
-    for a, s in zip(mine.scans, scans):
-        assert np.array_equal(a.ranges, s.ranges) and a.num == s.num
-        assert abs(a.corrected_pose.x - s.corrected_pose.x) < 1e-12 and abs(a.odom_pose.y - s.odom_pose.y) < 1e-12
+    assert len(mine.scans) == n and len(mine.constraints) == rec["edges"]
+    assert [s.num for s in mine.running_scans] == rec["running_scans"]
+    for a, s, q, num in zip(mine.scans, scans, rec["corrected_poses"], rec["nums"]):
+        assert np.array_equal(a.ranges, s.ranges) and a.num == num
+        assert abs(a.corrected_pose.x - q[0]) < 1e-12 and abs(a.odom_pose.y - s.odom_pose.y) < 1e-12
 
 
 def test_transform_speaks_tiny_tfs_constructor_and_attributes():
