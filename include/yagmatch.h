@@ -280,6 +280,27 @@ int ym_occupancy_get_info(const ym_occupancy *og, ym_occupancy_info *info);
 int ym_occupancy_read(const ym_occupancy *og, uint8_t *image, int64_t image_bytes); /* width*height bytes */
 void ym_occupancy_destroy(ym_occupancy *og);
 
+/* ---- virtual scans from an occupancy image: the ray casting of the ROS node's "start in a prior map" path
+ * (ingest_base_map -> map_to_graphslam -> map_to_graph, /root/reference/ros1/slam_node_ros1:131-147,
+ * /root/reference/yag_slam/splicing.py:82-107).  ym_raymap_trace is run_raytracing_sweep (raytracing.py:91-92) for
+ * n_starts viewpoints at once: every (viewpoint, angle) pair walks trace_ray (raytracing.py:63-88) -- pixel units, x = column,
+ * y = row of `image`, float32 point, one pixel per step, stop at a pixel < 210 (one more step after it, a 1000-pixel jump
+ * after a pixel in (180, 210)) or when the rounded point leaves [1, w - 1) x [1, h - 1) -- bit for bit.  starts_xy =
+ * n_starts (x, y) float64 (rounded to float32 as Point2 does; the rounded pixel must lie inside the image), dir_cs = n_angles
+ * unit (cos, sin) pairs computed by the caller (no trig on the device).  end_xy[n_starts][n_angles][2] receives the end
+ * points (RayInfo.end), length[n_starts][n_angles] |end - start| (RayInfo.length), *capped (nullable) the number of rays
+ * that reached the iteration cap 2 (w + h) + 4 (0 on every valid input).  Images up to 65536 x 65536 pixels.  Synchronous;
+ * n_starts or n_angles 0 returns YM_OK without a launch; on an invalid argument nothing is written. */
+typedef struct ym_raymap ym_raymap; /* an occupancy image resident on one device */
+ym_raymap *ym_raymap_create(int device, const uint8_t *image, int width, int height, int pitch);
+int ym_raymap_trace(ym_raymap *rm, const double *starts_xy, int n_starts, const double *dir_cs, int n_angles, float *end_xy,
+                    double *length, int64_t *capped);
+/* the same walk with a direction table per viewpoint: dir_cs = [n_starts][n_angles] (cos, sin) -- a scan per pose hypothesis,
+ * each cast along its own heading + beam angles, in one launch */
+int ym_raymap_trace_each(ym_raymap *rm, const double *starts_xy, int n_starts, const double *dir_cs, int n_angles, float *end_xy,
+                         double *length, int64_t *capped);
+void ym_raymap_destroy(ym_raymap *rm);
+
 /* ---- introspection for parity tests (state of the LAST completed synchronous match) ---- */
 typedef struct ym_grid_info {
     int32_t width, height, pitch; /* device window (bytes) */

@@ -26,6 +26,7 @@ EXPORTS = (
     "ym_coarse_dims", "ym_match_slice_begin", "ym_match_slice_finish",
     "ym_occupancy_create", "ym_occupancy_get_info", "ym_occupancy_read", "ym_occupancy_destroy",
     "ym_map_from_occupancy", "ym_map_from_grid", "ym_map_size", "ym_map_read", "ym_map_destroy", "ym_match_map",
+    "ym_raymap_create", "ym_raymap_trace", "ym_raymap_trace_each", "ym_raymap_destroy",
 )
 
 
@@ -210,6 +211,12 @@ def lib():
     L.ym_map_destroy.restype = None
     L.ym_match_map.argtypes = [vp, vp, C.c_double, C.c_double, C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(YmMapSearch),
                                C.POINTER(YmResult)]
+    L.ym_raymap_create.restype = vp
+    L.ym_raymap_create.argtypes = [C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int]
+    L.ym_raymap_trace.argtypes = [vp, dp, C.c_int, dp, C.c_int, C.POINTER(C.c_float), dp, C.POINTER(C.c_int64)]
+    L.ym_raymap_trace_each.argtypes = [vp, dp, C.c_int, dp, C.c_int, C.POINTER(C.c_float), dp, C.POINTER(C.c_int64)]
+    L.ym_raymap_destroy.argtypes = [vp]
+    L.ym_raymap_destroy.restype = None
     _lib = L
     return L
 

@@ -32,3 +32,4 @@
 #include "ym_k_gather.hpp"
 #include "ym_k_yagpy.hpp"
 #include "ym_k_occupancy.hpp"
+#include "ym_k_raytrace.hpp"
