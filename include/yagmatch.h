@@ -301,6 +301,34 @@ int ym_raymap_trace_each(ym_raymap *rm, const double *starts_xy, int n_starts, c
                          double *length, int64_t *capped);
 void ym_raymap_destroy(ym_raymap *rm);
 
+/* ---- the segment graph of a prior map from its label image: the rest of map_to_graph (yag_slam/splicing.py:57-80 of the
+ * reference).  `labels` is the segmentation of the map (segment_map's output: SLIC stays with the caller), int32
+ * [height][pitch_elems], x = column, y = row, 0 = no segment, 1 .. K = segments; 1 x 1 up to 65536 x 65536 pixels.
+ * ym_segments_create uploads it and finds the smallest and largest label (ym_segments_label_range returns them).
+ * ym_segments_stats replaces determine_centroids' per-segment image scans: count / sum_x / sum_y [n_labels], indexed by
+ * LABEL (0 included), exact 64-bit integers; the centroid of label l is (sum_x[l] / count[l], sum_y[l] / count[l]) in
+ * float64, bit for bit np.mean of the coordinate arrays.  Every label must lie in [0, n_labels): otherwise YM_ERR_INVALID.
+ * ym_segments_boundaries writes skimage.segmentation.find_boundaries(labels) (defaults: connectivity 1, mode "thick") as
+ * width * height bytes 0 / 1 -- restated from that library's documented behaviour: a pixel whose label differs from the
+ * maximum or minimum over itself and its 4 neighbours inside the image; label 0 takes part like any other.
+ * ym_segments_pairs replaces create_edges' loop over the boundary pixels: for a boundary pixel (y, x), y >= 2 and x >= 2,
+ * whose window of rows y-2 .. y+1 and columns x-2 .. x+1 (clipped at the image) holds exactly two distinct non-zero labels
+ * a < b, the pair (a - 1, b - 1) is counted.  It returns every counted pair, its count and the raster index y * width + x
+ * of the first pixel that counted it, sorted by that index (the reference's dict order); an edge of the graph is a pair
+ * with count > 3.  table_slots sizes the device hash table the pairs are counted in (0: sized by the library); a table
+ * that turns out too small is counted again in a larger one, beyond 2^26 slots the call fails with YM_ERR_UNSUPPORTED -- a
+ * pair is never dropped.  cap = the pairs the caller's arrays hold: with more pairs than that the call fails with
+ * YM_ERR_INVALID and *n_pairs = the number needed, nothing else written.  A negative label fails with YM_ERR_INVALID.
+ * Synchronous, on the handle's own stream; outputs are written only after the whole call succeeded. */
+typedef struct ym_segments ym_segments; /* a label image resident on one device */
+ym_segments *ym_segments_create(int device, const int32_t *labels, int width, int height, int pitch_elems);
+int ym_segments_label_range(const ym_segments *sg, int32_t *min_label, int32_t *max_label);
+int ym_segments_stats(ym_segments *sg, int n_labels, int64_t *count, int64_t *sum_x, int64_t *sum_y);
+int ym_segments_boundaries(ym_segments *sg, uint8_t *mask, int64_t mask_bytes);
+int ym_segments_pairs(ym_segments *sg, int table_slots, int cap, int32_t *pairs /* [cap][2] */, int32_t *counts, int64_t *first_index,
+                      int32_t *n_pairs);
+void ym_segments_destroy(ym_segments *sg);
+
 /* ---- introspection for parity tests (state of the LAST completed synchronous match) ---- */
 typedef struct ym_grid_info {
     int32_t width, height, pitch; /* device window (bytes) */

@@ -27,6 +27,8 @@ EXPORTS = (
     "ym_occupancy_create", "ym_occupancy_get_info", "ym_occupancy_read", "ym_occupancy_destroy",
     "ym_map_from_occupancy", "ym_map_from_grid", "ym_map_size", "ym_map_read", "ym_map_destroy", "ym_match_map",
     "ym_raymap_create", "ym_raymap_trace", "ym_raymap_trace_each", "ym_raymap_destroy",
+    "ym_segments_create", "ym_segments_label_range", "ym_segments_stats", "ym_segments_boundaries", "ym_segments_pairs",
+    "ym_segments_destroy",
 )
 
 
@@ -217,6 +219,15 @@ def lib():
     L.ym_raymap_trace_each.argtypes = [vp, dp, C.c_int, dp, C.c_int, C.POINTER(C.c_float), dp, C.POINTER(C.c_int64)]
     L.ym_raymap_destroy.argtypes = [vp]
     L.ym_raymap_destroy.restype = None
+    lp = C.POINTER(C.c_int64)
+    L.ym_segments_create.restype = vp
+    L.ym_segments_create.argtypes = [C.c_int, ip, C.c_int, C.c_int, C.c_int]
+    L.ym_segments_label_range.argtypes = [vp, ip, ip]
+    L.ym_segments_stats.argtypes = [vp, C.c_int, lp, lp, lp]
+    L.ym_segments_boundaries.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int64]
+    L.ym_segments_pairs.argtypes = [vp, C.c_int, C.c_int, ip, ip, lp, ip]
+    L.ym_segments_destroy.argtypes = [vp]
+    L.ym_segments_destroy.restype = None
     _lib = L
     return L
 

@@ -33,3 +33,4 @@
 #include "ym_k_yagpy.hpp"
 #include "ym_k_occupancy.hpp"
 #include "ym_k_raytrace.hpp"
+#include "ym_k_segments.hpp"

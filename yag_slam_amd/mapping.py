@@ -116,6 +116,17 @@ class PoseBuckets(object):
                     out.extend(got)
         return out
 
+    def near_ordered(self, pose, radius):
+        """the scans of `near` in the order `crude_radius_search` returns them (helpers.py:420-431): buckets by their
+        first insertion, scans by insertion within a bucket.  Visits the whole table, as the reference does."""
+        reach = radius + self.res
+        r2 = reach * reach
+        out = []
+        for (ix, iy), got in self.buckets.items():
+            if (ix * self.res - pose.x) ** 2 + (iy * self.res - pose.y) ** 2 < r2:
+                out.extend(got)
+        return out
+
 
 class LoopClosingMapper(SequentialMapper):
     """`GraphSlam.process_scan` + `try_to_close_loop` as the matcher sees them
@@ -277,3 +288,34 @@ class LoopClosingMapper(SequentialMapper):
         self.running_scans = self.running_scans[-self.scan_buffer_len:]
         self.results.append(res)
         return res, closed
+
+    def splice_first_scan(self, scan, radius=5):
+        """The first live scan after a prior map was ingested (`splicing.map_to_graphslam`): the ROS node's "first scan when
+        splicing into a map" (slam_node_ros1:240-253).  `scan.odom_pose` and `scan.corrected_pose` hold the initial pose.
+        num = the largest num + 1; candidates = the pose index's scans around `scan.odom_pose`
+        (`crude_radius_search(odom_pose, radius)`, in its order); `seq_matcher.match_scan(scan, candidates, True, True)`;
+        corrected_pose = best_pose; `add_vertex`; `link_scans(scan, candidates[0], covariance)`; the scan starts the running
+        chain.  Returns the matcher result; `process_scan` continues from here.  With no candidate (the reference fails on
+        `nearby_scans[0]`) a ValueError is raised before anything changes; if the matcher raises, the scan gets its old num back
+        and the mapper is as it was."""
+        if not self.scans:
+            raise ValueError("splice_first_scan: no map was ingested (the mapper holds no vertex)")
+        candidates = self.index.near_ordered(scan.odom_pose, radius)
+        if not candidates:
+            raise ValueError("splice_first_scan: no scan of the map within %g m of (%g, %g)"
+                             % (radius, scan.odom_pose.x, scan.odom_pose.y))
+        had_num, old_num = hasattr(scan, "num"), getattr(scan, "num", None)
+        scan.num = max(s.num for s in self.scans) + 1
+        try:
+            res = self.seq_matcher.match_scan(scan, candidates, True, True)
+        except Exception:  # the matcher raised: the mapper is untouched, and so is the scan's num
+            if had_num:
+                scan.num = old_num
+            else:
+                del scan.num
+            raise
+        scan.corrected_pose = res.best_pose
+        self.add_vertex(scan)
+        self.link_scans(scan, candidates[0], res.covariance)
+        self.running_scans.append(scan)
+        return res

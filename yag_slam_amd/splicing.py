@@ -4,8 +4,10 @@
 (/root/reference/yag_slam/raytracing.py:63-92).  Here every (viewpoint, angle) pair of a call walks in one kernel launch
 (include/yagmatch.h, ym_raymap_*), bit for bit the walk of `trace_ray`, and the scans' device twins are created in one call.
 
-The segmentation (`segment_map`: SLIC from scikit-image, OpenCV morphology) and `create_edges` stay with the caller: they are
-CPU image work.  Their output, the segment centroids, is what `virtual_scans` takes.
+The segmentation (`segment_map`: SLIC from scikit-image, OpenCV morphology) stays with the caller: it is CPU image work.
+Its output, the label image, is what `map_to_graph` takes here: `segment_centroids` (the reference's `determine_centroids`)
+and `segment_edges` (its `create_edges`, `find_boundaries` included) are one pass over the label image each on the device
+(ym_segments_*), and `map_to_graphslam` puts the scans and edges into an empty `mapping.LoopClosingMapper`.
 
 Frames.  `layout="reference"` reproduces `map_to_graph` exactly, quirks included: the image is the one the node passes
 (`cv2.imread(...)[::-1, :, 0]`, slam_node_ros1:138, so row 0 is the lowest y), the pose is `pixel_to_meters` of the centroid
@@ -220,3 +222,177 @@ def virtual_scan_block(map_image, resolution, origin, viewpoints, layout="refere
     block = ScanBlock(ranges, poses, sensor, device)
     block.ranges, block.poses = ranges, poses
     return block
+
+
+class SegmentMap(object):
+    """A label image ([rows][cols], any integer dtype; x = column, y = row; 0 = no segment, 1 .. K = segments) resident on
+    one device.  It is converted once to int32 (a contiguous copy unless it already is int32 with unit column stride)."""
+
+    def __init__(self, segments, device=0):
+        seg = _label_image(segments)
+        self.height, self.width = seg.shape
+        self.device = int(device)
+        self._h = None
+        h = _capi.lib().ym_segments_create(self.device, seg.ctypes.data_as(C.POINTER(C.c_int32)), self.width, self.height,
+                                           seg.strides[0] // 4)
+        if not h:
+            raise _capi.YmError(-1, _capi.last_error())
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("SegmentMap is closed")
+        return self._h
+
+    def label_range(self):
+        """(smallest, largest) label of the image"""
+        lo, hi = C.c_int32(0), C.c_int32(0)
+        _capi.check(_capi.lib().ym_segments_label_range(self._handle(), C.byref(lo), C.byref(hi)))
+        return int(lo.value), int(hi.value)
+
+    def stats(self, n_labels):
+        """(count, sum_x, sum_y), int64 [n_labels] indexed by label; every label must lie in [0, n_labels)"""
+        out = [np.zeros(int(n_labels), dtype=np.int64) for _ in range(3)]
+        lp = C.POINTER(C.c_int64)
+        _capi.check(_capi.lib().ym_segments_stats(self._handle(), int(n_labels), *[o.ctypes.data_as(lp) for o in out]))
+        return tuple(out)
+
+    def boundaries(self):
+        """skimage.segmentation.find_boundaries(segments) with its defaults, as a bool image"""
+        mask = np.zeros((self.height, self.width), dtype=np.uint8)
+        _capi.check(_capi.lib().ym_segments_boundaries(self._handle(), mask.ctypes.data_as(C.POINTER(C.c_uint8)), mask.size))
+        return mask.astype(bool)
+
+    def pairs(self, table_slots=0, cap=1 << 16):
+        """create_edges' table: (pairs int32 [n][2] of (a - 1, b - 1), counts int32 [n], first_index int64 [n]) in the order
+        the reference's dict holds them.  table_slots: the first size of the device hash table (0: the library's)."""
+        ip = C.POINTER(C.c_int32)
+        while True:
+            pairs = np.zeros((cap, 2), dtype=np.int32)
+            counts = np.zeros(cap, dtype=np.int32)
+            first = np.zeros(cap, dtype=np.int64)
+            n = C.c_int32(-1)
+            rc = _capi.lib().ym_segments_pairs(self._handle(), int(table_slots), cap, pairs.ctypes.data_as(ip), counts.ctypes.data_as(ip),
+                                               first.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n))
+            if rc != _capi.YM_OK and n.value > cap:  # the arrays were too short: n says how long they must be
+                cap = int(n.value)
+                continue
+            _capi.check(rc)
+            return pairs[:n.value], counts[:n.value], first[:n.value]
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            _capi.lib().ym_segments_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _label_image(segments):
+    """the label image as int32 with unit column stride and a row stride of whole elements (one conversion at most)"""
+    seg = np.asarray(segments)
+    if seg.ndim != 2 or seg.dtype.kind not in "iu" or seg.size == 0:
+        raise ValueError("segments: a non-empty 2-D integer label image, got %s %s" % (seg.dtype, seg.shape))
+    if seg.shape[0] > 65536 or seg.shape[1] > 65536:
+        raise ValueError("segments: %d x %d pixels, at most 65536 x 65536" % (seg.shape[1], seg.shape[0]))
+    if seg.dtype == np.int32 and seg.strides[1] == 4 and seg.strides[0] >= 4 * seg.shape[1] and seg.strides[0] % 4 == 0:
+        return seg
+    if not np.can_cast(seg.dtype, np.int32) and (int(seg.max()) > np.iinfo(np.int32).max or int(seg.min()) < np.iinfo(np.int32).min):
+        raise ValueError("segments: labels beyond int32")
+    return np.ascontiguousarray(seg, dtype=np.int32)
+
+
+def _checked_stats(sm):
+    """the statistics of labels 0 .. K, after the checks the reference's indexing implies: determine_centroids drops the
+    SMALLEST label present whatever it is (np.unique(...)[1:]) and map_to_graph reads centroid_map[0 .. K - 1], so label 0 must
+    occur and 1 .. K must all be present.  Checked on the device's label range and counts."""
+    lo, hi = sm.label_range()
+    if lo < 0:
+        raise ValueError("segments: a negative label (%d); labels are 0 (no segment) and 1 .. K" % lo)
+    if hi > sm.width * sm.height - 1:
+        raise ValueError("segments: a gap in the labels (largest label %d in an image of %d pixels)" % (hi, sm.width * sm.height))
+    count, sum_x, sum_y = sm.stats(hi + 1)
+    if count[0] == 0:
+        raise ValueError("segments: no pixel holds label 0; the reference drops the smallest label present, which would be "
+                         "segment %d" % lo)
+    missing = np.flatnonzero(count[1:] == 0)
+    if missing.size:
+        raise ValueError("segments: a gap in the labels (label %d of 1 .. %d does not occur)" % (missing[0] + 1, hi))
+    return count, sum_x, sum_y
+
+
+def _checked_pairs(sm):
+    lo, _ = sm.label_range()
+    if lo < 0:
+        raise ValueError("segments: a negative label (%d); labels are 0 (no segment) and 1 .. K" % lo)
+    return sm.pairs()
+
+
+def _centroids_of(stats):
+    count, sum_x, sum_y = stats
+    # one correctly rounded float64 division of exact integers: np.mean of the integer coordinate arrays, bit for bit
+    cx, cy = sum_x[1:] / count[1:], sum_y[1:] / count[1:]
+    return dict(enumerate(zip(cx.tolist(), cy.tolist())))
+
+
+def _edges_of(table, min_count):
+    pairs, counts, _ = table
+    return list(map(tuple, pairs[counts > min_count].tolist()))
+
+
+def segment_centroids(segments, device=0):
+    """determine_centroids (splicing.py:57-65): {index: (x, y)}, index = label - 1, (x, y) the mean column and row of the
+    label's pixels as np.mean gives them.  Raises ValueError when the labels are not 0 and every one of 1 .. K."""
+    with SegmentMap(segments, device) as sm:
+        return _centroids_of(_checked_stats(sm))
+
+
+def segment_edges(segments, device=0, min_count=3):
+    """create_edges (splicing.py:67-80): the (a, b) index pairs, a < b, whose segments share more than `min_count` boundary
+    pixels with exactly the two of them in the 4 x 4 window, in the reference's order.  Raises ValueError on a negative label."""
+    with SegmentMap(segments, device) as sm:
+        return _edges_of(_checked_pairs(sm), min_count)
+
+
+def map_to_graph(map_image, resolution, origin, segments, layout="reference", device=0):
+    """The reference's map_to_graph (splicing.py:82-107) with the label image passed in instead of computed by segment_map:
+    -> (scans, edges), scan i the virtual scan at the centroid of label i + 1 (`virtual_scans`), edges as `segment_edges`.
+    layout="world": the viewpoint of centroid pixel (x, y) is (ox + x res, oy + y res, 0), the frame of the module text."""
+    im = np.asarray(map_image)
+    if layout not in ("reference", "world"):
+        raise ValueError("layout: 'reference' or 'world', got %r" % (layout,))
+    if np.shape(segments) != im.shape:
+        raise ValueError("segments %s and map_image %s differ in shape" % (np.shape(segments), im.shape))
+    with SegmentMap(segments, device) as sm:
+        centroids = _centroids_of(_checked_stats(sm))
+        edges = _edges_of(_checked_pairs(sm), 3)
+    if layout == "world":
+        centroids = [(origin[0] + x * resolution, origin[1] + y * resolution, 0.0) for x, y in _centroid_list(centroids)]
+    return virtual_scans(im, resolution, origin, centroids, layout=layout, device=device), edges
+
+
+def map_to_graphslam(mapper, map_image, resolution, origin, segments, layout="reference", device=0):
+    """map_to_graphslam (splicing.py:109-126) into an EMPTY `mapping.LoopClosingMapper`: `add_vertex` for every scan of
+    `map_to_graph` in order, `link_scans(scan[a], scan[b], identity * 1e-12)` for every edge; `running_scans` stays empty, so
+    the first live scan goes through `mapper.splice_first_scan`.  All scans stay: the reference's "get rid of any nodes that
+    did not have edges" assigns an attribute (`slam_fake.vertices`) that nothing reads, and its renumbering over
+    `graph.vertices` is the identity -- no vertex is removed there, and none is here.  Returns the mapper."""
+    if mapper.scans or mapper.running_scans:
+        raise ValueError("map_to_graphslam: the mapper already holds %d vertices and %d running scans; it must be empty"
+                         % (len(mapper.scans), len(mapper.running_scans)))
+    scans, edges = map_to_graph(map_image, resolution, origin, segments, layout=layout, device=device)
+    for scan in scans:
+        mapper.add_vertex(scan)
+    for a, b in edges:
+        mapper.link_scans(scans[a], scans[b], np.identity(3) * 1e-12)
+    return mapper

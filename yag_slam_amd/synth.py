@@ -202,3 +202,42 @@ def loop_batch_jobs(n_chains, lo=0, hi=None, chain_len=10, scene=None):
     hi = n_chains if hi is None else hi
     poses = chain_poses(n_chains, chain_len=chain_len, scene=scene)
     return [(poses[c][i], 100000 + c * chain_len + i) for c in range(lo, hi) for i in range(chain_len)]
+
+
+def seeded_partition(h, w, n_seeds, seed):
+    """A label image [h][w] int32 with labels 1 .. K: every pixel gets the label of its nearest seed pixel (squared integer
+    distance, the lower label on a tie) -- compact segments like those SLIC cuts a map's free space into, for the tests and
+    timings of `splicing.segment_centroids` / `segment_edges`.  Small problems: K = n_seeds distinct uniformly random seeds,
+    every distance computed.  Large ones (h w n_seeds > 2e8): one seed in every cell of a gy x gx grid with gy gx ~ n_seeds
+    (returned K = gy gx), so the nearest seed lies within two cells and 25 candidates per pixel suffice."""
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.int64)
+    if h * w * n_seeds <= 2e8:
+        flat = rng.choice(h * w, size=n_seeds, replace=False)
+        sy, sx = flat // w, flat % w
+        best = np.full((h, w), np.iinfo(np.int64).max)
+        lab = np.zeros((h, w), dtype=np.int32)
+        for k in range(n_seeds):
+            d = (yy - sy[k]) ** 2 + (xx - sx[k]) ** 2
+            closer = d < best
+            best[closer] = d[closer]
+            lab[closer] = k + 1
+        return lab
+    gy = max(1, int(round(math.sqrt(n_seeds * h / w))))
+    gx = max(1, int(round(n_seeds / gy)))
+    ey, ex = np.linspace(0, h, gy + 1).astype(np.int64), np.linspace(0, w, gx + 1).astype(np.int64)
+    sy = ey[:-1, None] + (rng.random((gy, gx)) * (ey[1:] - ey[:-1])[:, None]).astype(np.int64)
+    sx = ex[None, :-1] + (rng.random((gy, gx)) * (ex[1:] - ex[:-1])[None, :]).astype(np.int64)
+    cy = np.searchsorted(ey, np.arange(h), side="right") - 1
+    cx = np.searchsorted(ex, np.arange(w), side="right") - 1
+    best = np.full((h, w), np.iinfo(np.int64).max)
+    lab = np.zeros((h, w), dtype=np.int32)
+    for dy in range(-2, 3):
+        for dx in range(-2, 3):
+            iy, ix = np.clip(cy + dy, 0, gy - 1), np.clip(cx + dx, 0, gx - 1)
+            k = (iy[:, None] * gx + ix[None, :]).astype(np.int32) + 1
+            d = (yy - sy[iy][:, ix]) ** 2 + (xx - sx[iy][:, ix]) ** 2
+            closer = (d < best) | ((d == best) & (k < lab))
+            best[closer] = d[closer]
+            lab[closer] = k[closer]
+    return lab
