@@ -329,6 +329,48 @@ int ym_segments_pairs(ym_segments *sg, int table_slots, int cap, int32_t *pairs 
                       int32_t *n_pairs);
 void ym_segments_destroy(ym_segments *sg);
 
+/* ---- the pose graph and its optimiser: what the reference hands to the third-party sba_cpp.SPA2d (graph_slam.py:64,
+ * 132-192, 262-272), in fp64 on one device.  The formulation is that of Konolige et al., "Efficient Sparse Pose Adjustment
+ * for 2D Mapping" (2010); sba_cpp itself is not available to this project, so PARITY with it is UNPINNED: the semantics
+ * are this library's own ("Pose-graph optimiser") and are pinned by tests/posegraph_ref.py.
+ * Node i has a pose (x, y, theta); node 0 is held fixed.  A constraint a -> b with mean (zx, zy, ztheta) and information L
+ * (3 x 3 row-major, stored as (L + L^T) / 2) has the residual e_xy = R(theta_a)^T (t_b - t_a) - z_xy, e_theta =
+ * wrap(theta_b - theta_a - ztheta) into (-pi, pi]; chi2 = sum e^T L e.
+ *   ym_graph_create / _destroy     SPA2d() and its destruction
+ *   ym_graph_add_nodes             SPA2d.add_node(x, y, yaw, num), n at a time; num is the running count
+ *   ym_graph_add_constraints       SPA2d.add_constraint(a, b, x, y, yaw, info), n at a time
+ *   ym_graph_get_poses / _size     SPA2d.nodes (x, y, yaw of every node) and its length
+ *   ym_graph_set_poses             (no SPA2d call: re-seeds poses, e.g. to replay an optimisation)
+ *   ym_graph_chi2                  (no SPA2d call: the cost at the current poses)
+ *   ym_graph_linearise             (test hook: chi2, the diagonal blocks of H = J^T L J and the gradient J^T L e, undamped,
+ *                                  node 0 included)
+ *   ym_graph_optimize              SPA2d.compute(iters, lambda, use_csparse, init_tol, max_cg_iters): Levenberg-Marquardt on
+ *                                  (H + lambda diag H) delta = -g; a step that lowers chi2 is kept and lambda halves (not
+ *                                  below 1e-12), otherwise the poses stay and lambda doubles.  It stops after `iters` steps
+ *                                  (status 0), when a kept step gains no more than 1e-9 chi2 (1), when chi2 <= 1e-18 of the
+ *                                  initial chi2 (2), when lambda > 1e10 (3).  Each step is solved by conjugate gradients
+ *                                  preconditioned with the Cholesky factor of the block band |i - j| <= band of the system
+ *                                  (band -1: the largest |a - b| among the constraints with |a - b| <= 16; 0: block-Jacobi).
+ *                                  exact != 0 (use_csparse): relative residual 1e-10, at most min(9 N, 20000) iterations,
+ *                                  cg_tol and max_cg_iters ignored; else those two.  A solve that reaches its cap still
+ *                                  yields a step, which is kept or not by the same rule.
+ * Errors (ym_last_error): a node index out of range, a constraint from a node to itself, a value that is not finite, an
+ * information matrix without a positive diagonal.  Fewer than two nodes or no constraint: ym_graph_optimize succeeds with
+ * zero steps.  The adds and ym_graph_size / _get_poses / _set_poses touch no device.  Synchronous, on the handle's stream. */
+typedef struct ym_graph ym_graph;
+ym_graph *ym_graph_create(int device);
+void ym_graph_destroy(ym_graph *g);
+int ym_graph_add_nodes(ym_graph *g, const double *xyt, int n); /* appended; index = running count */
+int ym_graph_add_constraints(ym_graph *g, const int32_t *from_to, const double *mean_xyt, const double *info9, int n);
+int ym_graph_size(const ym_graph *g, int32_t *nodes, int32_t *constraints);
+int ym_graph_set_poses(ym_graph *g, int first, const double *xyt, int n);
+int ym_graph_get_poses(const ym_graph *g, int first, double *xyt, int n);
+int ym_graph_chi2(ym_graph *g, double *chi2);
+int ym_graph_linearise(ym_graph *g, double *chi2, double *diag9 /* [N][9] */, double *grad3 /* [N][3] */);
+typedef struct ym_opt_params { int32_t iters, exact, max_cg_iters, band /* -1 auto */; double lambda0, cg_tol; } ym_opt_params;
+typedef struct ym_opt_report { double chi2_initial, chi2_final, lambda_final; int32_t lm_steps, accepted, cg_iterations, band, status; } ym_opt_report;
+int ym_graph_optimize(ym_graph *g, const ym_opt_params *p, ym_opt_report *out);
+
 /* ---- introspection for parity tests (state of the LAST completed synchronous match) ---- */
 typedef struct ym_grid_info {
     int32_t width, height, pitch; /* device window (bytes) */

@@ -29,6 +29,8 @@ EXPORTS = (
     "ym_raymap_create", "ym_raymap_trace", "ym_raymap_trace_each", "ym_raymap_destroy",
     "ym_segments_create", "ym_segments_label_range", "ym_segments_stats", "ym_segments_boundaries", "ym_segments_pairs",
     "ym_segments_destroy",
+    "ym_graph_create", "ym_graph_destroy", "ym_graph_add_nodes", "ym_graph_add_constraints", "ym_graph_size", "ym_graph_set_poses",
+    "ym_graph_get_poses", "ym_graph_chi2", "ym_graph_linearise", "ym_graph_optimize",
 )
 
 
@@ -101,6 +103,16 @@ class YmGridInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("width", "height", "pitch", "origin_x", "origin_y", "storage_w",
                                         "storage_h", "roi_x", "roi_y", "roi_w", "roi_h")] + [
         ("pad", C.c_int32), ("offset_x", C.c_double), ("offset_y", C.c_double)]
+
+
+class YmOptParams(C.Structure):
+    _fields_ = [("iters", C.c_int32), ("exact", C.c_int32), ("max_cg_iters", C.c_int32), ("band", C.c_int32),
+                ("lambda0", C.c_double), ("cg_tol", C.c_double)]
+
+
+class YmOptReport(C.Structure):
+    _fields_ = [("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("lambda_final", C.c_double), ("lm_steps", C.c_int32),
+                ("accepted", C.c_int32), ("cg_iterations", C.c_int32), ("band", C.c_int32), ("status", C.c_int32)]
 
 
 _lib = None
@@ -228,6 +240,18 @@ def lib():
     L.ym_segments_pairs.argtypes = [vp, C.c_int, C.c_int, ip, ip, lp, ip]
     L.ym_segments_destroy.argtypes = [vp]
     L.ym_segments_destroy.restype = None
+    L.ym_graph_create.restype = vp
+    L.ym_graph_create.argtypes = [C.c_int]
+    L.ym_graph_destroy.argtypes = [vp]
+    L.ym_graph_destroy.restype = None
+    L.ym_graph_add_nodes.argtypes = [vp, dp, C.c_int]
+    L.ym_graph_add_constraints.argtypes = [vp, ip, dp, dp, C.c_int]
+    L.ym_graph_size.argtypes = [vp, ip, ip]
+    L.ym_graph_set_poses.argtypes = [vp, C.c_int, dp, C.c_int]
+    L.ym_graph_get_poses.argtypes = [vp, C.c_int, dp, C.c_int]
+    L.ym_graph_chi2.argtypes = [vp, dp]
+    L.ym_graph_linearise.argtypes = [vp, dp, dp, dp]
+    L.ym_graph_optimize.argtypes = [vp, C.POINTER(YmOptParams), C.POINTER(YmOptReport)]
     _lib = L
     return L
 

@@ -43,5 +43,6 @@ extern "C" {
 #include "ym_abi_maps.hpp"
 #include "ym_abi_rays.hpp"
 #include "ym_abi_segments.hpp"
+#include "ym_abi_posegraph.hpp"
 #include "ym_abi_debug.hpp"
 }  // extern "C"

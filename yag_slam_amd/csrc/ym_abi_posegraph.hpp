@@ -1,0 +1,285 @@
+// ym_abi_posegraph.hpp -- C ABI: the pose graph and its optimiser (ym_graph_*; ym_k_posegraph.hpp)
+// Part of yagmatch.hip (included inside its extern "C" block); not a header of its own.
+// The host keeps every node and constraint (poses are copied back after an optimisation), so the device arrays are plain
+// mirrors: whatever changed since the last launch is uploaded whole before the next one.
+struct ym_graph {
+    int device;
+    hipStream_t stream = nullptr;
+    std::vector<double> pose, mean, info;
+    std::vector<int32_t> from_to;
+    bool poses_stale = true, edges_stale = true; // the device mirrors are behind the host's vectors
+    int cur = 0;                                 // which of d_pose[2] holds the poses (the other takes the trial step)
+    DevBuf<double> d_pose[2], d_mean, d_info, e_blk, e_grad, e_chi, diag, grad, aband, uband, ubandT, vec, partial, record;
+    DevBuf<int32_t> d_from_to, node_ptr, inc;
+};
+
+static void graph_free(ym_graph *g) {
+    if (!g) return;
+    if (g->stream) {
+        DevGuard guard(g->device);
+        g->d_pose[0].release(); g->d_pose[1].release(); g->d_mean.release(); g->d_info.release(); g->e_blk.release();
+        g->e_grad.release(); g->e_chi.release(); g->diag.release(); g->grad.release(); g->aband.release(); g->uband.release();
+        g->ubandT.release(); g->vec.release(); g->partial.release(); g->record.release(); g->d_from_to.release();
+        g->node_ptr.release(); g->inc.release();
+        (void)hipStreamDestroy(g->stream);
+    }
+    delete g;
+}
+
+ym_graph *ym_graph_create(int device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { set_err(YM_ERR_NO_DEVICE, "no HIP device"); return nullptr; }
+    if (device < 0 || device >= n_dev) { set_err(YM_ERR_NO_DEVICE, "device %d out of range (%d devices)", device, n_dev); return nullptr; }
+    DevGuard guard(device);
+    if (!guard.ok) { set_err(YM_ERR_HIP, "cannot make device %d current", device); return nullptr; }
+    ym_graph *g = new ym_graph();
+    g->device = device;
+    if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
+        g->stream = nullptr;
+        set_err(YM_ERR_HIP, "cannot create a stream on device %d", device);
+        graph_free(g);
+        return nullptr;
+    }
+    return g;
+}
+
+void ym_graph_destroy(ym_graph *g) { graph_free(g); }
+
+static bool graph_finite(const double *v, size_t n) {
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+int ym_graph_add_nodes(ym_graph *g, const double *xyt, int n) {
+    if (!g || n < 0 || (n > 0 && !xyt)) return set_err(YM_ERR_INVALID, "bad argument");
+    if (!graph_finite(xyt, 3 * (size_t)n)) return set_err(YM_ERR_INVALID, "a pose that is not finite");
+    if (g->pose.size() / 3 + (size_t)n > (size_t)(INT32_MAX / 64)) return set_err(YM_ERR_UNSUPPORTED, "too many nodes");
+    g->pose.insert(g->pose.end(), xyt, xyt + 3 * (size_t)n);
+    if (n) g->poses_stale = g->edges_stale = true; // (the incidence lists are per node)
+    return YM_OK;
+}
+
+int ym_graph_add_constraints(ym_graph *g, const int32_t *from_to, const double *mean_xyt, const double *info9, int n) {
+    if (!g || n < 0 || (n > 0 && (!from_to || !mean_xyt || !info9))) return set_err(YM_ERR_INVALID, "bad argument");
+    const int64_t N = (int64_t)(g->pose.size() / 3);
+    if (g->from_to.size() / 2 + (size_t)n > (size_t)(INT32_MAX / 64)) return set_err(YM_ERR_UNSUPPORTED, "too many constraints");
+    for (int i = 0; i < n; i++) { // (nothing is added unless every constraint is good)
+        const int32_t a = from_to[2 * i], b = from_to[2 * i + 1];
+        if (a < 0 || a >= N || b < 0 || b >= N)
+            return set_err(YM_ERR_INVALID, "constraint %d: nodes %d -> %d out of range (%lld nodes)", i, a, b, (long long)N);
+        if (a == b) return set_err(YM_ERR_INVALID, "constraint %d: from a node to itself (%d)", i, a);
+        if (!graph_finite(mean_xyt + 3 * (size_t)i, 3) || !graph_finite(info9 + 9 * (size_t)i, 9))
+            return set_err(YM_ERR_INVALID, "constraint %d: a value that is not finite", i);
+        const double *L = info9 + 9 * (size_t)i;
+        if (!(L[0] > 0.0) || !(L[4] > 0.0) || !(L[8] > 0.0))
+            return set_err(YM_ERR_INVALID, "constraint %d: an information matrix without a positive diagonal", i);
+    }
+    for (int i = 0; i < n; i++) {
+        const double *L = info9 + 9 * (size_t)i;
+        g->from_to.push_back(from_to[2 * i]);
+        g->from_to.push_back(from_to[2 * i + 1]);
+        g->mean.insert(g->mean.end(), mean_xyt + 3 * (size_t)i, mean_xyt + 3 * (size_t)i + 3);
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 3; c++) g->info.push_back((L[3 * r + c] + L[3 * c + r]) / 2.0);
+    }
+    if (n) g->edges_stale = true;
+    return YM_OK;
+}
+
+int ym_graph_size(const ym_graph *g, int32_t *nodes, int32_t *constraints) {
+    if (!g || !nodes || !constraints) return set_err(YM_ERR_INVALID, "null argument");
+    *nodes = (int32_t)(g->pose.size() / 3);
+    *constraints = (int32_t)(g->from_to.size() / 2);
+    return YM_OK;
+}
+
+static int graph_range(const ym_graph *g, int first, const double *xyt, int n) {
+    if (!g || n < 0 || (n > 0 && !xyt)) return set_err(YM_ERR_INVALID, "bad argument");
+    const int64_t N = (int64_t)(g->pose.size() / 3);
+    if (first < 0 || (int64_t)first + n > N) return set_err(YM_ERR_INVALID, "nodes %d .. %lld out of range (%lld nodes)", first, (long long)first + n - 1, (long long)N);
+    return YM_OK;
+}
+
+int ym_graph_set_poses(ym_graph *g, int first, const double *xyt, int n) {
+    int rc = graph_range(g, first, xyt, n);
+    if (rc != YM_OK) return rc;
+    if (!graph_finite(xyt, 3 * (size_t)n)) return set_err(YM_ERR_INVALID, "a pose that is not finite");
+    std::copy(xyt, xyt + 3 * (size_t)n, g->pose.begin() + 3 * (size_t)first);
+    if (n) g->poses_stale = true;
+    return YM_OK;
+}
+
+int ym_graph_get_poses(const ym_graph *g, int first, double *xyt, int n) {
+    int rc = graph_range(g, first, xyt, n);
+    if (rc != YM_OK) return rc;
+    std::copy(g->pose.begin() + 3 * (size_t)first, g->pose.begin() + 3 * ((size_t)first + n), xyt);
+    return YM_OK;
+}
+
+// the device mirrors, the incidence lists and the work arrays of a system of band W; `a` is filled in for the launches
+static int graph_sync(ym_graph *g, int W, ym::PgArgs *a) {
+    const size_t N = g->pose.size() / 3, M = g->from_to.size() / 2, rowlen = 9 * ((size_t)W + 1);
+    int rc;
+    if ((rc = g->d_pose[0].ensure(3 * N)) || (rc = g->d_pose[1].ensure(3 * N))) return rc;
+    if (g->poses_stale) {
+        HIP_TRY(hipMemcpy(g->d_pose[g->cur].p, g->pose.data(), 3 * N * sizeof(double), hipMemcpyHostToDevice));
+        g->poses_stale = false;
+    }
+    if (g->edges_stale) {
+        if ((rc = g->d_from_to.ensure(2 * M)) || (rc = g->d_mean.ensure(3 * M)) || (rc = g->d_info.ensure(9 * M)) ||
+            (rc = g->node_ptr.ensure(N + 1)) || (rc = g->inc.ensure(2 * M)))
+            return rc;
+        std::vector<int32_t> ptr(N + 1, 0), inc(2 * M);
+        for (size_t e = 0; e < 2 * M; e++) ptr[(size_t)g->from_to[e] + 1]++;
+        for (size_t i = 0; i < N; i++) ptr[i + 1] += ptr[i];
+        std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
+        for (size_t e = 0; e < M; e++)
+            for (int side = 0; side < 2; side++) inc[(size_t)fill[(size_t)g->from_to[2 * e + side]]++] = (int32_t)(2 * e + side);
+        HIP_TRY(hipMemcpy(g->d_from_to.p, g->from_to.data(), 2 * M * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(g->d_mean.p, g->mean.data(), 3 * M * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(g->d_info.p, g->info.data(), 9 * M * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(g->node_ptr.p, ptr.data(), (N + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(g->inc.p, inc.data(), 2 * M * sizeof(int32_t), hipMemcpyHostToDevice));
+        g->edges_stale = false;
+    }
+    if ((rc = g->e_blk.ensure(27 * M)) || (rc = g->e_grad.ensure(6 * M)) || (rc = g->e_chi.ensure(M)) || (rc = g->diag.ensure(9 * N)) ||
+        (rc = g->grad.ensure(3 * N)) || (rc = g->aband.ensure(N * rowlen)) || (rc = g->uband.ensure(N * rowlen)) ||
+        (rc = g->ubandT.ensure(N * rowlen)) || (rc = g->vec.ensure(15 * N)) || (rc = g->partial.ensure((M + 255) / 256)) ||
+        (rc = g->record.ensure(ym::kPgRecWords)))
+        return rc;
+    *a = ym::PgArgs{};
+    a->n_nodes = (int32_t)N; a->n_edges = (int32_t)M; a->band = W;
+    a->pose = g->d_pose[g->cur].p; a->trial = g->d_pose[g->cur ^ 1].p;
+    a->from_to = g->d_from_to.p; a->mean = g->d_mean.p; a->info = g->d_info.p; a->node_ptr = g->node_ptr.p; a->inc = g->inc.p;
+    a->e_blk = g->e_blk.p; a->e_grad = g->e_grad.p; a->e_chi = g->e_chi.p; a->diag = g->diag.p; a->grad = g->grad.p;
+    a->aband = g->aband.p; a->uband = g->uband.p; a->ubandT = g->ubandT.p; a->vec = g->vec.p; a->partial = g->partial.p;
+    a->record = g->record.p;
+    return YM_OK;
+}
+
+static unsigned graph_blocks(int n) { return (unsigned)((n + 255) / 256); }
+
+// linearise at a.pose; *chi2 = the sum of the edges' terms
+static int graph_linearise(ym_graph *g, const ym::PgArgs &a, double *chi2) {
+    hipLaunchKernelGGL(ym::pg_linearise_kernel, dim3(graph_blocks(a.n_edges)), dim3(256), 0, g->stream, a);
+    hipLaunchKernelGGL(ym::pg_chi2_kernel<false>, dim3(graph_blocks(a.n_edges)), dim3(256), 0, g->stream, a);
+    hipLaunchKernelGGL(ym::pg_sum_kernel, dim3(1), dim3(256), 0, g->stream, a);
+    HIP_TRY(hipGetLastError());
+    double rec[ym::kPgRecWords];
+    HIP_TRY(hipMemcpyAsync(rec, a.record, sizeof rec, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    *chi2 = rec[ym::kPgRecChi2];
+    return YM_OK;
+}
+
+int ym_graph_chi2(ym_graph *g, double *chi2) {
+    if (!g || !chi2) return set_err(YM_ERR_INVALID, "null argument");
+    if (g->from_to.empty()) { *chi2 = 0.0; return YM_OK; }
+    DEV_GUARD(g->device);
+    ym::PgArgs a;
+    int rc = graph_sync(g, 0, &a);
+    if (rc != YM_OK) return rc;
+    return graph_linearise(g, a, chi2);
+}
+
+int ym_graph_linearise(ym_graph *g, double *chi2, double *diag9, double *grad3) {
+    if (!g || !chi2 || !diag9 || !grad3) return set_err(YM_ERR_INVALID, "null argument");
+    const size_t N = g->pose.size() / 3;
+    if (g->from_to.empty()) {
+        *chi2 = 0.0;
+        std::fill(diag9, diag9 + 9 * N, 0.0);
+        std::fill(grad3, grad3 + 3 * N, 0.0);
+        return YM_OK;
+    }
+    DEV_GUARD(g->device);
+    ym::PgArgs a;
+    int rc = graph_sync(g, 0, &a);
+    if (rc != YM_OK) return rc;
+    a.lambda = 0.0;
+    double c2 = 0.0;
+    if ((rc = graph_linearise(g, a, &c2)) != YM_OK) return rc;
+    hipLaunchKernelGGL(ym::pg_assemble_kernel, dim3(graph_blocks(a.n_nodes)), dim3(256), 0, g->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    HIP_TRY(hipMemcpy(diag9, a.diag, 9 * N * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(grad3, a.grad, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    *chi2 = c2;
+    return YM_OK;
+}
+
+int ym_graph_optimize(ym_graph *g, const ym_opt_params *p, ym_opt_report *out) {
+    if (!g || !p || !out) return set_err(YM_ERR_INVALID, "null argument");
+    if (p->iters < 0 || !(p->lambda0 > 0.0) || !std::isfinite(p->lambda0)) return set_err(YM_ERR_INVALID, "iters >= 0 and lambda0 > 0 are required");
+    if (p->band < -1 || p->band > ym::kPgMaxBand) return set_err(YM_ERR_INVALID, "band %d: -1 (automatic) or 0 .. %d", p->band, ym::kPgMaxBand);
+    if (!p->exact && (p->max_cg_iters < 1 || !(p->cg_tol > 0.0) || !std::isfinite(p->cg_tol)))
+        return set_err(YM_ERR_INVALID, "max_cg_iters >= 1 and cg_tol > 0 are required");
+    const size_t N = g->pose.size() / 3, M = g->from_to.size() / 2;
+    *out = ym_opt_report{};
+    out->lambda_final = p->lambda0;
+    int W = p->band;
+    if (W < 0) { // the largest |a - b| among the edges that are at most kPgMaxBand apart
+        W = 0;
+        for (size_t e = 0; e < M; e++) {
+            const int d = std::abs(g->from_to[2 * e] - g->from_to[2 * e + 1]);
+            if (d <= ym::kPgMaxBand && d > W) W = d;
+        }
+    }
+    out->band = W;
+    if (N < 2 || M == 0) return YM_OK;
+    DEV_GUARD(g->device);
+    ym::PgArgs a;
+    int rc = graph_sync(g, W, &a);
+    if (rc != YM_OK) return rc;
+    g->poses_stale = true; // (until the poses are back on the host: a call that fails leaves the graph as it was)
+    a.cg_tol = p->exact ? 1e-10 : p->cg_tol;
+    a.cg_cap = p->exact ? (int32_t)std::min<size_t>(9 * N, 20000) : p->max_cg_iters;
+    double chi2 = 0.0, lambda = p->lambda0;
+    if ((rc = graph_linearise(g, a, &chi2)) != YM_OK) return rc;
+    const double chi2_0 = chi2;
+    out->chi2_initial = chi2;
+    int status = 0; // 0: the step limit; 1: an accepted step gained no more than 1e-9 chi2; 2: chi2 <= 1e-18 of the initial; 3: lambda > 1e10
+    bool linearised = true;
+    for (int step = 0; step < p->iters; step++) {
+        if (chi2 <= 1e-18 * chi2_0) { status = 2; break; }
+        if (!linearised) {
+            hipLaunchKernelGGL(ym::pg_linearise_kernel, dim3(graph_blocks(a.n_edges)), dim3(256), 0, g->stream, a);
+            linearised = true;
+        }
+        a.lambda = lambda;
+        hipLaunchKernelGGL(ym::pg_assemble_kernel, dim3(graph_blocks(a.n_nodes)), dim3(256), 0, g->stream, a);
+        hipLaunchKernelGGL(ym::pg_solve_kernel, dim3(1), dim3(ym::kPgSolveThreads), 0, g->stream, a);
+        hipLaunchKernelGGL(ym::pg_update_kernel, dim3(graph_blocks(a.n_nodes)), dim3(256), 0, g->stream, a);
+        hipLaunchKernelGGL(ym::pg_chi2_kernel<true>, dim3(graph_blocks(a.n_edges)), dim3(256), 0, g->stream, a);
+        hipLaunchKernelGGL(ym::pg_sum_kernel, dim3(1), dim3(256), 0, g->stream, a);
+        HIP_TRY(hipGetLastError());
+        double rec[ym::kPgRecWords];
+        HIP_TRY(hipMemcpyAsync(rec, a.record, sizeof rec, hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        out->lm_steps++;
+        out->cg_iterations += (int32_t)rec[ym::kPgRecCg];
+        if ((int)rec[ym::kPgRecFlags] & ym::kPgFlagPivot) return set_err(YM_ERR_INVALID, "the system of step %d is not positive definite", step);
+        const double chi2_new = rec[ym::kPgRecChi2];
+        if (chi2_new < chi2) {
+            const double gain = chi2 - chi2_new, before = chi2;
+            g->cur ^= 1;
+            a.pose = g->d_pose[g->cur].p;
+            a.trial = g->d_pose[g->cur ^ 1].p;
+            chi2 = chi2_new;
+            out->accepted++;
+            linearised = false;
+            lambda = std::max(lambda / 2.0, 1e-12);
+            if (gain <= 1e-9 * before) { status = 1; break; }
+        } else { // the poses stay (the trial went to the other buffer)
+            lambda *= 2.0;
+            if (lambda > 1e10) { status = 3; break; }
+        }
+    }
+    if (status == 0 && chi2 <= 1e-18 * chi2_0) status = 2;
+    HIP_TRY(hipMemcpy(g->pose.data(), g->d_pose[g->cur].p, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    g->poses_stale = false;
+    out->chi2_final = chi2;
+    out->lambda_final = lambda;
+    out->status = status;
+    return YM_OK;
+}

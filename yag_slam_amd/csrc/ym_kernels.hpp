@@ -34,3 +34,4 @@
 #include "ym_k_occupancy.hpp"
 #include "ym_k_raytrace.hpp"
 #include "ym_k_segments.hpp"
+#include "ym_k_posegraph.hpp"

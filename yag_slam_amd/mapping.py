@@ -139,9 +139,10 @@ class LoopClosingMapper(SequentialMapper):
     `loop_search_dist`, graph_slam.py:290, and its dropping of the last candidate of the sorted list,
     :284), the two-stage acceptance (coarse loop matcher without penalty >= min_response_coarse, then
     the fine sequential matcher seeded with the coarse pose), first acceptable chain wins.
-    What is not here: the sparse pose adjustment the reference runs after a closure (`SPA2d`, third
-    party, out of the hot path).  An `optimizer` with the same four calls (`add_node`,
-    `add_constraint`, `compute`, `nodes`) may be plugged in; without one the closure only corrects
+    The sparse pose adjustment the reference runs after a closure (`SPA2d`, third party) is what one
+    passes as `optimizer`: `yag_slam_amd.posegraph.PoseGraphOptimizer()` optimises the graph on the
+    device and `run_opt` re-poses every vertex; any object with the same four calls (`add_node`,
+    `add_constraint`, `compute`, `nodes`) works.  Without one (the default) the closure only corrects
     the closing scan.
 
     The reference rejects a low FINE response only when `verbose` is set (`... and self.verbose`,

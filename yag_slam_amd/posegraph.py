@@ -1,0 +1,189 @@
+"""The pose-graph optimiser behind `LoopClosingMapper(optimizer=...)`, `mapfile.from_file(..., optimizer=...)` and the
+reference's `GraphSlam.opt`: the four calls they make on `sba_cpp.SPA2d` (`add_node`, `add_constraint`, `compute`,
+`nodes`; /root/reference/yag_slam/graph_slam.py:64,132-192,262-272), served by `ym_graph_*` of libyagmatch.so in fp64 on
+one device.  The formulation is SPA2d's (Konolige et al. 2010); `sba_cpp` itself is not available to this project, so
+parity with it is NOT pinned: the semantics are DESIGN.md's ("Pose-graph optimiser"), pinned by tests/posegraph_ref.py.
+
+Adds are validated at once and buffered on the host; what is new goes to the library at the next `compute` / `chi2`.  The
+native handle is created then: without a device that raises `YmError`, nothing is computed on the CPU instead.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _capi
+
+STATUS = {0: "step limit", 1: "converged", 2: "residual vanished", 3: "lambda limit"}
+
+
+class OptReport(object):
+    """what one `compute` did (ym_opt_report)"""
+    __slots__ = ("chi2_initial", "chi2_final", "lambda_final", "lm_steps", "accepted", "cg_iterations", "band", "status")
+
+    def __init__(self, rep):
+        for name in self.__slots__:
+            setattr(self, name, getattr(rep, name))
+
+    def __repr__(self):
+        return "OptReport(%s)" % ", ".join("%s=%r" % (n, getattr(self, n)) for n in self.__slots__)
+
+
+class Node(object):
+    """an item of `PoseGraphOptimizer.nodes`"""
+    __slots__ = ("x", "y", "yaw")
+
+    def __init__(self, row):
+        self.x, self.y, self.yaw = float(row[0]), float(row[1]), float(row[2])
+
+    def __repr__(self):
+        return "Node(x=%r, y=%r, yaw=%r)" % (self.x, self.y, self.yaw)
+
+
+class NodeView(object):
+    """`SPA2d.nodes`: a sequence over the rows of one (N, 3) array; items are made when they are asked for"""
+
+    def __init__(self, xyt):
+        self._xyt = xyt
+
+    def __len__(self):
+        return len(self._xyt)
+
+    def __getitem__(self, k):
+        if isinstance(k, slice):
+            return NodeView(self._xyt[k])
+        return Node(self._xyt[k])
+
+    def __iter__(self):
+        return (Node(row) for row in self._xyt)
+
+
+def _finite(*values):
+    return all(math.isfinite(v) for v in values)
+
+
+class PoseGraphOptimizer(object):
+    def __init__(self, device=0):
+        self.device = int(device)
+        self._h = None
+        self._xyt = np.zeros((0, 3))   # every node's pose: as added, or as the last compute left it
+        self._new_nodes = []           # rows of _xyt the library has not seen
+        self._new_edges = []           # (a, b, x, y, yaw, info 3 x 3)
+        self._n_edges = 0
+        self.band = -1                 # compute's preconditioner band: -1 automatic, 0 .. 16 (0: block-Jacobi)
+        self.last_report = None
+
+    # ---- the SPA2d surface
+    def add_node(self, x, y, yaw, num):
+        n = len(self._xyt) + len(self._new_nodes)
+        if int(num) != n:
+            raise ValueError("add_node: num %r, the next node is %d" % (num, n))
+        x, y, yaw = float(x), float(y), float(yaw)
+        if not _finite(x, y, yaw):
+            raise ValueError("add_node: a pose that is not finite")
+        self._new_nodes.append((x, y, yaw))
+
+    def add_constraint(self, a, b, x, y, yaw, info):
+        n = len(self._xyt) + len(self._new_nodes)
+        a, b = int(a), int(b)
+        if not (0 <= a < n and 0 <= b < n):
+            raise ValueError("add_constraint: nodes %d -> %d out of range (%d nodes)" % (a, b, n))
+        if a == b:
+            raise ValueError("add_constraint: from a node to itself (%d)" % a)
+        info = np.array(info, dtype=np.float64)
+        if info.shape != (3, 3):
+            raise ValueError("add_constraint: info must be 3 x 3")
+        x, y, yaw = float(x), float(y), float(yaw)
+        if not _finite(x, y, yaw) or not np.isfinite(info).all():
+            raise ValueError("add_constraint: a value that is not finite")
+        if not (np.diag(info) > 0).all():
+            raise ValueError("add_constraint: an information matrix without a positive diagonal")
+        self._new_edges.append((a, b, x, y, yaw, info))
+        self._n_edges += 1
+
+    def compute(self, iters=100, lam=1.0e-4, use_csparse=True, init_tol=1.0e-9, max_cg_iters=50):
+        """`SPA2d.compute`.  use_csparse: every step solved to a relative residual of 1e-10 (init_tol and max_cg_iters are
+        ignored, as SPA2d's Cholesky path ignores them); otherwise conjugate gradients to init_tol within max_cg_iters."""
+        L = self._flush()
+        p = _capi.YmOptParams(int(iters), int(bool(use_csparse)), int(max_cg_iters), int(self.band), float(lam), float(init_tol))
+        rep = _capi.YmOptReport()
+        _capi.check(L.ym_graph_optimize(self._h, C.byref(p), C.byref(rep)))
+        if len(self._xyt):
+            _capi.check(L.ym_graph_get_poses(self._h, 0, self._xyt.ctypes.data_as(C.POINTER(C.c_double)), len(self._xyt)))
+        self.last_report = OptReport(rep)
+        return self.last_report
+
+    @property
+    def nodes(self):
+        return NodeView(self.nodes_xyt)
+
+    # ---- beyond SPA2d
+    @property
+    def nodes_xyt(self):
+        """(N, 3) float64: x, y, yaw of every node"""
+        if self._new_nodes:
+            return np.concatenate([self._xyt, np.array(self._new_nodes, dtype=np.float64).reshape(-1, 3)])
+        return self._xyt
+
+    @property
+    def n_constraints(self):
+        return self._n_edges
+
+    def chi2(self):
+        L = self._flush()
+        out = C.c_double()
+        _capi.check(L.ym_graph_chi2(self._h, C.byref(out)))
+        return out.value
+
+    def linearise(self):
+        """(chi2, diagonal blocks (N, 3, 3), gradient (N, 3)) of the undamped system at the current poses, node 0 included"""
+        L = self._flush()
+        n = len(self._xyt)
+        chi2, diag, grad = C.c_double(), np.zeros((n, 3, 3)), np.zeros((n, 3))
+        dp = C.POINTER(C.c_double)
+        _capi.check(L.ym_graph_linearise(self._h, C.byref(chi2), diag.ctypes.data_as(dp), grad.ctypes.data_as(dp)))
+        return chi2.value, diag, grad
+
+    def set_poses(self, xyt, first=0):
+        xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
+        L = self._flush()
+        _capi.check(L.ym_graph_set_poses(self._h, int(first), xyt.ctypes.data_as(C.POINTER(C.c_double)), len(xyt)))
+        self._xyt[first:first + len(xyt)] = xyt
+
+    def close(self):
+        """frees the native handle; the optimiser is not used afterwards"""
+        if self._h is not None:
+            _capi.lib().ym_graph_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _flush(self):
+        """the native handle, holding everything added so far"""
+        L = _capi.lib()
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+        if self._h is None:
+            h = L.ym_graph_create(self.device)
+            if not h:
+                raise _capi.YmError(-2, _capi.last_error())
+            self._h = h
+        if self._new_nodes:
+            new = np.ascontiguousarray(np.array(self._new_nodes, dtype=np.float64).reshape(-1, 3))
+            _capi.check(L.ym_graph_add_nodes(self._h, new.ctypes.data_as(dp), len(new)))
+            self._xyt = np.ascontiguousarray(np.concatenate([self._xyt, new]))
+            self._new_nodes = []
+        if self._new_edges:
+            ft = np.ascontiguousarray([(e[0], e[1]) for e in self._new_edges], dtype=np.int32)
+            mean = np.ascontiguousarray([e[2:5] for e in self._new_edges], dtype=np.float64)
+            info = np.ascontiguousarray([e[5] for e in self._new_edges], dtype=np.float64)
+            _capi.check(L.ym_graph_add_constraints(self._h, ft.ctypes.data_as(ip), mean.ctypes.data_as(dp), info.ctypes.data_as(dp),
+                                                   len(ft)))
+            self._new_edges = []
+        return L
+
+
+SPA2d = PoseGraphOptimizer
