@@ -302,7 +302,7 @@ int ym_raymap_trace_each(ym_raymap *rm, const double *starts_xy, int n_starts, c
 void ym_raymap_destroy(ym_raymap *rm);
 
 /* ---- the segment graph of a prior map from its label image: the rest of map_to_graph (yag_slam/splicing.py:57-80 of the
- * reference).  `labels` is the segmentation of the map (segment_map's output: SLIC stays with the caller), int32
+ * reference).  `labels` is the segmentation of the map (segment_map's output: the caller's, or ym_segments_from_map's below), int32
  * [height][pitch_elems], x = column, y = row, 0 = no segment, 1 .. K = segments; 1 x 1 up to 65536 x 65536 pixels.
  * ym_segments_create uploads it and finds the smallest and largest label (ym_segments_label_range returns them).
  * ym_segments_stats replaces determine_centroids' per-segment image scans: count / sum_x / sum_y [n_labels], indexed by
@@ -328,6 +328,42 @@ int ym_segments_boundaries(ym_segments *sg, uint8_t *mask, int64_t mask_bytes);
 int ym_segments_pairs(ym_segments *sg, int table_slots, int cap, int32_t *pairs /* [cap][2] */, int32_t *counts, int64_t *first_index,
                       int32_t *n_pairs);
 void ym_segments_destroy(ym_segments *sg);
+
+/* ---- the map segmenter: a prior map's image to its label image on the device, the reference's segment_map
+ * (yag_slam/splicing.py:32-55) without OpenCV or scikit-image.  `image` is uint8 [h][pitch bytes], x = column, y = row,
+ * 1 x 1 up to 65536 x 65536 pixels.  The pre-processing is the reference's, bit for bit by definition: a[a < 254] = 0,
+ * t = 255 - a, grey dilation then erosion of t with a close_size x close_size square (odd, 1 .. 31; pixels outside the image
+ * take no part, OpenCV's default border for morphology), closed = 255 - t.  ym_map_free_space returns `closed` (w * h
+ * bytes), its exact sum and its count of non-zero ("free") pixels.  The superpixel step is NOT scikit-image's SLIC (whose
+ * masked initialisation draws random samples and whose connectivity pass is a sequential flood fill): PARITY with it is
+ * UNPINNED, the rules are this library's own ("Map segmenter") and are pinned by tests/segmenter_ref.py.
+ * Inside the mask the reference's image is constant and its compactness 0.01, so its SLIC is essentially spatial k-means on
+ * the free pixels; that is what is defined:
+ *   n_segments = int(sum // 600000 * density) unless opts->n_segments > 0; step = max(1, int(sqrt(n_free / n_segments) + 0.5));
+ *   cells of step x step pixels anchored at pixel (0, 0); a cell at least a quarter free (4 count >= step^2) seeds a centre
+ *   at the mean of its free pixels, centres numbered in raster order of cells; `iterations` Lloyd passes (fewer when a
+ *   pass changes no pixel): a free pixel takes the nearest (dx^2 + dy^2 in fp64, ties to the lowest index) of the centres
+ *   seeded in the 5 x 5 cells around its own, none if there is none; then every centre with pixels moves to their mean;
+ *   every 4-connected component of equal assignment with at least min_size = (n_free // n_segments) // min_size_div pixels
+ *   is a segment, numbered 1 .. K by its first pixel in raster order; smaller components become 0 -- a free pixel may end
+ *   up in no segment.
+ * ym_segments_from_map returns the label image resident as a ym_segments (stats, boundaries and pairs run on it in place;
+ * ym_segments_labels reads it, w * h labels).  opts null: n_segments 0, density 1, close_size 11, iterations 10,
+ * min_size_div 4, stage FINAL.  stage ASSIGNED leaves centre index + 1 of every pixel as the label image (the state before
+ * the components: a test hook; info->segments is 0 and info->unlabelled -1 then).  info (nullable) receives the scalars above;
+ * min_size saturates at 2^31 - 1, unlabelled = free pixels with label 0.  Errors (null handle or YM_ERR_INVALID, the text
+ * names the argument): a null image, w or h out of range, pitch < w, close_size even or out of range, n_segments that
+ * comes out below 1, no free pixel, no seeded cell; YM_ERR_UNSUPPORTED when the cells make more than 2^31 - 1 blocks.
+ * Synchronous; outputs are written only after the whole call has succeeded. */
+#define YM_SEGMENT_STAGE_FINAL 0
+#define YM_SEGMENT_STAGE_ASSIGNED 1
+typedef struct ym_segment_opts { int32_t n_segments /* 0: the 600000 rule */; double density; int32_t close_size, iterations, min_size_div, stage; } ym_segment_opts;
+typedef struct ym_segment_info { int64_t sum, n_free; int32_t n_segments, step, seeds, segments, iterations_run, min_size; int64_t unlabelled; } ym_segment_info;
+int ym_map_free_space(int device, const uint8_t *image, int w, int h, int pitch, int close_size, uint8_t *closed, int64_t *sum,
+                      int64_t *n_free);
+ym_segments *ym_segments_from_map(int device, const uint8_t *image, int w, int h, int pitch, const ym_segment_opts *opts,
+                                  ym_segment_info *info);
+int ym_segments_labels(ym_segments *sg, int32_t *labels, int64_t n);
 
 /* ---- the pose graph and its optimiser: what the reference hands to the third-party sba_cpp.SPA2d (graph_slam.py:64,
  * 132-192, 262-272), in fp64 on one device.  The formulation is that of Konolige et al., "Efficient Sparse Pose Adjustment

@@ -28,7 +28,7 @@ EXPORTS = (
     "ym_map_from_occupancy", "ym_map_from_grid", "ym_map_size", "ym_map_read", "ym_map_destroy", "ym_match_map",
     "ym_raymap_create", "ym_raymap_trace", "ym_raymap_trace_each", "ym_raymap_destroy",
     "ym_segments_create", "ym_segments_label_range", "ym_segments_stats", "ym_segments_boundaries", "ym_segments_pairs",
-    "ym_segments_destroy",
+    "ym_segments_destroy", "ym_map_free_space", "ym_segments_from_map", "ym_segments_labels",
     "ym_graph_create", "ym_graph_destroy", "ym_graph_add_nodes", "ym_graph_add_constraints", "ym_graph_size", "ym_graph_set_poses",
     "ym_graph_get_poses", "ym_graph_chi2", "ym_graph_linearise", "ym_graph_optimize",
 )
@@ -114,6 +114,18 @@ class YmOptReport(C.Structure):
     _fields_ = [("chi2_initial", C.c_double), ("chi2_final", C.c_double), ("lambda_final", C.c_double), ("lm_steps", C.c_int32),
                 ("accepted", C.c_int32), ("cg_iterations", C.c_int32), ("band", C.c_int32), ("status", C.c_int32)]
 
+
+class YmSegmentOpts(C.Structure):
+    _fields_ = [("n_segments", C.c_int32), ("density", C.c_double), ("close_size", C.c_int32), ("iterations", C.c_int32),
+                ("min_size_div", C.c_int32), ("stage", C.c_int32)]
+
+
+class YmSegmentInfo(C.Structure):
+    _fields_ = [("sum", C.c_int64), ("n_free", C.c_int64)] + [(n, C.c_int32) for n in (
+        "n_segments", "step", "seeds", "segments", "iterations_run", "min_size")] + [("unlabelled", C.c_int64)]
+
+
+SEGMENT_STAGES = {"final": 0, "assigned": 1}
 
 _lib = None
 
@@ -240,6 +252,11 @@ def lib():
     L.ym_segments_pairs.argtypes = [vp, C.c_int, C.c_int, ip, ip, lp, ip]
     L.ym_segments_destroy.argtypes = [vp]
     L.ym_segments_destroy.restype = None
+    L.ym_map_free_space.argtypes = [C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint8), lp, lp]
+    L.ym_segments_from_map.restype = vp
+    L.ym_segments_from_map.argtypes = [C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.POINTER(YmSegmentOpts),
+                                       C.POINTER(YmSegmentInfo)]
+    L.ym_segments_labels.argtypes = [vp, ip, C.c_int64]
     L.ym_graph_create.restype = vp
     L.ym_graph_create.argtypes = [C.c_int]
     L.ym_graph_destroy.argtypes = [vp]

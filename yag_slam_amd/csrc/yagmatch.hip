@@ -43,6 +43,7 @@ extern "C" {
 #include "ym_abi_maps.hpp"
 #include "ym_abi_rays.hpp"
 #include "ym_abi_segments.hpp"
+#include "ym_abi_segmenter.hpp"
 #include "ym_abi_posegraph.hpp"
 #include "ym_abi_debug.hpp"
 }  // extern "C"

@@ -34,4 +34,5 @@
 #include "ym_k_occupancy.hpp"
 #include "ym_k_raytrace.hpp"
 #include "ym_k_segments.hpp"
+#include "ym_k_segmenter.hpp"
 #include "ym_k_posegraph.hpp"

@@ -4,10 +4,14 @@
 (/root/reference/yag_slam/raytracing.py:63-92).  Here every (viewpoint, angle) pair of a call walks in one kernel launch
 (include/yagmatch.h, ym_raymap_*), bit for bit the walk of `trace_ray`, and the scans' device twins are created in one call.
 
-The segmentation (`segment_map`: SLIC from scikit-image, OpenCV morphology) stays with the caller: it is CPU image work.
-Its output, the label image, is what `map_to_graph` takes here: `segment_centroids` (the reference's `determine_centroids`)
-and `segment_edges` (its `create_edges`, `find_boundaries` included) are one pass over the label image each on the device
-(ym_segments_*), and `map_to_graphslam` puts the scans and edges into an empty `mapping.LoopClosingMapper`.
+The segmentation (`segment_map`; the reference's is OpenCV morphology and SLIC from scikit-image) runs on the device too
+(`free_space`, `SegmentMap.from_map`, ym_segments_from_map): the threshold and the grey closing are the reference's bit for
+bit, the superpixel step is this package's own spatial k-means on the free pixels ("Map segmenter": not
+scikit-image's SLIC; a free pixel in a fragment below the minimum size ends up in no segment).  `map_to_graph` takes a
+caller's label image or, with `segments=None`, segments the map itself and goes on with the resident label image:
+`segment_centroids` (the reference's `determine_centroids`) and `segment_edges` (its `create_edges`, `find_boundaries`
+included) are one pass over the label image each on the device (ym_segments_*), and `map_to_graphslam` puts the scans and
+edges into an empty `mapping.LoopClosingMapper`.
 
 Frames.  `layout="reference"` reproduces `map_to_graph` exactly, quirks included: the image is the one the node passes
 (`cv2.imread(...)[::-1, :, 0]`, slam_node_ros1:138, so row 0 is the lowest y), the pose is `pixel_to_meters` of the centroid
@@ -224,6 +228,10 @@ def virtual_scan_block(map_image, resolution, origin, viewpoints, layout="refere
     return block
 
 
+class SegmentError(_capi.YmError, ValueError):
+    """the map segmenter refused its input (an image that yields no segment is a ValueError) or the library failed"""
+
+
 class SegmentMap(object):
     """A label image ([rows][cols], any integer dtype; x = column, y = row; 0 = no segment, 1 .. K = segments) resident on
     one device.  It is converted once to int32 (a contiguous copy unless it already is int32 with unit column stride)."""
@@ -239,10 +247,38 @@ class SegmentMap(object):
             raise _capi.YmError(-1, _capi.last_error())
         self._h = h
 
+    @classmethod
+    def from_map(cls, map_image, density=1, device=0, n_segments=0, close_size=11, iterations=10, min_size_div=4, stage="final"):
+        """The map segmenter ("Map segmenter"): the label image of an occupancy image (uint8; free = 254 / 255),
+        computed and kept on the device.  n_segments=0: the reference's rule, int(sum of the closed image // 600000 * density).
+        stage="assigned" keeps centre index + 1 of every pixel, the state before the components (a test hook).  `.info` holds
+        sum, n_free, n_segments, step, seeds, segments, iterations_run, min_size, unlabelled.  Raises SegmentError (a
+        ValueError) on an image that yields no segment."""
+        im = _map_image(map_image)
+        opts = _capi.YmSegmentOpts(int(n_segments), float(density), int(close_size), int(iterations), int(min_size_div),
+                                   _capi.SEGMENT_STAGES[stage])
+        info = _capi.YmSegmentInfo()
+        h = _capi.lib().ym_segments_from_map(int(device), im.ctypes.data_as(C.POINTER(C.c_uint8)), im.shape[1], im.shape[0],
+                                             int(im.strides[0]), C.byref(opts), C.byref(info))
+        if not h:
+            raise SegmentError(-1, _capi.last_error())
+        self = cls.__new__(cls)
+        self.height, self.width = im.shape
+        self.device = int(device)
+        self._h = h
+        self.info = {name: int(getattr(info, name)) for name, _ in _capi.YmSegmentInfo._fields_}
+        return self
+
     def _handle(self):
         if self._h is None:
             raise ValueError("SegmentMap is closed")
         return self._h
+
+    def labels(self):
+        """the resident label image as int32 [rows][cols]"""
+        out = np.empty((self.height, self.width), dtype=np.int32)
+        _capi.check(_capi.lib().ym_segments_labels(self._handle(), out.ctypes.data_as(C.POINTER(C.c_int32)), out.size))
+        return out
 
     def label_range(self):
         """(smallest, largest) label of the image"""
@@ -296,6 +332,36 @@ class SegmentMap(object):
             self.close()
         except Exception:
             pass
+
+
+def _map_image(map_image):
+    """the occupancy image as uint8 with unit column stride (a strided view is passed as it is, by its pitch)"""
+    im = np.asarray(map_image)
+    if im.ndim != 2 or im.dtype != np.uint8 or im.size == 0:
+        raise ValueError("map_image: a non-empty 2-D uint8 image, got %s %s" % (im.dtype, im.shape))
+    if im.strides[1] != 1 or im.strides[0] < im.shape[1]:
+        im = np.ascontiguousarray(im)
+    return im
+
+
+def free_space(map_image, close_size=11, device=0):
+    """The pre-processing of the reference's segment_map (splicing.py:33-44), bit for bit: pixels < 254 -> 0, then the grey
+    closing of 255 - image with a close_size x close_size square, inverted back -> (closed uint8, its sum, its non-zero
+    pixels).  Pixels outside the image take no part in a window (OpenCV's default border for morphology)."""
+    im = _map_image(map_image)
+    closed = np.empty(im.shape, dtype=np.uint8)
+    total, n_free = C.c_int64(0), C.c_int64(0)
+    bp = C.POINTER(C.c_uint8)
+    _capi.check(_capi.lib().ym_map_free_space(int(device), im.ctypes.data_as(bp), im.shape[1], im.shape[0], int(im.strides[0]),
+                                              int(close_size), closed.ctypes.data_as(bp), C.byref(total), C.byref(n_free)))
+    return closed, int(total.value), int(n_free.value)
+
+
+def segment_map(map_image, density=1, device=0, **opts):
+    """The reference's segment_map (splicing.py:32-55) on the device -> int32 label image, 0 = no segment, 1 .. K.  The
+    pre-processing is the reference's; the superpixels are `SegmentMap.from_map`'s (its keyword options pass through)."""
+    with SegmentMap.from_map(map_image, density=density, device=device, **opts) as sm:
+        return sm.labels()
 
 
 def _label_image(segments):
@@ -364,16 +430,18 @@ def segment_edges(segments, device=0, min_count=3):
         return _edges_of(_checked_pairs(sm), min_count)
 
 
-def map_to_graph(map_image, resolution, origin, segments, layout="reference", device=0):
-    """The reference's map_to_graph (splicing.py:82-107) with the label image passed in instead of computed by segment_map:
-    -> (scans, edges), scan i the virtual scan at the centroid of label i + 1 (`virtual_scans`), edges as `segment_edges`.
+def map_to_graph(map_image, resolution, origin, segments=None, layout="reference", device=0, density=1):
+    """The reference's map_to_graph (splicing.py:82-107): -> (scans, edges), scan i the virtual scan at the centroid of
+    label i + 1 (`virtual_scans`), edges as `segment_edges`.  segments=None: the map is segmented on the device
+    (`SegmentMap.from_map(map_image, density)`, the reference's `segment_map(map_image, density)` step) and centroids and
+    edges run on the resident label image; otherwise `segments` is the caller's label image.
     layout="world": the viewpoint of centroid pixel (x, y) is (ox + x res, oy + y res, 0), the frame of the module text."""
     im = np.asarray(map_image)
     if layout not in ("reference", "world"):
         raise ValueError("layout: 'reference' or 'world', got %r" % (layout,))
-    if np.shape(segments) != im.shape:
+    if segments is not None and np.shape(segments) != im.shape:
         raise ValueError("segments %s and map_image %s differ in shape" % (np.shape(segments), im.shape))
-    with SegmentMap(segments, device) as sm:
+    with (SegmentMap.from_map(im, density=density, device=device) if segments is None else SegmentMap(segments, device)) as sm:
         centroids = _centroids_of(_checked_stats(sm))
         edges = _edges_of(_checked_pairs(sm), 3)
     if layout == "world":
@@ -381,7 +449,7 @@ def map_to_graph(map_image, resolution, origin, segments, layout="reference", de
     return virtual_scans(im, resolution, origin, centroids, layout=layout, device=device), edges
 
 
-def map_to_graphslam(mapper, map_image, resolution, origin, segments, layout="reference", device=0):
+def map_to_graphslam(mapper, map_image, resolution, origin, segments=None, layout="reference", device=0, density=1):
     """map_to_graphslam (splicing.py:109-126) into an EMPTY `mapping.LoopClosingMapper`: `add_vertex` for every scan of
     `map_to_graph` in order, `link_scans(scan[a], scan[b], identity * 1e-12)` for every edge; `running_scans` stays empty, so
     the first live scan goes through `mapper.splice_first_scan`.  All scans stay: the reference's "get rid of any nodes that
@@ -390,7 +458,8 @@ def map_to_graphslam(mapper, map_image, resolution, origin, segments, layout="re
     if mapper.scans or mapper.running_scans:
         raise ValueError("map_to_graphslam: the mapper already holds %d vertices and %d running scans; it must be empty"
                          % (len(mapper.scans), len(mapper.running_scans)))
-    scans, edges = map_to_graph(map_image, resolution, origin, segments, layout=layout, device=device)
+    more = {"density": density} if density != 1 else {}  # (the default is map_to_graph's own)
+    scans, edges = map_to_graph(map_image, resolution, origin, segments, layout=layout, device=device, **more)
     for scan in scans:
         mapper.add_vertex(scan)
     for a, b in edges:
