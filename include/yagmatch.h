@@ -380,6 +380,14 @@ int ym_segments_labels(ym_segments *sg, int32_t *labels, int64_t n);
  *   ym_graph_chi2                  (no SPA2d call: the cost at the current poses)
  *   ym_graph_linearise             (test hook: chi2, the diagonal blocks of H = J^T L J and the gradient J^T L e, undamped,
  *                                  node 0 included)
+ *   ym_graph_solve                 (test hook: ONE damped solve at the current poses, which do not change.  It linearises,
+ *                                  assembles (H + lambda diag H) with node 0 held and the band chosen as ym_graph_optimize
+ *                                  chooses it, and runs the solve once: delta3 = x, the conjugate-gradient iterate;
+ *                                  precond3 (may be NULL) = z, the last application of the preconditioner.  max_cg_iters
+ *                                  = 0 runs no iteration: x = 0 and z = band(A, band)^-1 b exactly, the factor and both
+ *                                  substitutions alone.  flags: 1 converged, 2 a pivot was not positive, 4 breakdown;
+ *                                  residual: |r| / |b| of the recursively updated r.  Fewer than two nodes or no constraint:
+ *                                  zeros.  The arguments are checked as ym_graph_optimize checks them, the cap from 0.)
  *   ym_graph_optimize              SPA2d.compute(iters, lambda, use_csparse, init_tol, max_cg_iters): Levenberg-Marquardt on
  *                                  (H + lambda diag H) delta = -g; a step that lowers chi2 is kept and lambda halves (not
  *                                  below 1e-12), otherwise the poses stay and lambda doubles.  It stops after `iters` steps
@@ -403,6 +411,9 @@ int ym_graph_set_poses(ym_graph *g, int first, const double *xyt, int n);
 int ym_graph_get_poses(const ym_graph *g, int first, double *xyt, int n);
 int ym_graph_chi2(ym_graph *g, double *chi2);
 int ym_graph_linearise(ym_graph *g, double *chi2, double *diag9 /* [N][9] */, double *grad3 /* [N][3] */);
+int ym_graph_solve(ym_graph *g, int band /* -1 auto, 0 .. 16 */, double lambda, double cg_tol, int max_cg_iters /* >= 0 */,
+                   double *delta3 /* [N][3] */, double *precond3 /* [N][3], may be NULL */, int32_t *band_used,
+                   int32_t *cg_iterations, double *residual, int32_t *flags);
 typedef struct ym_opt_params { int32_t iters, exact, max_cg_iters, band /* -1 auto */; double lambda0, cg_tol; } ym_opt_params;
 typedef struct ym_opt_report { double chi2_initial, chi2_final, lambda_final; int32_t lm_steps, accepted, cg_iterations, band, status; } ym_opt_report;
 int ym_graph_optimize(ym_graph *g, const ym_opt_params *p, ym_opt_report *out);

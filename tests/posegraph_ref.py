@@ -168,3 +168,95 @@ def grid(rows, cols, noise=0.0, seed=0, spacing=0.5):
     truth = np.array([[spacing * (i % cols), spacing * (i // cols), 0.3 * math.sin(0.7 * i)] for i in range(n)])
     pairs = [(i, i + 1) for i in range(n - 1) if (i + 1) % cols] + [(i, i + cols) for i in range(n - cols)]
     return _finish(truth, pairs, noise, rng, jitter=(0.05, 0.05, 0.02))
+
+
+def banded(n, reach, seed, far=2, reverse=0.4, noise=0.02):
+    """n nodes on a gentle spiral whose system has block band `reach`: edges i -> i+1, every i -> i+reach, and a seeded half
+    of the pairs at the distances in between; then `far` seeded edges longer than `reach` when n > reach + 2 (longer than 16,
+    the widest band of the device, where n allows it, so that the automatic band stays `reach`), then one seeded edge a second
+    time when n > 3.  A seeded share `reverse` of all edges is stored as (b, a), with the mean of the reversed pair; from
+    three nodes on at least one in-band edge clear of node 0 is (node 0 is held, its off-diagonal blocks are not assembled),
+    and the repeated edge is clear of node 0 too.  The start is the truth plus N(0, 1) * (0.05, 0.05, 0.02)."""
+    rng = np.random.default_rng(seed)
+    i = np.arange(n)
+    rad, ang = 5.0 + 0.05 * i, 0.15 * i
+    truth = np.stack([rad * np.cos(ang), rad * np.sin(ang), wrap(ang + math.pi / 2)], axis=1)
+    pairs = [(a, a + 1) for a in range(n - 1)] + [(a, a + reach) for a in range(n - reach) if reach > 1]
+    pairs += [(a, a + d) for d in range(2, reach) for a in range(n - d) if rng.random() < 0.5]
+    in_band = len(pairs)
+    if n > reach + 2:
+        least = 17 if n > 18 + far else reach + 1
+        have = set()
+        while len(have) < far:
+            a, b = sorted(int(v) for v in rng.integers(0, n, 2))
+            if b - a >= max(least, reach + 1) and (a, b) not in have:
+                have.add((a, b))
+                pairs.append((a, b))
+    if n > 3:
+        clear = [p for p in pairs[:in_band] if p[0] != 0]
+        pairs.append(clear[int(rng.integers(0, len(clear)))])
+    flip = rng.random(len(pairs)) < reverse
+    clear = [k for k in range(in_band) if pairs[k][0] != 0]
+    if clear and not flip[clear].any():
+        flip[clear[int(rng.integers(0, len(clear)))]] = True
+    pairs = [(b, a) if f else (a, b) for (a, b), f in zip(pairs, flip)]
+    return _finish(truth, pairs, noise, rng, jitter=(0.05, 0.05, 0.02))
+
+
+def auto_band(graph, widest=16):
+    """the band the device picks for band -1: the largest |a - b| among the edges that are at most `widest` apart"""
+    d = np.abs(graph["edges"][:, 0].astype(int) - graph["edges"][:, 1])
+    d = d[d <= widest]
+    return int(d.max()) if len(d) else 0
+
+
+def damped_system(graph, lam, band):
+    """dense (A, M, b) of one step: A = H + lam diag(H) with node 0's rows and columns replaced by the identity, M the
+    blocks of A with |i - j| <= band, b = -g with node 0's entries zero"""
+    h, g = linear_system(graph["poses"], graph["edges"], graph["means"], graph["infos"])
+    h = h.toarray()
+    h = (h + h.T) / 2.0  # (the two off-diagonal blocks of an edge are rounded apart; the device keeps one and transposes it)
+    a = h + lam * np.diag(np.diag(h))
+    a[:3, :] = 0.0
+    a[:, :3] = 0.0
+    a[:3, :3] = np.eye(3)
+    node = np.arange(len(a)) // 3
+    m = np.where(np.abs(node[:, None] - node[None, :]) <= band, a, 0.0)
+    b = -g
+    b[:3] = 0.0
+    return a, m, b
+
+
+def pcg(A, M, b, tol, cap):
+    """The device's recurrence (ym_k_posegraph.hpp, pg_solve_kernel) with a dense solve for M: (x, iterations, |r| / |b| of
+    the recursively updated r)."""
+    import scipy.linalg as sla
+    x, r = np.zeros_like(b), b.copy()
+    bb = float(b @ b)
+    if not bb > 0.0:
+        return x, 0, 0.0
+    fac = sla.cho_factor(M)
+    z = sla.cho_solve(fac, r)
+    p = z.copy()
+    rz, rr, iters = float(r @ z), bb, 0
+    for _ in range(cap):
+        q = A @ p
+        alpha = rz / float(p @ q)
+        x = x + alpha * p
+        r = r - alpha * q
+        rr = float(r @ r)
+        iters += 1
+        if rr <= tol * tol * bb:
+            break
+        z = sla.cho_solve(fac, r)
+        rz_new = float(r @ z)
+        p = z + (rz_new / rz) * p
+        rz = rz_new
+    return x, iters, math.sqrt(rr / bb)
+
+
+def backward_error(M, z, b):
+    """|M z - b|_inf / (|M|_inf |z|_inf + |b|_inf) in np.longdouble: the normwise backward error of z as a solution of M z = b"""
+    M, z, b = (np.asarray(v, dtype=np.longdouble) for v in (M, np.ravel(z), np.ravel(b)))
+    res = np.abs(M @ z - b).max()
+    return float(res / (np.abs(M).sum(axis=1).max() * np.abs(z).max() + np.abs(b).max()))

@@ -30,7 +30,7 @@ EXPORTS = (
     "ym_segments_create", "ym_segments_label_range", "ym_segments_stats", "ym_segments_boundaries", "ym_segments_pairs",
     "ym_segments_destroy", "ym_map_free_space", "ym_segments_from_map", "ym_segments_labels",
     "ym_graph_create", "ym_graph_destroy", "ym_graph_add_nodes", "ym_graph_add_constraints", "ym_graph_size", "ym_graph_set_poses",
-    "ym_graph_get_poses", "ym_graph_chi2", "ym_graph_linearise", "ym_graph_optimize",
+    "ym_graph_get_poses", "ym_graph_chi2", "ym_graph_linearise", "ym_graph_solve", "ym_graph_optimize",
 )
 
 
@@ -268,6 +268,7 @@ def lib():
     L.ym_graph_get_poses.argtypes = [vp, C.c_int, dp, C.c_int]
     L.ym_graph_chi2.argtypes = [vp, dp]
     L.ym_graph_linearise.argtypes = [vp, dp, dp, dp]
+    L.ym_graph_solve.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, dp, dp, ip, ip, dp, ip]
     L.ym_graph_optimize.argtypes = [vp, C.POINTER(YmOptParams), C.POINTER(YmOptReport)]
     _lib = L
     return L

@@ -208,29 +208,75 @@ int ym_graph_linearise(ym_graph *g, double *chi2, double *diag9, double *grad3) 
     return YM_OK;
 }
 
-int ym_graph_optimize(ym_graph *g, const ym_opt_params *p, ym_opt_report *out) {
-    if (!g || !p || !out) return set_err(YM_ERR_INVALID, "null argument");
-    if (p->iters < 0 || !(p->lambda0 > 0.0) || !std::isfinite(p->lambda0)) return set_err(YM_ERR_INVALID, "iters >= 0 and lambda0 > 0 are required");
-    if (p->band < -1 || p->band > ym::kPgMaxBand) return set_err(YM_ERR_INVALID, "band %d: -1 (automatic) or 0 .. %d", p->band, ym::kPgMaxBand);
-    if (!p->exact && (p->max_cg_iters < 1 || !(p->cg_tol > 0.0) || !std::isfinite(p->cg_tol)))
-        return set_err(YM_ERR_INVALID, "max_cg_iters >= 1 and cg_tol > 0 are required");
-    const size_t N = g->pose.size() / 3, M = g->from_to.size() / 2;
-    *out = ym_opt_report{};
-    out->lambda_final = p->lambda0;
-    int W = p->band;
+// the argument checks a solve shares (iters: of the Levenberg-Marquardt loop; cg: whether the tolerance and the cap count, the
+// cap at least min_cg) and the band it runs with
+static int graph_solve_args(const ym_graph *g, int iters, double lambda, int band, bool cg, int max_cg_iters, int min_cg, double cg_tol, int *W_out) {
+    if (iters < 0 || !(lambda > 0.0) || !std::isfinite(lambda)) return set_err(YM_ERR_INVALID, "iters >= 0 and lambda0 > 0 are required");
+    if (band < -1 || band > ym::kPgMaxBand) return set_err(YM_ERR_INVALID, "band %d: -1 (automatic) or 0 .. %d", band, ym::kPgMaxBand);
+    if (cg && (max_cg_iters < min_cg || !(cg_tol > 0.0) || !std::isfinite(cg_tol)))
+        return set_err(YM_ERR_INVALID, "max_cg_iters >= %d and cg_tol > 0 are required", min_cg);
+    int W = band;
     if (W < 0) { // the largest |a - b| among the edges that are at most kPgMaxBand apart
         W = 0;
-        for (size_t e = 0; e < M; e++) {
+        for (size_t e = 0; e < g->from_to.size() / 2; e++) {
             const int d = std::abs(g->from_to[2 * e] - g->from_to[2 * e + 1]);
             if (d <= ym::kPgMaxBand && d > W) W = d;
         }
     }
+    *W_out = W;
+    return YM_OK;
+}
+
+int ym_graph_solve(ym_graph *g, int band, double lambda, double cg_tol, int max_cg_iters, double *delta3, double *precond3,
+                   int32_t *band_used, int32_t *cg_iterations, double *residual, int32_t *flags) {
+    if (!g || !delta3 || !band_used || !cg_iterations || !residual || !flags) return set_err(YM_ERR_INVALID, "null argument");
+    int W = 0;
+    int rc = graph_solve_args(g, 0, lambda, band, true, max_cg_iters, 0, cg_tol, &W);
+    if (rc != YM_OK) return rc;
+    const size_t N = g->pose.size() / 3, M = g->from_to.size() / 2;
+    *band_used = W;
+    *cg_iterations = 0;
+    *residual = 0.0;
+    *flags = 0;
+    std::fill(delta3, delta3 + 3 * N, 0.0);
+    if (precond3) std::fill(precond3, precond3 + 3 * N, 0.0);
+    if (N < 2 || M == 0) return YM_OK;
+    DEV_GUARD(g->device);
+    ym::PgArgs a;
+    if ((rc = graph_sync(g, W, &a)) != YM_OK) return rc;
+    a.lambda = lambda;
+    a.cg_tol = cg_tol;
+    a.cg_cap = max_cg_iters;
+    double chi2 = 0.0;
+    if ((rc = graph_linearise(g, a, &chi2)) != YM_OK) return rc;
+    HIP_TRY(hipMemsetAsync(a.vec, 0, 15 * N * sizeof(double), g->stream)); // (a right-hand side of zero leaves z unwritten)
+    hipLaunchKernelGGL(ym::pg_assemble_kernel, dim3(graph_blocks(a.n_nodes)), dim3(256), 0, g->stream, a);
+    hipLaunchKernelGGL(ym::pg_solve_kernel, dim3(1), dim3(ym::kPgSolveThreads), 0, g->stream, a);
+    HIP_TRY(hipGetLastError());
+    double rec[ym::kPgRecWords];
+    HIP_TRY(hipMemcpyAsync(rec, a.record, sizeof rec, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    HIP_TRY(hipMemcpy(delta3, a.vec, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    if (precond3) HIP_TRY(hipMemcpy(precond3, a.vec + 6 * N, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    *cg_iterations = (int32_t)rec[ym::kPgRecCg];
+    *residual = rec[ym::kPgRecResidual];
+    *flags = (int32_t)rec[ym::kPgRecFlags];
+    return YM_OK;
+}
+
+int ym_graph_optimize(ym_graph *g, const ym_opt_params *p, ym_opt_report *out) {
+    if (!g || !p || !out) return set_err(YM_ERR_INVALID, "null argument");
+    int W = 0;
+    int rc = graph_solve_args(g, p->iters, p->lambda0, p->band, !p->exact, p->max_cg_iters, 1, p->cg_tol, &W);
+    if (rc != YM_OK) return rc;
+    const size_t N = g->pose.size() / 3, M = g->from_to.size() / 2;
+    *out = ym_opt_report{};
+    out->lambda_final = p->lambda0;
     out->band = W;
     if (N < 2 || M == 0) return YM_OK;
     DEV_GUARD(g->device);
     ym::PgArgs a;
-    int rc = graph_sync(g, W, &a);
-    if (rc != YM_OK) return rc;
+    if ((rc = graph_sync(g, W, &a)) != YM_OK) return rc;
     g->poses_stale = true; // (until the poses are back on the host: a call that fails leaves the graph as it was)
     a.cg_tol = p->exact ? 1e-10 : p->cg_tol;
     a.cg_cap = p->exact ? (int32_t)std::min<size_t>(9 * N, 20000) : p->max_cg_iters;

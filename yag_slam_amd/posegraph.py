@@ -144,6 +144,20 @@ class PoseGraphOptimizer(object):
         _capi.check(L.ym_graph_linearise(self._h, C.byref(chi2), diag.ctypes.data_as(dp), grad.ctypes.data_as(dp)))
         return chi2.value, diag, grad
 
+    def solve_step(self, lam, band=None, cg_tol=1.0e-10, max_cg_iters=0):
+        """One damped solve at the current poses, which stay (ym_graph_solve, a test hook): (delta (N, 3), z (N, 3), band,
+        iterations, residual, flags).  delta is the conjugate-gradient iterate and z the last application of the
+        preconditioner; with max_cg_iters = 0 delta is 0 and z = band(A, band)^-1 b.  band None: `self.band`."""
+        L = self._flush()
+        n = len(self._xyt)
+        delta, z = np.zeros((n, 3)), np.zeros((n, 3))
+        used, iters, res, flags = C.c_int32(), C.c_int32(), C.c_double(), C.c_int32()
+        dp = C.POINTER(C.c_double)
+        _capi.check(L.ym_graph_solve(self._h, int(self.band if band is None else band), float(lam), float(cg_tol), int(max_cg_iters),
+                                     delta.ctypes.data_as(dp), z.ctypes.data_as(dp), C.byref(used), C.byref(iters), C.byref(res),
+                                     C.byref(flags)))
+        return delta, z, used.value, iters.value, res.value, flags.value
+
     def set_poses(self, xyt, first=0):
         xyt = np.ascontiguousarray(xyt, dtype=np.float64).reshape(-1, 3)
         L = self._flush()
