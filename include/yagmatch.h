@@ -269,15 +269,23 @@ int ym_match_map(ym_matcher *m, const ym_map *map, double ox, double oy, const y
  * from its pose (open_karto OccupancyGrid::CreateFromScans): cells count passes and end-point hits, a cell passed more
  * than twice is occupied when hits / passes > 0.1, else free.  image[y][x] uses the codes the ROS node reads: 0 occupied,
  * 200 unknown, 255 free; row 0 is the lowest y; cell (0, 0) is at world (offset_x, offset_y).  Parity unpinned (the
- * wheel's source is not in the reference tree). */
+ * wheel's source is not in the reference tree).
+ *   ym_occupancy_create_counted    (test hook: the same rendering by the same launches, and the handle also keeps a host copy
+ *                                  of the two count arrays the image is decided from, which ym_occupancy_create frees unread)
+ *   ym_occupancy_read_counts       (test hook: pass[height][width] = how often a ray crossed or ended in the cell, the valid
+ *                                  end point counted twice; hits[height][width] = valid end points in it.  `cells` is the
+ *                                  length of each array.  On a handle of ym_occupancy_create, or with cells < width * height,
+ *                                  it fails and writes nothing.) */
 typedef struct ym_occupancy ym_occupancy;
 typedef struct ym_occupancy_info {
     int32_t width, height;
     double offset_x, offset_y, resolution;
 } ym_occupancy_info;
 ym_occupancy *ym_occupancy_create(const ym_scan *const *scans, int n_scans, double resolution, double range_threshold);
+ym_occupancy *ym_occupancy_create_counted(const ym_scan *const *scans, int n_scans, double resolution, double range_threshold);
 int ym_occupancy_get_info(const ym_occupancy *og, ym_occupancy_info *info);
 int ym_occupancy_read(const ym_occupancy *og, uint8_t *image, int64_t image_bytes); /* width*height bytes */
+int ym_occupancy_read_counts(const ym_occupancy *og, uint32_t *pass, uint32_t *hits, int64_t cells);
 void ym_occupancy_destroy(ym_occupancy *og);
 
 /* ---- virtual scans from an occupancy image: the ray casting of the ROS node's "start in a prior map" path

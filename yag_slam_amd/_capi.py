@@ -24,7 +24,8 @@ EXPORTS = (
     "ym_profile_enable",
     "ym_profile_read", "ym_cache_stats", "ym_debug_counters",
     "ym_coarse_dims", "ym_match_slice_begin", "ym_match_slice_finish",
-    "ym_occupancy_create", "ym_occupancy_get_info", "ym_occupancy_read", "ym_occupancy_destroy",
+    "ym_occupancy_create", "ym_occupancy_create_counted", "ym_occupancy_get_info", "ym_occupancy_read", "ym_occupancy_read_counts",
+    "ym_occupancy_destroy",
     "ym_map_from_occupancy", "ym_map_from_grid", "ym_map_size", "ym_map_read", "ym_map_destroy", "ym_match_map",
     "ym_raymap_create", "ym_raymap_trace", "ym_raymap_trace_each", "ym_raymap_destroy",
     "ym_segments_create", "ym_segments_label_range", "ym_segments_stats", "ym_segments_boundaries", "ym_segments_pairs",
@@ -223,8 +224,11 @@ def lib():
     L.ym_match_slice_finish.argtypes = [vp, C.POINTER(YmResult)]
     L.ym_occupancy_create.restype = vp
     L.ym_occupancy_create.argtypes = [C.POINTER(vp), C.c_int, C.c_double, C.c_double]
+    L.ym_occupancy_create_counted.restype = vp
+    L.ym_occupancy_create_counted.argtypes = [C.POINTER(vp), C.c_int, C.c_double, C.c_double]
     L.ym_occupancy_get_info.argtypes = [vp, C.POINTER(YmOccupancyInfo)]
     L.ym_occupancy_read.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int64]
+    L.ym_occupancy_read_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int64]
     L.ym_occupancy_destroy.argtypes = [vp]
     L.ym_occupancy_destroy.restype = None
     L.ym_map_from_occupancy.restype = vp

@@ -195,7 +195,8 @@ int ym_match_map(ym_matcher *m, const ym_map *mp, double ox, double oy, const ym
 }
 
 // ---- occupancy-grid rendering (karto_scanmatcher.create_occupancy_grid)
-ym_occupancy *ym_occupancy_create(const ym_scan *const *scans, int n_scans, double resolution, double range_threshold) {
+// keep_counts (ym_occupancy_create_counted, a test hook): the pass and hit counts are copied to the host before they are freed
+static ym_occupancy *occupancy_render(const ym_scan *const *scans, int n_scans, double resolution, double range_threshold, bool keep_counts) {
     if (!scans || n_scans <= 0) { set_err(YM_ERR_INVALID, "no scans"); return nullptr; }
     if (!(resolution > 0) || !(range_threshold > 0)) { set_err(YM_ERR_INVALID, "resolution and range_threshold must be > 0"); return nullptr; }
     const int device = scans[0] ? scans[0]->device : -1;
@@ -262,6 +263,10 @@ ym_occupancy *ym_occupancy_create(const ym_scan *const *scans, int n_scans, doub
                     og->info.offset_x = x0; og->info.offset_y = y0; og->info.resolution = resolution;
                     og->image.resize(n);
                     ok = ok && hipGetLastError() == hipSuccess && hipMemcpy(og->image.data(), d_img, n, hipMemcpyDeviceToHost) == hipSuccess;
+                    if (ok && keep_counts) {
+                        og->counts.resize(2 * n);
+                        ok = hipMemcpy(og->counts.data(), d_cnt, 2 * n * sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess;
+                    }
                 }
             }
         }
@@ -278,6 +283,14 @@ ym_occupancy *ym_occupancy_create(const ym_scan *const *scans, int n_scans, doub
     return og;
 }
 
+ym_occupancy *ym_occupancy_create(const ym_scan *const *scans, int n_scans, double resolution, double range_threshold) {
+    return occupancy_render(scans, n_scans, resolution, range_threshold, false);
+}
+
+ym_occupancy *ym_occupancy_create_counted(const ym_scan *const *scans, int n_scans, double resolution, double range_threshold) {
+    return occupancy_render(scans, n_scans, resolution, range_threshold, true);
+}
+
 int ym_occupancy_get_info(const ym_occupancy *og, ym_occupancy_info *info) {
     if (!og || !info) return set_err(YM_ERR_INVALID, "null argument");
     *info = og->info;
@@ -288,6 +301,16 @@ int ym_occupancy_read(const ym_occupancy *og, uint8_t *image, int64_t image_byte
     if (!og || !image) return set_err(YM_ERR_INVALID, "null argument");
     if ((size_t)image_bytes < og->image.size()) return set_err(YM_ERR_INVALID, "buffer too small: need %zu bytes", og->image.size());
     std::memcpy(image, og->image.data(), og->image.size());
+    return YM_OK;
+}
+
+int ym_occupancy_read_counts(const ym_occupancy *og, uint32_t *pass, uint32_t *hits, int64_t cells) {
+    if (!og || !pass || !hits) return set_err(YM_ERR_INVALID, "null argument");
+    const size_t n = og->image.size();
+    if (og->counts.size() != 2 * n) return set_err(YM_ERR_INVALID, "this grid was made without counts: use ym_occupancy_create_counted");
+    if (cells < 0 || (size_t)cells < n) return set_err(YM_ERR_INVALID, "buffers too small: need %zu cells each", n);
+    std::memcpy(pass, og->counts.data(), n * sizeof(uint32_t));
+    std::memcpy(hits, og->counts.data() + n, n * sizeof(uint32_t));
     return YM_OK;
 }
 

@@ -11,6 +11,7 @@ struct ym_occupancy {
     int device;
     ym_occupancy_info info;
     std::vector<uint8_t> image; // [height][width], row 0 = lowest y
+    std::vector<uint32_t> counts; // ym_occupancy_create_counted only: pass [height][width], then hits [height][width]
 };
 
 struct ym_batch {

@@ -20,12 +20,25 @@ class OccupancyGrid(object):
         self.resolution = resolution
 
 
-def create_occupancy_grid(scans, resolution, range_threshold, device=0):
-    """scans: yag_slam_amd.models.LocalizedRangeScan (or their native handles, as the reference passes `v.obj._scan`)"""
+def _handle(s, device):
+    """ym_scan* of one element: a scan's device twin, or a handle as a plain int, a numpy integer (an element of
+    ScanBlock.handles), a ctypes pointer or None (a null scan, which the library refuses)"""
+    if hasattr(s, "native"):
+        return s.native(device)
+    if s is None or isinstance(s, C.c_void_p):
+        return s
+    return int(s)
+
+
+def create_occupancy_grid(scans, resolution, range_threshold, device=0, counts=False):
+    """scans: yag_slam_amd.models.LocalizedRangeScan (or their native handles, as the reference passes `v.obj._scan`), or a
+    models.ScanBlock.  counts=True (a test hook, ym_occupancy_create_counted): the grid also has `.passes` and `.hits`, uint32
+    [height][width], the counts the image is decided from."""
     L = _capi.lib()
-    handles = [s.native(device) if hasattr(s, "native") else s for s in scans]
+    handles = [_handle(s, device) for s in getattr(scans, "handles", scans)]
     arr = (C.c_void_p * max(1, len(handles)))(*handles)
-    h = L.ym_occupancy_create(arr, len(handles), float(resolution), float(range_threshold))
+    create = L.ym_occupancy_create_counted if counts else L.ym_occupancy_create
+    h = create(arr, len(handles), float(resolution), float(range_threshold))
     if not h:
         raise _capi.YmError(-1, _capi.last_error())
     try:
@@ -33,6 +46,13 @@ def create_occupancy_grid(scans, resolution, range_threshold, device=0):
         _capi.check(L.ym_occupancy_get_info(h, C.byref(info)))
         image = np.empty((info.height, info.width), dtype=np.uint8)
         _capi.check(L.ym_occupancy_read(h, image.ctypes.data_as(C.POINTER(C.c_uint8)), image.size))
+        if counts:
+            passes, hits = np.empty(image.shape, dtype=np.uint32), np.empty(image.shape, dtype=np.uint32)
+            u32 = C.POINTER(C.c_uint32)
+            _capi.check(L.ym_occupancy_read_counts(h, passes.ctypes.data_as(u32), hits.ctypes.data_as(u32), image.size))
     finally:
         L.ym_occupancy_destroy(h)
-    return OccupancyGrid(image, Pose2(info.offset_x, info.offset_y, 0.0), info.resolution)
+    g = OccupancyGrid(image, Pose2(info.offset_x, info.offset_y, 0.0), info.resolution)
+    if counts:
+        g.passes, g.hits = passes, hits
+    return g
