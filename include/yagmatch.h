@@ -309,6 +309,66 @@ int ym_raymap_trace_each(ym_raymap *rm, const double *starts_xy, int n_starts, c
                          double *length, int64_t *capped);
 void ym_raymap_destroy(ym_raymap *rm);
 
+/* ---- locate a scan set anywhere in a prebuilt map: the exact best hypotheses over the whole map and all headings, by
+ * branch and bound over a max pyramid of the map (no counterpart in the reference, whose node is told
+ * its initial pose).  YM_SEM_YAGPY matchers only.
+ * Definition.  g8 = the map's byte grid (0 .. 100), W x H, cell (cx, cy) centred at world (ox + cx res, oy + cy res), res = the
+ * matcher's resolution.  The point set is ym_match_map's: the valid point readings of all query scans at their own poses minus
+ * the mean query position, heading 0; point_stride s keeps points 0, s, 2s, ...; nq = the number kept (1 .. 65536).  For
+ * heading k with (c, s) = dir_cs[k] and point P: r = (P.x c - P.y s, P.y c + P.x s), d = (rint(r.x / res), rint(r.y / res)),
+ * every |d| <= 32767 or the call fails with YM_ERR_UNSUPPORTED.  S(k, cx, cy) = sum over the points of
+ * g8[cy + d.y][cx + d.x], a read outside the map counting 0, for cx in [0, W), cy in [0, H); response = S / (100 nq).
+ * The call returns the top_k hypotheses with S >= ceil(min_response * 100 * nq), ordered by S descending, ties by ascending
+ * index = (k H + cy) W + cx, and how many there are (fewer than top_k may exist) -- exactly this list whatever `levels`,
+ * max_nodes or the launch order are.  pose = (ox + cx res, oy + cy res, atan2(sin_k, cos_k)): the set's centre.
+ *   ym_locator_create    builds the pyramid (levels 0 .. L of window maxima over 2^j x 2^j cells, with their low-side margins) and
+ *                        allocates the two frontier buffers of max_nodes entries (8 bytes each).  levels < 0: the largest L with
+ *                        2^L <= min(W, H) / 4, at most 6.  An explicit L > 8, or one whose top-level node is wider than the map's short
+ *                        side (2^L > min(W, H)), is REFUSED with YM_ERR_INVALID, not clamped.  max_nodes <= 0: 2^25; at most 2^30.  The
+ *                        top-level nodes are searched in chunks: as many, in (k, Y, X) order, as can be fully expanded within
+ *                        max_nodes entries; if a single one cannot, create fails with YM_ERR_INVALID before anything is launched.
+ *                        Maps up to 65536 cells per axis.  The handle copies the map's bytes (the map may be destroyed) and uses the
+ *                        matcher's stream and resolution (the matcher must outlive it).
+ *   ym_locator_get_info  width, height, levels, max_nodes, device bytes held
+ *   ym_locator_read_level (test hook) level `level` of the pyramid over [0, W) x [0, H), n >= W H bytes
+ *   ym_locator_locate    opts null: top_k 16, point_stride 1, min_response 0.  out holds top_k entries; points_out (nullable)
+ *                        receives the nq points the search used; stats (nullable) nq, the number of chunks, and per level the
+ *                        nodes the exact pass scored and those that survived (at level 0: the leaves passed to the top-K merge),
+ *                        and the nodes the probes scored besides.
+ *                        n_angles * W * H must stay below 2^40 (YM_ERR_UNSUPPORTED).  Synchronous; never throws.
+ *                        YM_ERR_INVALID: a null argument, n_queries outside [1, 64], a query that is null or on another device,
+ *                        n_angles outside [1, 65536], top_k outside [1, 64], point_stride < 1 or no valid reading, min_response < 0.
+ *                        On an error nothing is written. */
+typedef struct ym_locator ym_locator;
+typedef struct ym_locator_info {
+    int32_t width, height, levels, reserved;
+    int64_t max_nodes, bytes;
+} ym_locator_info;
+typedef struct ym_locate_opts {
+    int32_t top_k, point_stride;
+    double min_response;
+} ym_locate_opts;
+typedef struct ym_locate_candidate {
+    int32_t score;          /* S */
+    int32_t k, cx, cy;      /* heading index, cell */
+    int64_t index;          /* (k H + cy) W + cx */
+    double response;        /* S / (100 nq) */
+    double pose[3];         /* world pose of the set's centre */
+} ym_locate_candidate;
+typedef struct ym_locate_stats {
+    int32_t nq, chunks;
+    int64_t nodes[9];       /* scored per level (index = level) */
+    int64_t survivors[9];   /* of those, not pruned */
+    int64_t probe_nodes;    /* scored besides, by the probes that raise the threshold before each chunk's exact pass */
+} ym_locate_stats;
+ym_locator *ym_locator_create(ym_matcher *m, const ym_map *map, int levels, int64_t max_nodes);
+int ym_locator_get_info(const ym_locator *lc, ym_locator_info *info);
+int ym_locator_read_level(const ym_locator *lc, int level, uint8_t *out, int64_t n);
+int ym_locator_locate(ym_locator *lc, double ox, double oy, const ym_scan *const *queries, int n_queries, const double *dir_cs,
+                      int n_angles, const ym_locate_opts *opts, ym_locate_candidate *out, int *n_found, double *points_out,
+                      ym_locate_stats *stats);
+void ym_locator_destroy(ym_locator *lc);
+
 /* ---- the segment graph of a prior map from its label image: the rest of map_to_graph (yag_slam/splicing.py:57-80 of the
  * reference).  `labels` is the segmentation of the map (segment_map's output: the caller's, or ym_segments_from_map's below), int32
  * [height][pitch_elems], x = column, y = row, 0 = no segment, 1 .. K = segments; 1 x 1 up to 65536 x 65536 pixels.

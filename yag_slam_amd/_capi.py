@@ -28,6 +28,7 @@ EXPORTS = (
     "ym_occupancy_destroy",
     "ym_map_from_occupancy", "ym_map_from_grid", "ym_map_size", "ym_map_read", "ym_map_destroy", "ym_match_map",
     "ym_raymap_create", "ym_raymap_trace", "ym_raymap_trace_each", "ym_raymap_destroy",
+    "ym_locator_create", "ym_locator_get_info", "ym_locator_read_level", "ym_locator_locate", "ym_locator_destroy",
     "ym_segments_create", "ym_segments_label_range", "ym_segments_stats", "ym_segments_boundaries", "ym_segments_pairs",
     "ym_segments_destroy", "ym_map_free_space", "ym_segments_from_map", "ym_segments_labels",
     "ym_graph_create", "ym_graph_destroy", "ym_graph_add_nodes", "ym_graph_add_constraints", "ym_graph_size", "ym_graph_set_poses",
@@ -124,6 +125,25 @@ class YmSegmentOpts(C.Structure):
 class YmSegmentInfo(C.Structure):
     _fields_ = [("sum", C.c_int64), ("n_free", C.c_int64)] + [(n, C.c_int32) for n in (
         "n_segments", "step", "seeds", "segments", "iterations_run", "min_size")] + [("unlabelled", C.c_int64)]
+
+
+class YmLocatorInfo(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("levels", C.c_int32), ("reserved", C.c_int32),
+                ("max_nodes", C.c_int64), ("bytes", C.c_int64)]
+
+
+class YmLocateOpts(C.Structure):
+    _fields_ = [("top_k", C.c_int32), ("point_stride", C.c_int32), ("min_response", C.c_double)]
+
+
+class YmLocateCandidate(C.Structure):
+    _fields_ = [("score", C.c_int32), ("k", C.c_int32), ("cx", C.c_int32), ("cy", C.c_int32), ("index", C.c_int64),
+                ("response", C.c_double), ("pose", C.c_double * 3)]
+
+
+class YmLocateStats(C.Structure):
+    _fields_ = [("nq", C.c_int32), ("chunks", C.c_int32), ("nodes", C.c_int64 * 9), ("survivors", C.c_int64 * 9),
+                ("probe_nodes", C.c_int64)]
 
 
 SEGMENT_STAGES = {"final": 0, "assigned": 1}
@@ -247,6 +267,14 @@ def lib():
     L.ym_raymap_trace_each.argtypes = [vp, dp, C.c_int, dp, C.c_int, C.POINTER(C.c_float), dp, C.POINTER(C.c_int64)]
     L.ym_raymap_destroy.argtypes = [vp]
     L.ym_raymap_destroy.restype = None
+    L.ym_locator_create.restype = vp
+    L.ym_locator_create.argtypes = [vp, vp, C.c_int, C.c_int64]
+    L.ym_locator_get_info.argtypes = [vp, C.POINTER(YmLocatorInfo)]
+    L.ym_locator_read_level.argtypes = [vp, C.c_int, C.POINTER(C.c_uint8), C.c_int64]
+    L.ym_locator_locate.argtypes = [vp, C.c_double, C.c_double, C.POINTER(vp), C.c_int, dp, C.c_int, C.POINTER(YmLocateOpts),
+                                    C.POINTER(YmLocateCandidate), C.POINTER(C.c_int), dp, C.POINTER(YmLocateStats)]
+    L.ym_locator_destroy.argtypes = [vp]
+    L.ym_locator_destroy.restype = None
     lp = C.POINTER(C.c_int64)
     L.ym_segments_create.restype = vp
     L.ym_segments_create.argtypes = [C.c_int, ip, C.c_int, C.c_int, C.c_int]

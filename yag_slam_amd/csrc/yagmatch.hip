@@ -42,6 +42,7 @@ extern "C" {
 #include "ym_abi_match.hpp"
 #include "ym_abi_maps.hpp"
 #include "ym_abi_rays.hpp"
+#include "ym_abi_locate.hpp"
 #include "ym_abi_segments.hpp"
 #include "ym_abi_segmenter.hpp"
 #include "ym_abi_posegraph.hpp"

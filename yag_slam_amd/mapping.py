@@ -290,6 +290,17 @@ class LoopClosingMapper(SequentialMapper):
         self.results.append(res)
         return res, closed
 
+    def relocalize(self, scan, cmap, ox, oy, **kw):
+        """A node switched on somewhere inside a known map: find where `scan` was taken in the resident CorrelationMap `cmap`
+        (cell (0, 0) at world (ox, oy); `ScanMatcher.locate_in_map` of the map's matcher, keywords passed on), set
+        `scan.odom_pose` and `scan.corrected_pose` to the located and polished pose and return the result;
+        `splice_first_scan(scan)` proceeds from there.  Raises ValueError when nothing reaches min_response."""
+        res = cmap.m.locate_in_map(cmap, ox, oy, [scan], **kw)
+        p = res.best_pose[0]
+        scan.odom_pose = Transform(p.x, p.y, 0.0, p.euler[-1])
+        scan.corrected_pose = Transform(p.x, p.y, 0.0, p.euler[-1])
+        return res
+
     def splice_first_scan(self, scan, radius=5):
         """The first live scan after a prior map was ingested (`splicing.map_to_graphslam`): the ROS node's "first scan when
         splicing into a map" (slam_node_ros1:240-253).  `scan.odom_pose` and `scan.corrected_pose` hold the initial pose.

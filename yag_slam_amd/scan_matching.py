@@ -405,6 +405,44 @@ class ScanMatcher(object):
         r.meta["corrected_centre"] = (r.best_pose.x, r.best_pose.y, r.best_pose.euler[-1])
         return ScanMatcherResult(r.response, r.covariance, [q.corrected_pose + diff for q in query_scans], r.meta)
 
+    # ---- locate a scan set anywhere in a map (ym_locator_*) -------------------------------------
+    def map_locator(self, cmap, levels=None, max_nodes=None):
+        """A MapLocator over the resident CorrelationMap `cmap`: its max pyramid and search buffers on the device.
+        levels: pyramid levels above the map (None: by the map's size); max_nodes: frontier entries per buffer (None: 2^25)."""
+        return MapLocator(self, cmap, levels, max_nodes)
+
+    def locate_in_map(self, cmap, ox, oy, query_scans, refine=True, **kw):
+        """One shot: where in the map `cmap` (cell (0, 0) at world (ox, oy)) were `query_scans` taken, as one rigid set?
+        The exact best hypothesis over all cells and headings (`MapLocator.locate`, keywords passed on), then, with `refine`,
+        polished: copies of the scans are moved to the located poses and matched with `match_scan_sets_with_map` (coarse
+        window +-2 cells and +- one heading step, then its fine pass).  Returns a ScanMatcherResult whose best_pose holds one
+        pose per query scan and whose meta["candidates"] is the located list.  The polish's correction is applied as a rigid
+        motion about the set's centre (the wrapper's own list, which composes the correction in each scan's frame as the
+        reference does, is meta["wrapper_poses"]).  Raises ValueError when no hypothesis reaches min_response."""
+        with self.map_locator(cmap) as loc:
+            cands = loc.locate(query_scans, ox, oy, **kw)
+            stats, step = loc.last_stats, loc.last_heading_step
+        if not cands:
+            raise ValueError("locate_in_map: no hypothesis reaches min_response = %g" % kw.get("min_response", 0.0))
+        best = cands[0]
+        meta = {"candidates": cands, "stats": stats}
+        if not refine:
+            return ScanMatcherResult(best.response, None, list(best.poses), meta)
+        moved = []
+        for q, p in zip(query_scans, best.poses):
+            c = q.copy()
+            c.corrected_pose = p
+            moved.append(c)
+        res = float(self.config.resolution)
+        r = self.match_scan_sets_with_map(cmap, ox, oy, moved, True, True,
+                                          coarse=dict(xy_search=2 * res, xy_step=res / 4, angle_search=step, angle_step=step / 20,
+                                                      grid_resolution=res))
+        c0, c1 = r.meta["centre"], r.meta["corrected_centre"]
+        meta.update(r.meta)
+        meta["wrapper_poses"] = r.best_pose
+        poses = _move_rigidly([m_.corrected_pose for m_ in moved], c0[0], c0[1], c1[0], c1[1], c1[2] - c0[2])
+        return ScanMatcherResult(r.response, r.covariance, poses, meta)
+
     # ---- pipelined form ----------------------------------------------------------------------
     def match_scan_async(self, query, base_scans, penalty=True, do_fine=False, slot=0):
         hq = self._require_native(query)
@@ -502,6 +540,108 @@ class CorrelationMap(object):
         if getattr(self, "_h", None):
             self.m._lib.ym_map_destroy(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+LocateCandidate = namedtuple("LocateCandidate", ["score", "response", "index", "k", "cx", "cy", "pose", "poses"])
+
+
+def _move_rigidly(poses, cx, cy, nx, ny, dyaw):
+    """the poses after the rigid motion that turns the plane by dyaw about (cx, cy) and takes that point to (nx, ny)"""
+    c, s = np.cos(dyaw), np.sin(dyaw)
+    return [Transform(nx + c * (p.x - cx) - s * (p.y - cy), ny + s * (p.x - cx) + c * (p.y - cy), 0.0, p.euler[-1] + dyaw)
+            for p in poses]
+
+
+def filter_min_separation(candidates, metres, radians):
+    """Greedy, best first: a candidate is dropped when a better kept one lies within BOTH `metres` and `radians` of it
+    (headings compared modulo 2 pi).  `candidates` carry `.pose` (x, y, euler) and come best first."""
+    kept = []
+    for c in candidates:
+        for b in kept:
+            da = (c.pose.euler[-1] - b.pose.euler[-1] + np.pi) % (2 * np.pi) - np.pi
+            if np.hypot(c.pose.x - b.pose.x, c.pose.y - b.pose.y) <= metres and abs(da) <= radians:
+                break
+        else:
+            kept.append(c)
+    return kept
+
+
+class MapLocator(object):
+    """Where in a resident map was a scan set taken?  The exact top-K of the integer correlation score over every cell and
+    heading, by branch and bound over a max pyramid of the map on the device (ym_locator)."""
+
+    def __init__(self, matcher, cmap, levels=None, max_nodes=None):
+        self.m = matcher
+        self._h = matcher._lib.ym_locator_create(matcher._m, cmap._h, -1 if levels is None else int(levels),
+                                                 0 if max_nodes is None else int(max_nodes))
+        if not self._h:
+            raise _capi.YmError(-1, _capi.last_error())
+        info = _capi.YmLocatorInfo()
+        _capi.check(matcher._lib.ym_locator_get_info(self._h, C.byref(info)))
+        self.shape, self.levels, self.max_nodes, self.bytes = (info.height, info.width), info.levels, info.max_nodes, info.bytes
+        self.last_stats, self.last_points, self.last_heading_step = None, None, None
+
+    def read_level(self, level):
+        """test hook: level `level` of the pyramid over the map's own cells"""
+        out = np.empty(self.shape, dtype=np.uint8)
+        _capi.check(self.m._lib.ym_locator_read_level(self._h, int(level), out.ctypes.data_as(C.POINTER(C.c_uint8)), out.size))
+        return out
+
+    def locate(self, query_scans, ox, oy, n_angles=360, headings=None, top_k=16, min_response=0.0, point_stride=1,
+               min_separation=None):
+        """The `top_k` best hypotheses (LocateCandidate: score, response, index, k, cx, cy, pose = Transform of the set's
+        centre, poses = every query scan's pose after the rigid motion that takes the centre -- the mean query position,
+        heading 0 -- to `pose`), best first, ties by ascending index.  headings: explicit angles (default 2 pi k / n_angles).
+        min_separation = (metres, radians): the device's best 64 are filtered greedily (filter_min_separation) before the
+        first top_k are returned.  `.last_stats`: dict(nq, chunks, nodes and survivors per level, probe_nodes); `.last_points`: the point set."""
+        if headings is None:
+            headings = 2.0 * np.pi * np.arange(int(n_angles)) / float(int(n_angles))
+        headings = np.ascontiguousarray(headings, dtype=np.float64).reshape(-1)
+        dir_cs = np.ascontiguousarray(np.stack([np.cos(headings), np.sin(headings)], axis=1))
+        want = 64 if min_separation is not None else int(top_k)
+        if min_separation is not None and not 1 <= int(top_k) <= 64:
+            raise ValueError("top_k must be in [1, 64]")
+        hs = (C.c_void_p * max(1, len(query_scans)))(*[self.m._require_native(q) for q in query_scans])
+        opts = _capi.YmLocateOpts(want, int(point_stride), float(min_response))
+        out = (_capi.YmLocateCandidate * max(1, want))()
+        n_found, stats = C.c_int(0), _capi.YmLocateStats()
+        cap = sum(len(q.ranges) for q in query_scans)
+        pts = np.zeros((max(1, cap), 2))
+        _capi.check(self.m._lib.ym_locator_locate(self._h, float(ox), float(oy), hs, len(query_scans),
+                                                  dir_cs.ctypes.data_as(C.POINTER(C.c_double)), dir_cs.shape[0], C.byref(opts), out,
+                                                  C.byref(n_found), pts.ctypes.data_as(C.POINTER(C.c_double)), C.byref(stats)))
+        self.last_stats = dict(nq=stats.nq, chunks=stats.chunks, nodes=list(stats.nodes), survivors=list(stats.survivors),
+                               probe_nodes=stats.probe_nodes)
+        self.last_points = pts[:stats.nq].copy()
+        self.last_heading_step = float(2.0 * np.pi / len(headings)) if len(headings) < 2 else float(abs(headings[1] - headings[0]))
+        xs = [float(q.corrected_pose.x) for q in query_scans]
+        ys = [float(q.corrected_pose.y) for q in query_scans]
+        cx, cy = sum(xs) / float(len(xs)), sum(ys) / float(len(ys))
+        cands = []
+        for c in out[:n_found.value]:
+            pose = Transform(c.pose[0], c.pose[1], 0.0, c.pose[2])
+            cands.append(LocateCandidate(c.score, c.response, c.index, c.k, c.cx, c.cy, pose,
+                                         _move_rigidly([q.corrected_pose for q in query_scans], cx, cy, pose.x, pose.y, c.pose[2])))
+        if min_separation is not None:
+            cands = filter_min_separation(cands, float(min_separation[0]), float(min_separation[1]))[:int(top_k)]
+        return cands
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.m._lib.ym_locator_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:
