@@ -560,6 +560,11 @@ int ym_debug_option(ym_matcher *m, int option, int value);
 #define YM_DEBUG_COUNTERS 8
 int ym_debug_counters(ym_matcher *m, int64_t *out, int32_t count);
 
+/* test hook: the bytes of device memory and of pinned host memory that the library's handles hold right now, in this process (every
+ * handle of every device; the scan pool's slabs, which outlive their scans on purpose, are not counted).  A handle that is created,
+ * used and destroyed leaves both numbers exactly where they were. */
+int ym_debug_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes);
+
 /* development aid: 100 MHz wall-clock stamps written by block 0 of each kernel at phase boundaries.
  * Reads the stamps of the last call into out[0..count) (count <= 32), then switches stamping on/off. */
 int ym_debug_stamps(ym_matcher *m, int enable, uint64_t *out, int32_t count);

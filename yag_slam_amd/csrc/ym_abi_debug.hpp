@@ -160,6 +160,13 @@ int ym_debug_option(ym_matcher *m, int option, int value) {
     return YM_OK;
 }
 
+int ym_debug_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes) {
+    if (!device_bytes || !pinned_bytes) return set_err(YM_ERR_INVALID, "null argument");
+    *device_bytes = g_live_dev_bytes.load();
+    *pinned_bytes = g_live_pinned_bytes.load();
+    return YM_OK;
+}
+
 int ym_debug_stamps(ym_matcher *m, int enable, uint64_t *out, int32_t count) {
     if (!m) return set_err(YM_ERR_INVALID, "null matcher");
     DEV_GUARD(m->device);

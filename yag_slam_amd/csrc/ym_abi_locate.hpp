@@ -11,29 +11,16 @@ struct ym_locator {
     int width, height, levels;
     int64_t max_nodes;
     size_t bytes = 0;    // device memory the handle holds
-    uint8_t *d_pyr = nullptr; // level 0 (a copy of the map's byte grid), then levels 1 .. L with their low-side margins
+    DevBuf<uint8_t> d_pyr;    // level 0 (a copy of the map's byte grid), then levels 1 .. L with their low-side margins
     LocLevelHost level[ym::kLocMaxLevels + 1];
-    uint64_t *d_front[2] = {nullptr, nullptr}; // the frontier, ping-pong: max_nodes + kLocMaxTop entries each
-    uint64_t *d_beam = nullptr;                // the probe's nodes, ping-pong: 4 kLocMaxTop entries each
-    ym::LocState *d_state = nullptr;
-    YmItemState *d_item = nullptr;             // map_points_kernel leaves the number of points here
+    DevBuf<uint64_t> d_front[2];  // the frontier, ping-pong: max_nodes + kLocMaxTop entries each
+    DevBuf<uint64_t> d_beam;      // the probe's nodes, ping-pong: 4 kLocMaxTop entries each
+    DevBuf<ym::LocState> d_state;
+    DevBuf<YmItemState> d_item;   // map_points_kernel leaves the number of points here
     DevBuf<unsigned char> scans_dev;
     DevBuf<double2> pts, dirs;
     DevBuf<uint32_t> offsets;
 };
-
-static void locator_free(ym_locator *lc) {
-    if (!lc) return;
-    DevGuard guard(lc->device);
-    if (lc->d_pyr) (void)hipFree(lc->d_pyr);
-    for (int i = 0; i < 2; i++)
-        if (lc->d_front[i]) (void)hipFree(lc->d_front[i]);
-    if (lc->d_beam) (void)hipFree(lc->d_beam);
-    if (lc->d_state) (void)hipFree(lc->d_state);
-    if (lc->d_item) (void)hipFree(lc->d_item);
-    lc->scans_dev.release(); lc->pts.release(); lc->dirs.release(); lc->offsets.release();
-    delete lc;
-}
 
 // cells of the map covered by the first i top-level nodes of one heading, in (Y, X) order
 static uint64_t locator_cells_before(const ym_locator *lc, uint64_t i) {
@@ -67,7 +54,7 @@ ym_locator *ym_locator_create(ym_matcher *m, const ym_map *mp, int levels, int64
         return nullptr;
     }
     DevGuard guard(m->device);
-    if (!guard.ok) { set_err(YM_ERR_HIP, "cannot make device %d current", m->device); return nullptr; }
+    if (guard.status() != YM_OK) return nullptr;
     ym_locator *lc = new ym_locator();
     lc->m = m; lc->device = m->device; lc->width = W; lc->height = H; lc->levels = levels; lc->max_nodes = max_nodes;
     size_t pyr_bytes = 0, at[ym::kLocMaxLevels + 1];
@@ -78,30 +65,26 @@ ym_locator *ym_locator_create(ym_matcher *m, const ym_map *mp, int levels, int64
         pyr_bytes += align_up((size_t)lv.pitch * lv.rows, 256);
     }
     // (the probe's keys of up to 4 kLocMaxTop beam children go through the second buffer too, whatever max_nodes is)
-    const size_t front_bytes = ((size_t)std::max<int64_t>(max_nodes, 4 * ym::kLocMaxTop) + ym::kLocMaxTop) * sizeof(uint64_t);
-    bool ok = hipMalloc(reinterpret_cast<void **>(&lc->d_pyr), pyr_bytes) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&lc->d_front[0]), front_bytes) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&lc->d_front[1]), front_bytes) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&lc->d_beam), 8 * ym::kLocMaxTop * sizeof(uint64_t)) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&lc->d_state), sizeof(ym::LocState)) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&lc->d_item), sizeof(YmItemState)) == hipSuccess;
-    lc->bytes = pyr_bytes + 2 * front_bytes + 8 * ym::kLocMaxTop * sizeof(uint64_t) + sizeof(ym::LocState) + sizeof(YmItemState);
-    if (ok) {
-        for (int j = 0; j <= levels; j++) lc->level[j].p = lc->d_pyr + at[j];
+    const size_t front_n = (size_t)std::max<int64_t>(max_nodes, 4 * ym::kLocMaxTop) + ym::kLocMaxTop;
+    lc->bytes = pyr_bytes + 2 * front_n * sizeof(uint64_t) + 8 * ym::kLocMaxTop * sizeof(uint64_t) + sizeof(ym::LocState) + sizeof(YmItemState);
+    auto setup = [&]() -> int {
+        int rc;
+        if ((rc = lc->d_pyr.alloc(pyr_bytes)) || (rc = lc->d_front[0].alloc(front_n)) || (rc = lc->d_front[1].alloc(front_n)) ||
+            (rc = lc->d_beam.alloc(8 * ym::kLocMaxTop)) || (rc = lc->d_state.alloc(1)) || (rc = lc->d_item.alloc(1)))
+            return rc;
+        for (int j = 0; j <= levels; j++) lc->level[j].p = lc->d_pyr.p + at[j];
         hipStream_t st = m->stream;
-        ok = hipMemcpyAsync(lc->level[0].p, mp->d_g8, (size_t)W * H, hipMemcpyDeviceToDevice, st) == hipSuccess;
-        for (int j = 1; ok && j <= levels; j++) {
+        HIP_TRY(hipMemcpyAsync(lc->level[0].p, mp->d_g8.p, (size_t)W * H, hipMemcpyDeviceToDevice, st));
+        for (int j = 1; j <= levels; j++) {
             const LocLevelHost &s = lc->level[j - 1], &d = lc->level[j];
             hipLaunchKernelGGL(ym::loc_pyramid_kernel, dim3((d.pitch + 63) / 64, (d.rows + 3) / 4), dim3(256), 0, st, s.p, s.pitch, s.rows, s.margin,
                                d.p, d.pitch, d.rows, d.margin, 1 << (j - 1));
         }
-        ok = ok && hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-    }
-    if (!ok) {
-        set_err(YM_ERR_HIP, "building the locator of a %d x %d map failed: %s", W, H, hipGetErrorString(hipGetLastError()));
-        locator_free(lc);
-        return nullptr;
-    }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        return YM_OK;
+    };
+    if (setup() != YM_OK) { delete lc; return nullptr; } // (the error text is set)
     return lc;
 }
 
@@ -169,16 +152,16 @@ int ym_locator_locate(ym_locator *lc, double ox, double oy, const ym_scan *const
         return rc;
     HIP_TRY(hipMemcpyAsync(lc->scans_dev.p, hs.data(), sizeof(YmScanRef) * n_queries, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(lc->dirs.p, dir_cs, sizeof(double) * 2 * n_angles, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(lc->d_item, 0, sizeof(YmItemState), st));
+    HIP_TRY(hipMemsetAsync(lc->d_item.p, 0, sizeof(YmItemState), st));
     ym::MapPointsArgs pa;
     pa.scans = reinterpret_cast<const YmScanRef *>(lc->scans_dev.p); pa.n_scans = n_queries; pa.max_n = max_n;
-    pa.ox_real = ox_real; pa.oy_real = oy_real; pa.out = lc->pts.p; pa.state = lc->d_item;
+    pa.ox_real = ox_real; pa.oy_real = oy_real; pa.out = lc->pts.p; pa.state = lc->d_item.p;
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ym::map_points_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)YM_PREP_LDS_BYTES(YM_MAX_BEAMS));
     hipLaunchKernelGGL(ym::map_points_kernel, dim3(1), dim3(1024), YM_PREP_LDS_BYTES(max_n), st, pa);
     HIP_TRY(hipGetLastError());
     int32_t n_points = 0;
-    HIP_TRY(hipMemcpyAsync(&n_points, &lc->d_item->nq, sizeof n_points, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&n_points, &lc->d_item.p->nq, sizeof n_points, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (n_points < 1 || n_points > total) return set_err(YM_ERR_INVALID, "the query scans hold no valid reading");
     const int stride = o.point_stride, nq = (n_points + stride - 1) / stride;
@@ -189,13 +172,13 @@ int ym_locator_locate(ym_locator *lc, double ox, double oy, const ym_scan *const
     ym::LocState init;
     std::memset(&init, 0, sizeof init);
     init.tau = -1;
-    HIP_TRY(hipMemcpyAsync(lc->d_state, &init, sizeof init, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(lc->d_state.p, &init, sizeof init, hipMemcpyHostToDevice, st));
     const double res = m->cfg.resolution;
     hipLaunchKernelGGL(ym::loc_offsets_kernel, dim3((unsigned)(((size_t)nq * n_angles + 255) / 256)), dim3(256), 0, st, lc->pts.p, stride, nq,
-                       lc->dirs.p, n_angles, res, lc->offsets.p, lc->d_state);
+                       lc->dirs.p, n_angles, res, lc->offsets.p, lc->d_state.p);
     HIP_TRY(hipGetLastError());
     uint32_t bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, &lc->d_state->bad_offset, sizeof bad, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&bad, &lc->d_state.p->bad_offset, sizeof bad, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (bad) return set_err(YM_ERR_UNSUPPORTED, "a point lies more than 32767 cells from the set's centre");
     const double s_min_d = std::ceil(o.min_response * 100.0 * (double)nq);
@@ -218,18 +201,18 @@ int ym_locator_locate(ym_locator *lc, double ox, double oy, const ym_scan *const
         a.in = in; a.n_in = n; a.out = outp; a.out_cap = cap;
         a.offsets = lc->offsets.p; a.nq = nq;
         a.lvl = lv.p; a.pitch = lv.pitch; a.rows = lv.rows; a.margin = lv.margin;
-        a.level = j; a.W = W; a.H = H; a.s_min = s_min; a.st = lc->d_state;
+        a.level = j; a.W = W; a.H = H; a.s_min = s_min; a.st = lc->d_state.p;
         return a;
     };
     // the `want` largest of n unique keys, ranked, into the list `dest` names (loc_sel_rank_kernel)
     auto select = [&](const uint64_t *keys, uint32_t n, uint32_t want, int dest) {
         const unsigned blocks = std::min<unsigned>((n + 255) / 256, 2048u);
         for (int shift = 56; shift >= 0; shift -= 8) {
-            hipLaunchKernelGGL(ym::loc_sel_hist_kernel, dim3(blocks), dim3(256), 0, st, keys, n, shift, lc->d_state);
-            hipLaunchKernelGGL(ym::loc_sel_pick_kernel, dim3(1), dim3(64), 0, st, shift, want, lc->d_state);
+            hipLaunchKernelGGL(ym::loc_sel_hist_kernel, dim3(blocks), dim3(256), 0, st, keys, n, shift, lc->d_state.p);
+            hipLaunchKernelGGL(ym::loc_sel_pick_kernel, dim3(1), dim3(64), 0, st, shift, want, lc->d_state.p);
         }
-        hipLaunchKernelGGL(ym::loc_sel_collect_kernel, dim3(blocks), dim3(256), 0, st, keys, n, lc->d_state);
-        hipLaunchKernelGGL(ym::loc_sel_rank_kernel, dim3(1), dim3(64), 0, st, o.top_k, dest, lc->d_state);
+        hipLaunchKernelGGL(ym::loc_sel_collect_kernel, dim3(blocks), dim3(256), 0, st, keys, n, lc->d_state.p);
+        hipLaunchKernelGGL(ym::loc_sel_rank_kernel, dim3(1), dim3(64), 0, st, o.top_k, dest, lc->d_state.p);
     };
     for (uint64_t t0 = 0; t0 < n_top_nodes;) {
         uint64_t lo = t0 + 1, hi = n_top_nodes; // the largest t1 with cells [t0, t1) <= max_nodes (t0 + 1 always fits: checked at create)
@@ -241,22 +224,22 @@ int ym_locator_locate(ym_locator *lc, double ox, double oy, const ym_scan *const
         const uint64_t t1 = lo;
         uint32_t n = (uint32_t)(t1 - t0);
         sts.chunks++;
-        hipLaunchKernelGGL(ym::loc_top_nodes_kernel, dim3((n + 255) / 256), dim3(256), 0, st, t0, n, (uint32_t)tx_n, (uint32_t)ty_n, L, lc->d_front[0]);
+        hipLaunchKernelGGL(ym::loc_top_nodes_kernel, dim3((n + 255) / 256), dim3(256), 0, st, t0, n, (uint32_t)tx_n, (uint32_t)ty_n, L, lc->d_front[0].p);
         // ---- the probe: a beam of the kLocMaxTop best-bounded nodes followed down to level 0, where its top_k best exact scores
         // raise tau before the exact pass starts (without it a chunk's first leaves are reached with nothing pruned)
         if (L > 0) {
-            const uint64_t *pin = lc->d_front[0];
+            const uint64_t *pin = lc->d_front[0].p;
             uint32_t pn = n;
             for (int j = L; j >= 0 && pn > 0; j--) {
-                const ym::LocScoreArgs a = score_args(j, pin, pn, lc->d_front[1]);
+                const ym::LocScoreArgs a = score_args(j, pin, pn, lc->d_front[1].p);
                 hipLaunchKernelGGL(ym::loc_score_kernel<2>, dim3((pn + ym::kLocThreads - 1) / ym::kLocThreads), dim3(ym::kLocThreads), lds, st, a);
                 sts.probe_nodes += pn;
-                select(lc->d_front[1], pn, std::min<uint32_t>(j == 0 ? (uint32_t)o.top_k : (uint32_t)ym::kLocMaxTop, pn), j == 0 ? 2 : 1);
+                select(lc->d_front[1].p, pn, std::min<uint32_t>(j == 0 ? (uint32_t)o.top_k : (uint32_t)ym::kLocMaxTop, pn), j == 0 ? 2 : 1);
                 HIP_TRY(hipGetLastError());
                 if (j == 0) break;
-                uint64_t *next = lc->d_beam + (size_t)((L - j) & 1) * 4 * ym::kLocMaxTop;
-                hipLaunchKernelGGL(ym::loc_probe_expand_kernel, dim3(1), dim3(64), 0, st, lc->d_state, pin, j, W, H, next);
-                HIP_TRY(hipMemcpyAsync(counters, &lc->d_state->n_out, sizeof counters, hipMemcpyDeviceToHost, st));
+                uint64_t *next = lc->d_beam.p + (size_t)((L - j) & 1) * 4 * ym::kLocMaxTop;
+                hipLaunchKernelGGL(ym::loc_probe_expand_kernel, dim3(1), dim3(64), 0, st, lc->d_state.p, pin, j, W, H, next);
+                HIP_TRY(hipMemcpyAsync(counters, &lc->d_state.p->n_out, sizeof counters, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipStreamSynchronize(st));
                 if (counters[0] > 4u * ym::kLocMaxTop) return set_err(YM_ERR_UNSUPPORTED, "the probe's beam outgrew its buffer (a defect: please report)");
                 pin = next;
@@ -266,12 +249,12 @@ int ym_locator_locate(ym_locator *lc, double ox, double oy, const ym_scan *const
         // ---- the exact pass
         int cur = 0;
         for (int j = L; j >= 0 && n > 0; j--) {
-            const ym::LocScoreArgs a = score_args(j, lc->d_front[cur], n, lc->d_front[cur ^ 1]);
-            hipLaunchKernelGGL(ym::loc_begin_kernel, dim3(1), dim3(64), 0, st, lc->d_state, a.out, j == 0 ? 1 : 0);
+            const ym::LocScoreArgs a = score_args(j, lc->d_front[cur].p, n, lc->d_front[cur ^ 1].p);
+            hipLaunchKernelGGL(ym::loc_begin_kernel, dim3(1), dim3(64), 0, st, lc->d_state.p, a.out, j == 0 ? 1 : 0);
             if (j > 0) hipLaunchKernelGGL(ym::loc_score_kernel<0>, dim3((n + ym::kLocThreads - 1) / ym::kLocThreads), dim3(ym::kLocThreads), lds, st, a);
             else hipLaunchKernelGGL(ym::loc_score_kernel<1>, dim3((n + ym::kLocThreads - 1) / ym::kLocThreads), dim3(ym::kLocThreads), lds, st, a);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(counters, &lc->d_state->n_out, sizeof counters, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(counters, &lc->d_state.p->n_out, sizeof counters, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             if (counters[1] || counters[0] > cap) return set_err(YM_ERR_UNSUPPORTED, "the frontier outgrew its buffers at level %d (a defect: please report)", j);
             sts.nodes[j] += n;
@@ -279,14 +262,14 @@ int ym_locator_locate(ym_locator *lc, double ox, double oy, const ym_scan *const
             cur ^= 1;
             if (j == 0 && n > (uint32_t)known) { // new leaves beside the `known` best so far: the best top_k of all
                 known = (int)std::min<uint32_t>((uint32_t)o.top_k, n);
-                select(lc->d_front[cur], n, (uint32_t)known, 0);
+                select(lc->d_front[cur].p, n, (uint32_t)known, 0);
                 HIP_TRY(hipGetLastError());
             }
         }
         t0 = t1;
     }
     ym::LocState fin;
-    HIP_TRY(hipMemcpyAsync(&fin, lc->d_state, sizeof fin, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&fin, lc->d_state.p, sizeof fin, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (fin.n_top != known || fin.n_top > o.top_k) return set_err(YM_ERR_UNSUPPORTED, "the top-K merge kept %d of %d candidates (a defect: please report)", fin.n_top, known);
     std::vector<double> pts_host;
@@ -317,4 +300,8 @@ int ym_locator_locate(ym_locator *lc, double ox, double oy, const ym_scan *const
     return YM_OK;
 }
 
-void ym_locator_destroy(ym_locator *lc) { locator_free(lc); }
+void ym_locator_destroy(ym_locator *lc) {
+    if (!lc) return;
+    DevGuard guard(lc->device);
+    delete lc;
+}

@@ -11,12 +11,8 @@ static ym_map *map_alloc(ym_matcher *m, int width, int height) {
     ym_map *mp = new ym_map();
     mp->device = m->device;
     mp->width = width; mp->height = height;
-    mp->d_cgrid = nullptr; mp->d_g8 = nullptr;
     const size_t n = (size_t)width * height;
-    if (hipMalloc(reinterpret_cast<void **>(&mp->d_cgrid), n * sizeof(double)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&mp->d_g8), n + 64) != hipSuccess) {
-        set_err(YM_ERR_HIP, "cannot allocate a %d x %d map", width, height);
-        if (mp->d_cgrid) (void)hipFree(mp->d_cgrid);
+    if (mp->d_cgrid.alloc(n) != YM_OK || mp->d_g8.alloc(n + 64) != YM_OK) { // (the error text is set)
         delete mp;
         return nullptr;
     }
@@ -29,18 +25,20 @@ ym_map *ym_map_from_occupancy(ym_matcher *m, const uint8_t *image, int width, in
     ym_map *mp = map_alloc(m, width, height);
     if (!mp) return nullptr;
     const int ks = 2 * m->geom.half_kernel + 1;
-    uint8_t *d_img = nullptr;
-    bool ok = hipMalloc(reinterpret_cast<void **>(&d_img), (size_t)pitch * height) == hipSuccess &&
-              hipMemcpyAsync(d_img, image, (size_t)pitch * height, hipMemcpyHostToDevice, m->stream) == hipSuccess &&
-              m->kernel_f_dev.ensure(m->kernel_f.size()) == YM_OK &&
-              hipMemcpyAsync(m->kernel_f_dev.p, m->kernel_f.data(), m->kernel_f.size() * sizeof(double), hipMemcpyHostToDevice, m->stream) == hipSuccess;
-    if (ok) {
-        hipLaunchKernelGGL(ym::map_from_occupancy_kernel, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0, m->stream, d_img, width,
-                           height, pitch, occupied_value, m->kernel_f_dev.p, ks, mp->d_cgrid, mp->d_g8);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(m->stream) == hipSuccess;
-    }
-    if (d_img) (void)hipFree(d_img);
-    if (!ok) { set_err(YM_ERR_HIP, "building the map failed"); ym_map_destroy(mp); return nullptr; }
+    DevBuf<uint8_t> d_img;
+    auto setup = [&]() -> int {
+        int rc;
+        if ((rc = d_img.alloc((size_t)pitch * height))) return rc;
+        HIP_TRY(hipMemcpyAsync(d_img.p, image, (size_t)pitch * height, hipMemcpyHostToDevice, m->stream));
+        if ((rc = m->kernel_f_dev.ensure(m->kernel_f.size()))) return rc;
+        HIP_TRY(hipMemcpyAsync(m->kernel_f_dev.p, m->kernel_f.data(), m->kernel_f.size() * sizeof(double), hipMemcpyHostToDevice, m->stream));
+        hipLaunchKernelGGL(ym::map_from_occupancy_kernel, dim3((width + 63) / 64, (height + 3) / 4), dim3(256), 0, m->stream, d_img.p, width,
+                           height, pitch, occupied_value, m->kernel_f_dev.p, ks, mp->d_cgrid.p, mp->d_g8.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(m->stream));
+        return YM_OK;
+    };
+    if (setup() != YM_OK) { delete mp; return nullptr; } // (the error text is set)
     return mp;
 }
 
@@ -50,12 +48,14 @@ ym_map *ym_map_from_grid(ym_matcher *m, const double *cgrid, int width, int heig
     ym_map *mp = map_alloc(m, width, height);
     if (!mp) return nullptr;
     const size_t n = (size_t)width * height;
-    bool ok = hipMemcpyAsync(mp->d_cgrid, cgrid, n * sizeof(double), hipMemcpyHostToDevice, m->stream) == hipSuccess;
-    if (ok) {
-        hipLaunchKernelGGL(ym::map_from_grid_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, mp->d_cgrid, n, mp->d_g8);
-        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(m->stream) == hipSuccess;
-    }
-    if (!ok) { set_err(YM_ERR_HIP, "uploading the map failed"); ym_map_destroy(mp); return nullptr; }
+    auto setup = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(mp->d_cgrid.p, cgrid, n * sizeof(double), hipMemcpyHostToDevice, m->stream));
+        hipLaunchKernelGGL(ym::map_from_grid_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, mp->d_cgrid.p, n, mp->d_g8.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(m->stream));
+        return YM_OK;
+    };
+    if (setup() != YM_OK) { delete mp; return nullptr; } // (the error text is set)
     return mp;
 }
 
@@ -71,15 +71,13 @@ int ym_map_read(const ym_map *mp, double *out, int64_t out_count) {
     const size_t n = (size_t)mp->width * mp->height;
     if ((size_t)out_count < n) return set_err(YM_ERR_INVALID, "buffer too small: need %zu entries", n);
     DEV_GUARD(mp->device);
-    HIP_TRY(hipMemcpy(out, mp->d_cgrid, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, mp->d_cgrid.p, n * sizeof(double), hipMemcpyDeviceToHost));
     return YM_OK;
 }
 
 void ym_map_destroy(ym_map *mp) {
     if (!mp) return;
     DevGuard guard(mp->device);
-    if (mp->d_cgrid) (void)hipFree(mp->d_cgrid);
-    if (mp->d_g8) (void)hipFree(mp->d_g8);
     delete mp;
 }
 
@@ -170,7 +168,7 @@ int ym_match_map(ym_matcher *m, const ym_map *mp, double ox, double oy, const ym
         a.states = m->states.p; a.host_out = reinterpret_cast<YmItemState *>(slot.result.dp);
         a.axes = m->yaxes.p; a.rot = m->yrot.p;
         a.sums = m->sums.p + m->sums_pass_offset[pass]; a.out = m->resp.p;
-        a.grid = mp->d_g8; a.grid_stride = 0; a.vol_stride = vol;
+        a.grid = mp->d_g8.p; a.grid_stride = 0; a.vol_stride = vol;
         a.max_n = total; a.maxd = maxd; a.maxt = maxt;
         a.map_w = mp->width; a.map_h = mp->height; a.map_ox = ox; a.map_oy = oy;
         hipLaunchKernelGGL(ym::yag_setup_kernel, dim3(maxt, 1), dim3(256), 0, st, a);
@@ -206,7 +204,7 @@ static ym_occupancy *occupancy_render(const ym_scan *const *scans, int n_scans, 
         max_n = std::max(max_n, scans[i]->n);
     }
     DevGuard guard(device);
-    if (!guard.ok) { set_err(YM_ERR_HIP, "cannot make device %d current", device); return nullptr; }
+    if (guard.status() != YM_OK) return nullptr;
     std::vector<YmScanRef> hs(n_scans);
     std::memset(hs.data(), 0, sizeof(YmScanRef) * n_scans);
     for (int i = 0; i < n_scans; i++) {
@@ -217,69 +215,53 @@ static ym_occupancy *occupancy_render(const ym_scan *const *scans, int n_scans, 
         hs[i].range_threshold = q->max_range; // the laser's MAXIMUM range travels in this field (see occ_trace_kernel)
         hs[i].pose[0] = q->pose[0]; hs[i].pose[1] = q->pose[1]; hs[i].pose[2] = q->pose[2];
     }
-    YmScanRef *d_scans = nullptr;
-    double *d_boxes = nullptr;
-    unsigned *d_cnt = nullptr;
-    uint8_t *d_img = nullptr;
-    ym_occupancy *og = nullptr;
-    bool said = false; // this call has set its own error message (the thread's last message may be an older one)
-    bool ok = hipMalloc(reinterpret_cast<void **>(&d_scans), sizeof(YmScanRef) * n_scans) == hipSuccess &&
-              hipMalloc(reinterpret_cast<void **>(&d_boxes), sizeof(double) * 4 * n_scans) == hipSuccess &&
-              hipMemcpy(d_scans, hs.data(), sizeof(YmScanRef) * n_scans, hipMemcpyHostToDevice) == hipSuccess;
-    ym::OccArgs a;
-    std::memset(&a, 0, sizeof a);
-    if (ok) {
-        a.scans = d_scans; a.n_scans = n_scans; a.max_n = max_n; a.range_threshold = range_threshold; a.boxes = d_boxes;
+    DevBuf<YmScanRef> d_scans;
+    DevBuf<double> d_boxes;
+    DevBuf<unsigned> d_cnt;
+    DevBuf<uint8_t> d_img;
+    ym_occupancy *og = new ym_occupancy();
+    og->device = device;
+    auto render = [&]() -> int {
+        int rc;
+        if ((rc = d_scans.alloc(n_scans)) || (rc = d_boxes.alloc((size_t)4 * n_scans))) return rc;
+        HIP_TRY(hipMemcpy(d_scans.p, hs.data(), sizeof(YmScanRef) * n_scans, hipMemcpyHostToDevice));
+        ym::OccArgs a;
+        std::memset(&a, 0, sizeof a);
+        a.scans = d_scans.p; a.n_scans = n_scans; a.max_n = max_n; a.range_threshold = range_threshold; a.boxes = d_boxes.p;
         hipLaunchKernelGGL(ym::occ_bbox_kernel, dim3(n_scans), dim3(256), 0, nullptr, a);
+        HIP_TRY(hipGetLastError());
         std::vector<double> boxes((size_t)4 * n_scans);
-        ok = hipGetLastError() == hipSuccess && hipMemcpy(boxes.data(), d_boxes, sizeof(double) * boxes.size(), hipMemcpyDeviceToHost) == hipSuccess;
-        if (ok) {
-            // OccupancyGrid::ComputeDimensions: the scans' bounding boxes joined, width = Round(size * scale)
-            double x0 = 1e300, y0 = 1e300, x1 = -1e300, y1 = -1e300;
-            for (int i = 0; i < n_scans; i++) {
-                x0 = std::min(x0, boxes[4 * i]); y0 = std::min(y0, boxes[4 * i + 1]);
-                x1 = std::max(x1, boxes[4 * i + 2]); y1 = std::max(y1, boxes[4 * i + 3]);
-            }
-            const double scale = 1.0 / resolution;
-            const int width = (int)kt_round_h((x1 - x0) * scale), height = (int)kt_round_h((y1 - y0) * scale);
-            if (width <= 0 || height <= 0 || (double)width * height > 2.0e9) {
-                set_err(YM_ERR_UNSUPPORTED, "occupancy grid of %d x %d cells", width, height);
-                said = true;
-                ok = false;
-            } else {
-                const size_t n = (size_t)width * height;
-                ok = hipMalloc(reinterpret_cast<void **>(&d_cnt), 2 * n * sizeof(unsigned)) == hipSuccess &&
-                     hipMalloc(reinterpret_cast<void **>(&d_img), n) == hipSuccess &&
-                     hipMemset(d_cnt, 0, 2 * n * sizeof(unsigned)) == hipSuccess;
-                if (ok) {
-                    a.scale = scale; a.off_x = x0; a.off_y = y0; a.width = width; a.height = height;
-                    a.pass = d_cnt; a.hits = d_cnt + n; a.image = d_img;
-                    hipLaunchKernelGGL(ym::occ_trace_kernel, dim3((max_n + 255) / 256, n_scans), dim3(256), 0, nullptr, a);
-                    ok = hipGetLastError() == hipSuccess;
-                    hipLaunchKernelGGL(ym::occ_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, a);
-                    og = new ym_occupancy();
-                    og->device = device;
-                    og->info.width = width; og->info.height = height;
-                    og->info.offset_x = x0; og->info.offset_y = y0; og->info.resolution = resolution;
-                    og->image.resize(n);
-                    ok = ok && hipGetLastError() == hipSuccess && hipMemcpy(og->image.data(), d_img, n, hipMemcpyDeviceToHost) == hipSuccess;
-                    if (ok && keep_counts) {
-                        og->counts.resize(2 * n);
-                        ok = hipMemcpy(og->counts.data(), d_cnt, 2 * n * sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess;
-                    }
-                }
-            }
+        HIP_TRY(hipMemcpy(boxes.data(), d_boxes.p, sizeof(double) * boxes.size(), hipMemcpyDeviceToHost));
+        // OccupancyGrid::ComputeDimensions: the scans' bounding boxes joined, width = Round(size * scale)
+        double x0 = 1e300, y0 = 1e300, x1 = -1e300, y1 = -1e300;
+        for (int i = 0; i < n_scans; i++) {
+            x0 = std::min(x0, boxes[4 * i]); y0 = std::min(y0, boxes[4 * i + 1]);
+            x1 = std::max(x1, boxes[4 * i + 2]); y1 = std::max(y1, boxes[4 * i + 3]);
         }
-    }
-    if (d_scans) (void)hipFree(d_scans);
-    if (d_boxes) (void)hipFree(d_boxes);
-    if (d_cnt) (void)hipFree(d_cnt);
-    if (d_img) (void)hipFree(d_img);
-    if (!ok) {
-        if (!said) set_err(YM_ERR_HIP, "rendering the occupancy grid failed: %s", hipGetErrorString(hipGetLastError()));
-        delete og;
-        return nullptr;
-    }
+        const double scale = 1.0 / resolution;
+        const int width = (int)kt_round_h((x1 - x0) * scale), height = (int)kt_round_h((y1 - y0) * scale);
+        if (width <= 0 || height <= 0 || (double)width * height > 2.0e9)
+            return set_err(YM_ERR_UNSUPPORTED, "occupancy grid of %d x %d cells", width, height);
+        const size_t n = (size_t)width * height;
+        if ((rc = d_cnt.alloc(2 * n)) || (rc = d_img.alloc(n))) return rc;
+        HIP_TRY(hipMemset(d_cnt.p, 0, 2 * n * sizeof(unsigned)));
+        a.scale = scale; a.off_x = x0; a.off_y = y0; a.width = width; a.height = height;
+        a.pass = d_cnt.p; a.hits = d_cnt.p + n; a.image = d_img.p;
+        hipLaunchKernelGGL(ym::occ_trace_kernel, dim3((max_n + 255) / 256, n_scans), dim3(256), 0, nullptr, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(ym::occ_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, a);
+        HIP_TRY(hipGetLastError());
+        og->info.width = width; og->info.height = height;
+        og->info.offset_x = x0; og->info.offset_y = y0; og->info.resolution = resolution;
+        og->image.resize(n);
+        HIP_TRY(hipMemcpy(og->image.data(), d_img.p, n, hipMemcpyDeviceToHost));
+        if (keep_counts) {
+            og->counts.resize(2 * n);
+            HIP_TRY(hipMemcpy(og->counts.data(), d_cnt.p, 2 * n * sizeof(unsigned), hipMemcpyDeviceToHost));
+        }
+        return YM_OK;
+    };
+    if (render() != YM_OK) { delete og; return nullptr; } // (the error text is set)
     return og;
 }
 

@@ -18,12 +18,9 @@ const char *ym_last_error(void) { return g_err.c_str(); }
 
 ym_matcher *ym_create(const ym_config *cfg, int device) {
     if (!cfg) { set_err(YM_ERR_INVALID, "null config"); return nullptr; }
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        set_err(YM_ERR_NO_DEVICE, "no HIP device available (libyagmatch has no CPU fallback)");
-        return nullptr;
-    }
-    if (device < 0 || device >= n) { set_err(YM_ERR_NO_DEVICE, "device %d out of range [0, %d)", device, n); return nullptr; }
+    if (check_device(device) != YM_OK) return nullptr;
+    DevGuard guard(device);
+    if (guard.status() != YM_OK) return nullptr;
     ym_matcher *m = new ym_matcher();
     m->cfg = *cfg;
     m->device = device;
@@ -34,8 +31,7 @@ ym_matcher *ym_create(const ym_config *cfg, int device) {
     }
     m->own_stream = nullptr;
     if (build_geometry(m) != YM_OK) { delete m; return nullptr; }
-    DevGuard guard(device);
-    if (!guard.ok || hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking) != hipSuccess) {
+    if (hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking) != hipSuccess) {
         set_err(YM_ERR_HIP, "cannot create a stream on device %d", device);
         delete m;
         return nullptr;
@@ -69,25 +65,15 @@ void ym_destroy(ym_matcher *m) {
     pool_register_stream(m->device, m->stream, false);
     pool_register_stream(m->device, m->own_stream, false);
     pool_register_stream(m->device, m->side_stream, false);
-    m->ktab.release(); m->rowtab.release(); m->desc_dev.release(); m->states.release(); m->qlocal.release(); m->qnp.release(); m->tmp_cache.release(); m->cells.release(); m->bbox.release(); m->grid.release(); m->planes.release(); m->tile_zero.release(); m->sub_zero.release(); m->tile_list.release(); m->tile_count.release(); m->tile_max.release(); m->tile_hits.release(); m->sel_scratch.release(); m->sel_tables.release(); m->sel_rec.release(); m->sel_slot.release();
-    m->rg_entries.release(); m->rg_starts.release(); m->rg_rbox.release(); m->rg_walk.release(); m->ga_units.release(); m->ga_starts.release(); m->ga_work.release(); m->ga_counters.release(); m->ga_lane_job.release();
-    if (m->tile_max_host) { (void)hipHostFree(m->tile_max_host); m->tile_max_host = nullptr; }
-    m->ctrig.release(); m->foffsets.release(); m->hypcell.release(); m->partial.release(); m->sums.release();
-    m->resp.release(); m->blockmax.release(); m->probs.release(); m->tmp_ranges.release();
-    m->tmp_ranges_host.release(); m->kernel_f_dev.release(); m->map_pts.release(); m->yag_counters.release(); m->cache_arena.release(); m->stamps.release(); m->yaxes.release(); m->yrot.release();
-    for (Slot &s : m->slots) {
-        s.desc.release();
-        s.desc_dev.release();
-        s.result.release();
+    for (Slot &s : m->slots)
         if (s.done) (void)hipEventDestroy(s.done);
-    }
     for (auto &p : m->prof)
         for (auto &e : p.pairs) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
     if (m->side_stream) (void)hipStreamDestroy(m->side_stream);
     if (m->ev_fork) (void)hipEventDestroy(m->ev_fork);
     if (m->ev_join) (void)hipEventDestroy(m->ev_join);
-    delete m;
+    delete m; // (every buffer goes with it, the device still current)
 }
 
 int ym_get_config(const ym_matcher *m, ym_config *out) {

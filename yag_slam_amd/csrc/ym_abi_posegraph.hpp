@@ -4,7 +4,7 @@
 // mirrors: whatever changed since the last launch is uploaded whole before the next one.
 struct ym_graph {
     int device;
-    hipStream_t stream = nullptr;
+    OwnStream stream;
     std::vector<double> pose, mean, info;
     std::vector<int32_t> from_to;
     bool poses_stale = true, edges_stale = true; // the device mirrors are behind the host's vectors
@@ -13,37 +13,21 @@ struct ym_graph {
     DevBuf<int32_t> d_from_to, node_ptr, inc;
 };
 
-static void graph_free(ym_graph *g) {
-    if (!g) return;
-    if (g->stream) {
-        DevGuard guard(g->device);
-        g->d_pose[0].release(); g->d_pose[1].release(); g->d_mean.release(); g->d_info.release(); g->e_blk.release();
-        g->e_grad.release(); g->e_chi.release(); g->diag.release(); g->grad.release(); g->aband.release(); g->uband.release();
-        g->ubandT.release(); g->vec.release(); g->partial.release(); g->record.release(); g->d_from_to.release();
-        g->node_ptr.release(); g->inc.release();
-        (void)hipStreamDestroy(g->stream);
-    }
-    delete g;
-}
-
 ym_graph *ym_graph_create(int device) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { set_err(YM_ERR_NO_DEVICE, "no HIP device"); return nullptr; }
-    if (device < 0 || device >= n_dev) { set_err(YM_ERR_NO_DEVICE, "device %d out of range (%d devices)", device, n_dev); return nullptr; }
+    if (check_device(device) != YM_OK) return nullptr;
     DevGuard guard(device);
-    if (!guard.ok) { set_err(YM_ERR_HIP, "cannot make device %d current", device); return nullptr; }
+    if (guard.status() != YM_OK) return nullptr;
     ym_graph *g = new ym_graph();
     g->device = device;
-    if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) {
-        g->stream = nullptr;
-        set_err(YM_ERR_HIP, "cannot create a stream on device %d", device);
-        graph_free(g);
-        return nullptr;
-    }
+    if (g->stream.create() != YM_OK) { delete g; return nullptr; } // (the error text is set)
     return g;
 }
 
-void ym_graph_destroy(ym_graph *g) { graph_free(g); }
+void ym_graph_destroy(ym_graph *g) {
+    if (!g) return;
+    DevGuard guard(g->device);
+    delete g;
+}
 
 static bool graph_finite(const double *v, size_t n) {
     for (size_t i = 0; i < n; i++)

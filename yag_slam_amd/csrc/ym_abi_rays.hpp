@@ -3,21 +3,12 @@
 struct ym_raymap {
     int device;
     int width, height;   // the image, resident on the device with pitch = width
-    uint8_t *d_img = nullptr;
-    hipStream_t stream = nullptr;
+    OwnStream stream;
+    DevBuf<uint8_t> d_img;
     DevBuf<double> starts, dirs, length;
     DevBuf<float> end_xy;
     DevBuf<unsigned long long> capped;
 };
-
-static void raymap_free(ym_raymap *rm) {
-    if (!rm) return;
-    DevGuard guard(rm->device);
-    if (rm->d_img) (void)hipFree(rm->d_img);
-    rm->starts.release(); rm->dirs.release(); rm->length.release(); rm->end_xy.release(); rm->capped.release();
-    if (rm->stream) (void)hipStreamDestroy(rm->stream);
-    delete rm;
-}
 
 ym_raymap *ym_raymap_create(int device, const uint8_t *image, int width, int height, int pitch) {
     if (!image || width < 1 || height < 1 || pitch < width) { set_err(YM_ERR_INVALID, "bad occupancy image"); return nullptr; }
@@ -25,21 +16,18 @@ ym_raymap *ym_raymap_create(int device, const uint8_t *image, int width, int hei
         set_err(YM_ERR_INVALID, "image of %d x %d pixels: at most 65536 x 65536 (the walk's termination bound)", width, height);
         return nullptr;
     }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { set_err(YM_ERR_NO_DEVICE, "no HIP device"); return nullptr; }
-    if (device < 0 || device >= n_dev) { set_err(YM_ERR_NO_DEVICE, "device %d out of range (%d devices)", device, n_dev); return nullptr; }
+    if (check_device(device) != YM_OK) return nullptr;
     DevGuard guard(device);
-    if (!guard.ok) { set_err(YM_ERR_HIP, "cannot make device %d current", device); return nullptr; }
+    if (guard.status() != YM_OK) return nullptr;
     ym_raymap *rm = new ym_raymap();
     rm->device = device; rm->width = width; rm->height = height;
-    const bool ok = hipStreamCreateWithFlags(&rm->stream, hipStreamNonBlocking) == hipSuccess &&
-                    hipMalloc(reinterpret_cast<void **>(&rm->d_img), (size_t)width * height) == hipSuccess &&
-                    hipMemcpy2D(rm->d_img, width, image, pitch, width, height, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) {
-        set_err(YM_ERR_HIP, "uploading the occupancy image failed: %s", hipGetErrorString(hipGetLastError()));
-        raymap_free(rm);
-        return nullptr;
-    }
+    auto setup = [&]() -> int {
+        int rc;
+        if ((rc = rm->stream.create()) || (rc = rm->d_img.alloc((size_t)width * height))) return rc;
+        HIP_TRY(hipMemcpy2D(rm->d_img.p, width, image, pitch, width, height, hipMemcpyHostToDevice));
+        return YM_OK;
+    };
+    if (setup() != YM_OK) { delete rm; return nullptr; } // (the error text is set)
     return rm;
 }
 
@@ -79,7 +67,7 @@ static int raymap_trace(ym_raymap *rm, const double *starts_xy, int n_starts, co
     HIP_TRY(hipMemcpyAsync(rm->dirs.p, dir_cs, sizeof(double) * 2 * n_dirs, hipMemcpyHostToDevice, rm->stream));
     HIP_TRY(hipMemsetAsync(rm->capped.p, 0, sizeof(unsigned long long), rm->stream));
     ym::RayArgs a;
-    a.img = rm->d_img; a.width = rm->width; a.height = rm->height; a.pitch = rm->width;
+    a.img = rm->d_img.p; a.width = rm->width; a.height = rm->height; a.pitch = rm->width;
     a.starts = rm->starts.p; a.dirs = rm->dirs.p; a.n_starts = n_starts; a.n_angles = n_angles;
     a.dirs_per_start = per_start ? 1 : 0;
     a.max_steps = 2 * (rm->width + rm->height) + 4;
@@ -106,4 +94,8 @@ int ym_raymap_trace_each(ym_raymap *rm, const double *starts_xy, int n_starts, c
     return raymap_trace(rm, starts_xy, n_starts, dir_cs, n_angles, true, end_xy, length, capped);
 }
 
-void ym_raymap_destroy(ym_raymap *rm) { raymap_free(rm); }
+void ym_raymap_destroy(ym_raymap *rm) {
+    if (!rm) return;
+    DevGuard guard(rm->device);
+    delete rm;
+}

@@ -32,15 +32,13 @@ struct ScanLayout {
 
 ym_scan *ym_scan_create(int device, const ym_scan_desc *d) {
     if (check_desc(d) != YM_OK) return nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_err(YM_ERR_NO_DEVICE, "no HIP device available"); return nullptr; }
-    if (device < 0 || device >= n) { set_err(YM_ERR_NO_DEVICE, "device %d out of range [0, %d)", device, n); return nullptr; }
+    if (check_device(device) != YM_OK) return nullptr;
     ym_scan *s = scan_host_side(device, d);
     DevGuard guard(device);
     const ScanLayout L(d->n);
     const size_t ranges_bytes = L.ranges_bytes, gov_bytes = L.gov_bytes, cidx_bytes = L.cidx_bytes, total = L.total;
     const bool structured = d->n > 0 && d->n <= YM_MAX_BEAMS;
-    if (!guard.ok) { set_err(YM_ERR_HIP, "cannot select device %d", device); delete s; return nullptr; }
+    if (guard.status() != YM_OK) { delete s; return nullptr; }
     if (structured) {
         unsigned char *base = nullptr;
         {
@@ -132,9 +130,7 @@ void ym_scan_destroy(ym_scan *s) {
 // staging slot, nothing left to wait for).
 int ym_scans_create(int device, const ym_scan_desc *descs, int n, ym_scan **out) {
     if (n < 0 || (n > 0 && (!descs || !out))) return set_err(YM_ERR_INVALID, "null argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_err(YM_ERR_NO_DEVICE, "no HIP device available");
-    if (device < 0 || device >= ndev) return set_err(YM_ERR_NO_DEVICE, "device %d out of range [0, %d)", device, ndev);
+    if (int rc = check_device(device)) return rc;
     for (int i = 0; i < n; i++) {
         int rc = check_desc(&descs[i]);
         if (rc) return rc;

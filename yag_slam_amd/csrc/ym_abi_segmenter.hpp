@@ -11,10 +11,6 @@ struct SegmenterWork {
     DevBuf<unsigned> err, block_counts, parent, size;
     DevBuf<int32_t> cell_centre, assign;
     DevBuf<double2> centres[2];
-    ~SegmenterWork() {
-        src.release(); closed.release(); sums.release(); cell_acc.release(); acc.release(); err.release(); block_counts.release();
-        parent.release(); size.release(); cell_centre.release(); assign.release(); centres[0].release(); centres[1].release();
-    }
 };
 
 static int segmenter_check_image(const uint8_t *image, int w, int h, int pitch, int close_size) {
@@ -24,13 +20,6 @@ static int segmenter_check_image(const uint8_t *image, int w, int h, int pitch, 
     if (pitch < w) return set_err(YM_ERR_INVALID, "pitch %d: at least w (%d bytes)", pitch, w);
     if (close_size < 1 || close_size > 2 * ym::kCloseMaxR + 1 || close_size % 2 == 0)
         return set_err(YM_ERR_INVALID, "close_size %d: odd, 1 .. %d", close_size, 2 * ym::kCloseMaxR + 1);
-    return YM_OK;
-}
-
-static int segmenter_check_device(int device) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) return set_err(YM_ERR_NO_DEVICE, "no HIP device");
-    if (device < 0 || device >= n_dev) return set_err(YM_ERR_NO_DEVICE, "device %d out of range (%d devices)", device, n_dev);
     return YM_OK;
 }
 
@@ -58,7 +47,7 @@ int ym_map_free_space(int device, const uint8_t *image, int w, int h, int pitch,
     int rc;
     if ((rc = segmenter_check_image(image, w, h, pitch, close_size))) return rc;
     if (!closed || !sum || !n_free) return set_err(YM_ERR_INVALID, "closed, sum or n_free: null");
-    if ((rc = segmenter_check_device(device))) return rc;
+    if ((rc = check_device(device))) return rc;
     DEV_GUARD(device);
     SegmenterWork wk;
     ym::SegmenterArgs a{};
@@ -155,12 +144,12 @@ static int segmenter_run(ym_segments *sg, const uint8_t *image, int pitch, const
     unsigned segments = 0;
     int64_t labelled = 0;
     if (o.stage == YM_SEGMENT_STAGE_ASSIGNED) {
-        HIP_TRY(hipMemcpyAsync(sg->d_img, wk.assign.p, n_img * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(sg->d_img.p, wk.assign.p, n_img * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
     } else {
         // D: components, sizes, numbers
         if ((rc = wk.parent.ensure(n_pix)) || (rc = wk.size.ensure(n_pix))) return rc;
         HIP_TRY(hipMemsetAsync(wk.size.p, 0, n_pix * sizeof(unsigned), stream));
-        a.parent = wk.parent.p; a.size = wk.size.p; a.min_size = (unsigned long long)min_size; a.labels = sg->d_img;
+        a.parent = wk.parent.p; a.size = wk.size.p; a.min_size = (unsigned long long)min_size; a.labels = sg->d_img.p;
         const dim3 grid((unsigned)((w + 63) / 64), (unsigned)((h + 15) / 16));
         hipLaunchKernelGGL(ym::seg_cc_init_kernel, grid, dim3(256), 0, stream, a);
         hipLaunchKernelGGL(ym::seg_cc_merge_kernel, grid, dim3(256), 0, stream, a);
@@ -215,21 +204,19 @@ ym_segments *ym_segments_from_map(int device, const uint8_t *image, int w, int h
     if (o.iterations < 1) { set_err(YM_ERR_INVALID, "iterations %d: at least 1", o.iterations); return nullptr; }
     if (o.min_size_div < 1) { set_err(YM_ERR_INVALID, "min_size_div %d: at least 1", o.min_size_div); return nullptr; }
     if (o.stage != YM_SEGMENT_STAGE_FINAL && o.stage != YM_SEGMENT_STAGE_ASSIGNED) { set_err(YM_ERR_INVALID, "stage %d: 0 or 1", o.stage); return nullptr; }
-    if (segmenter_check_device(device) != YM_OK) return nullptr;
+    if (check_device(device) != YM_OK) return nullptr;
     DevGuard guard(device);
-    if (!guard.ok) { set_err(YM_ERR_HIP, "cannot make device %d current", device); return nullptr; }
+    if (guard.status() != YM_OK) return nullptr;
     ym_segments *sg = new ym_segments();
     sg->device = device; sg->width = w; sg->height = h; sg->pitch = (w + 3) / 4 * 4;
     auto setup = [&]() -> int {
-        HIP_TRY(hipStreamCreateWithFlags(&sg->stream, hipStreamNonBlocking));
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sg->d_img), (size_t)sg->pitch * h * sizeof(int32_t)));
         int rc;
-        if ((rc = sg->range.ensure(2)) || (rc = sg->flags.ensure(4))) return rc;
+        if ((rc = sg->stream.create()) || (rc = sg->d_img.alloc((size_t)sg->pitch * h)) || (rc = sg->range.ensure(2)) || (rc = sg->flags.ensure(4))) return rc;
         return segmenter_run(sg, image, pitch, o, info);
     };
     if (setup() != YM_OK) { // (the error text is set)
         if (sg->stream) (void)hipStreamSynchronize(sg->stream);
-        segments_free(sg);
+        delete sg;
         return nullptr;
     }
     return sg;
@@ -241,7 +228,7 @@ int ym_segments_labels(ym_segments *sg, int32_t *labels, int64_t n) {
     if (!labels || n < 0 || (uint64_t)n < need) return set_err(YM_ERR_INVALID, "labels: room for %zu labels needed", need);
     DEV_GUARD(sg->device);
     HIP_TRY(hipStreamSynchronize(sg->stream));
-    HIP_TRY(hipMemcpy2D(labels, sizeof(int32_t) * sg->width, sg->d_img, sizeof(int32_t) * sg->pitch, sizeof(int32_t) * sg->width, sg->height,
+    HIP_TRY(hipMemcpy2D(labels, sizeof(int32_t) * sg->width, sg->d_img.p, sizeof(int32_t) * sg->pitch, sizeof(int32_t) * sg->width, sg->height,
                         hipMemcpyDeviceToHost));
     return YM_OK;
 }

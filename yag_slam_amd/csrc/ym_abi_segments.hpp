@@ -4,8 +4,8 @@ struct ym_segments {
     int device;
     int width, height, pitch; // the label image, resident on the device; pitch (elements) a multiple of 4
     int32_t min_label = 0, max_label = 0;
-    int32_t *d_img = nullptr;
-    hipStream_t stream = nullptr;
+    OwnStream stream;
+    DevBuf<int32_t> d_img;
     DevBuf<unsigned long long> sums, keys, first; // sums: count, sum_x, sum_y of every label, one after the other
     DevBuf<unsigned> counts, flags;
     DevBuf<int32_t> range, out_pairs, out_counts;
@@ -15,19 +15,9 @@ struct ym_segments {
 
 constexpr uint32_t kSegMaxSlots = 1u << 26; // the largest pair table the library grows to (20 bytes a slot)
 
-static void segments_free(ym_segments *sg) {
-    if (!sg) return;
-    DevGuard guard(sg->device);
-    if (sg->d_img) (void)hipFree(sg->d_img);
-    sg->sums.release(); sg->keys.release(); sg->first.release(); sg->counts.release(); sg->flags.release();
-    sg->range.release(); sg->out_pairs.release(); sg->out_counts.release(); sg->out_first.release(); sg->mask.release();
-    if (sg->stream) (void)hipStreamDestroy(sg->stream);
-    delete sg;
-}
-
 static ym::SegArgs segments_args(const ym_segments *sg) {
     ym::SegArgs a{};
-    a.img = sg->d_img; a.width = sg->width; a.height = sg->height; a.pitch = sg->pitch;
+    a.img = sg->d_img.p; a.width = sg->width; a.height = sg->height; a.pitch = sg->pitch;
     a.flags = sg->flags.p;
     return a;
 }
@@ -39,16 +29,14 @@ static dim3 segments_grid(const ym_segments *sg, int tile_h) {
 // upload + the label range (one launch), so that every later call knows the labels' bounds
 static int segments_upload(ym_segments *sg, const int32_t *labels, int pitch_elems) {
     const size_t n = (size_t)sg->pitch * sg->height;
-    HIP_TRY(hipStreamCreateWithFlags(&sg->stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&sg->d_img), n * sizeof(int32_t)));
+    int rc; // (every allocation before the copy is queued: no return below leaves the caller's buffer the source of a copy in flight)
+    if ((rc = sg->stream.create()) || (rc = sg->d_img.alloc(n)) || (rc = sg->range.ensure(2)) || (rc = sg->flags.ensure(4))) return rc;
     const size_t n_vec = (size_t)((sg->width + 3) / 4) * sg->height;
     const unsigned blocks = (unsigned)std::min<size_t>((n_vec + 255) / 256, ym::kSegRangeBlocks);
-    int rc; // (every allocation before the copy is queued: no return below leaves the caller's buffer the source of a copy in flight)
-    if ((rc = sg->range.ensure(2)) || (rc = sg->flags.ensure(4))) return rc;
     const int32_t init[2] = {INT32_MAX, INT32_MIN};
     HIP_TRY(hipMemcpy(sg->range.p, init, sizeof init, hipMemcpyHostToDevice));
     // (the padding columns stay as they are: every kernel masks them by coordinate)
-    HIP_TRY(hipMemcpy2D(sg->d_img, sizeof(int32_t) * sg->pitch, labels, sizeof(int32_t) * pitch_elems, sizeof(int32_t) * sg->width,
+    HIP_TRY(hipMemcpy2D(sg->d_img.p, sizeof(int32_t) * sg->pitch, labels, sizeof(int32_t) * pitch_elems, sizeof(int32_t) * sg->width,
                         sg->height, hipMemcpyHostToDevice));
     ym::SegArgs a = segments_args(sg);
     a.range = sg->range.p;
@@ -67,17 +55,12 @@ ym_segments *ym_segments_create(int device, const int32_t *labels, int width, in
         set_err(YM_ERR_INVALID, "label image of %d x %d pixels: at most 65536 x 65536 (the 64-bit sums stay exact)", width, height);
         return nullptr;
     }
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { set_err(YM_ERR_NO_DEVICE, "no HIP device"); return nullptr; }
-    if (device < 0 || device >= n_dev) { set_err(YM_ERR_NO_DEVICE, "device %d out of range (%d devices)", device, n_dev); return nullptr; }
+    if (check_device(device) != YM_OK) return nullptr;
     DevGuard guard(device);
-    if (!guard.ok) { set_err(YM_ERR_HIP, "cannot make device %d current", device); return nullptr; }
+    if (guard.status() != YM_OK) return nullptr;
     ym_segments *sg = new ym_segments();
     sg->device = device; sg->width = width; sg->height = height; sg->pitch = (width + 3) / 4 * 4;
-    if (segments_upload(sg, labels, pitch_elems) != YM_OK) { // (the error text is set)
-        segments_free(sg);
-        return nullptr;
-    }
+    if (segments_upload(sg, labels, pitch_elems) != YM_OK) { delete sg; return nullptr; } // (the error text is set)
     return sg;
 }
 
@@ -208,4 +191,8 @@ int ym_segments_pairs(ym_segments *sg, int table_slots, int cap, int32_t *pairs,
     return YM_OK;
 }
 
-void ym_segments_destroy(ym_segments *sg) { segments_free(sg); }
+void ym_segments_destroy(ym_segments *sg) {
+    if (!sg) return;
+    DevGuard guard(sg->device);
+    delete sg;
+}

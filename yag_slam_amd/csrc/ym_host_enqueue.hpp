@@ -105,7 +105,7 @@ int enqueue_raster(ym_matcher *m, const CallPlan &P) {
     a.tile_zero = m->tile_zero.p; a.sub_zero = m->sub_zero.p; a.planes_only = m->raster_planes_only;
     a.n_rowtab = m->raster_no_rowtab ? 0 : m->n_rowtab; a.rowtab = reinterpret_cast<const uint2 *>(m->rowtab.p); a.rowtab_shift = m->rowtab_shift; a.no_planes = P.win_only ? 1 : 0;
     const size_t rlds = YM_RASTER_LDS_BYTES(P.tile_h, g.half_kernel, a.n_rowtab);
-    a.tile_max = m->tile_max.p; a.tile_max_host = P.use_tile_list ? m->tile_max_host : nullptr;
+    a.tile_max = m->tile_max.p; a.tile_max_host = P.use_tile_list ? reinterpret_cast<int32_t *>(m->tile_max_host.p) : nullptr;
     a.hits = (P.use_tile_list && P.use_tile_hits) ? m->tile_hits.p : nullptr; a.lty = P.lty; a.pad0 = 0;
     int rc;
     hipEvent_t ev_k = nullptr;
@@ -113,7 +113,7 @@ int enqueue_raster(ym_matcher *m, const CallPlan &P) {
     if (P.ltx > 0 && P.lty > 0) {
         // blocks per item: the longest work list an earlier call of this matcher reported (+ 1/8), at most one per tile of
         // the sub-grid; the blocks stride over the list, so a stale or missing number only costs time
-        const int hint = m->tile_max_host ? *reinterpret_cast<volatile int32_t *>(m->tile_max_host) : 0;
+        const int hint = m->tile_max_host.p ? *reinterpret_cast<volatile int32_t *>(m->tile_max_host.p) : 0;
         const int gx = m->raster_gx > 0 ? std::min(P.ltx * P.lty, m->raster_gx)
                                         : hint > 0 ? std::min(P.ltx * P.lty, hint + hint / 8 + 2) : P.ltx * P.lty;
         a.first_overflow = gx;

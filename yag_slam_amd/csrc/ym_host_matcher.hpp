@@ -3,8 +3,8 @@
 struct ym_map {
     int device;
     int width, height;
-    double *d_cgrid;  // the float correlation grid as the reference holds it
-    uint8_t *d_g8;    // int(100 * cell): what scoring reads
+    DevBuf<double> d_cgrid;  // the float correlation grid as the reference holds it
+    DevBuf<uint8_t> d_g8;    // int(100 * cell): what scoring reads (+ 64 bytes)
 };
 
 struct ym_occupancy {
@@ -166,7 +166,7 @@ struct ym_matcher {
     DevBuf<int32_t> tile_count;
     DevBuf<int32_t> tile_max;        // [1] longest raster work list of the call
     DevBuf<uint16_t> tile_hits;      // per entry of the work list: the chunks that reach its tile (YM_TILE_HITS slots)
-    int32_t *tile_max_host = nullptr; // pinned: the raster kernel leaves that number here, the next call sizes its grid by it
+    PinnedBuf tile_max_host;         // one int32: the raster kernel leaves that number here, the next call sizes its grid by it
     int finish_form = 0; // development: 1 = fine_kernel + final_kernel even on batches, 2 = finish_kernel always
     int corr_chunks = 0; // development: force the number of beam chunks of the correlate kernel
     int corr_pad_lds = 0; // development: extra dynamic LDS per correlate block (limits blocks per CU)

@@ -754,9 +754,9 @@ int plan_raster(ym_matcher *m, Slot &slot, CallPlan &P) {
         if (P.use_tile_hits) {
             if ((rc = m->tile_hits.ensure((size_t)B * P.tile_cap * YM_TILE_HITS))) return rc;
         }
-        if (!m->tile_max_host) {
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&m->tile_max_host), sizeof(int32_t), hipHostMallocDefault));
-            *m->tile_max_host = 0;
+        if (!m->tile_max_host.p) {
+            if ((rc = m->tile_max_host.alloc(sizeof(int32_t)))) return rc;
+            *reinterpret_cast<int32_t *>(m->tile_max_host.p) = 0;
         }
     }
     return YM_OK;

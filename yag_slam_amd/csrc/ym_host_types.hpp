@@ -49,27 +49,48 @@ struct DevGuard {
     }
     DevGuard(const DevGuard &) = delete;
     DevGuard &operator=(const DevGuard &) = delete;
+    int status() const { return ok ? YM_OK : set_err(YM_ERR_HIP, "cannot make device %d current", dev); }
 };
-#define DEV_GUARD(d)                                                                     \
-    DevGuard dev_guard_(d);                                                              \
-    if (!dev_guard_.ok) return set_err(YM_ERR_HIP, "cannot make device %d current", (d))
+#define DEV_GUARD(d)                             \
+    DevGuard dev_guard_(d);                      \
+    if (int rc_ = dev_guard_.status()) return rc_
+
+// the device check of every entry that takes a device number
+int check_device(int device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
+        return set_err(YM_ERR_NO_DEVICE, "no HIP device available (libyagmatch has no CPU fallback)");
+    if (device < 0 || device >= n) return set_err(YM_ERR_NO_DEVICE, "device %d out of range [0, %d)", device, n);
+    return YM_OK;
+}
+
+// Ownership.  DevBuf, PinnedBuf and OwnStream free what they hold when they are destroyed, so a handle needs no list of
+// its buffers.  The one rule: an owner is destroyed while its device is current -- every ym_*_destroy takes the DevGuard
+// and then deletes the handle, and an owner on the stack is declared after the guard of its function.
+// (bytes the two buffer types hold, process-wide: ym_debug_live_bytes)
+std::atomic<int64_t> g_live_dev_bytes{0}, g_live_pinned_bytes{0};
 
 template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t cap = 0; // elements
-    int ensure(size_t n) {
-        if (n <= cap) return YM_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = n + n / 4 + 64;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), want * sizeof(T)));
-        cap = want;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    // room for n elements and a quarter more (buffers that grow with the calls)
+    int ensure(size_t n) { return n <= cap ? YM_OK : alloc(n + n / 4 + 64); }
+    // exactly n elements, whatever the buffer held (memory of a fixed size)
+    int alloc(size_t n) {
+        release();
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), n * sizeof(T)));
+        cap = n;
+        g_live_dev_bytes += (int64_t)(n * sizeof(T));
         return YM_OK;
     }
     void release() {
         if (p) (void)hipFree(p);
+        g_live_dev_bytes -= (int64_t)(cap * sizeof(T));
         p = nullptr;
         cap = 0;
     }
@@ -79,22 +100,37 @@ struct PinnedBuf {
     unsigned char *p = nullptr;   // host address
     unsigned char *dp = nullptr;  // the same memory as the device sees it
     size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return YM_OK;
-        if (p) (void)hipHostFree(p);
-        p = dp = nullptr;
-        cap = 0;
-        size_t want = align_up(n + n / 4 + 256, 256);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocMapped));
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { release(); }
+    int ensure(size_t n) { return n <= cap ? YM_OK : alloc(align_up(n + n / 4 + 256, 256)); }
+    int alloc(size_t n) { // exactly n bytes
+        release();
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&p), n, hipHostMallocMapped));
+        cap = n;
+        g_live_pinned_bytes += (int64_t)n;
         HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&dp), p, 0));
-        cap = want;
         return YM_OK;
     }
     void release() {
         if (p) (void)hipHostFree(p);
+        g_live_pinned_bytes -= (int64_t)cap;
         p = dp = nullptr;
         cap = 0;
     }
+};
+
+// a non-blocking stream of its own.  In a handle it is declared BEFORE the buffers: members are destroyed in reverse
+// order, so the stream goes after the memory its work used.
+struct OwnStream {
+    hipStream_t s = nullptr;
+    OwnStream() = default;
+    OwnStream(const OwnStream &) = delete;
+    OwnStream &operator=(const OwnStream &) = delete;
+    ~OwnStream() { if (s) (void)hipStreamDestroy(s); }
+    int create() { HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); return YM_OK; }
+    operator hipStream_t() const { return s; }
 };
 
 // a scan as a call sees it: device ranges + metadata + pose
