@@ -288,6 +288,32 @@ int ym_occupancy_read(const ym_occupancy *og, uint8_t *image, int64_t image_byte
 int ym_occupancy_read_counts(const ym_occupancy *og, uint32_t *pass, uint32_t *hits, int64_t cells);
 void ym_occupancy_destroy(ym_occupancy *og);
 
+/* ---- the map the ROS node publishes: the rendered grid with its specks removed (ros1/slam_node_ros1:187-212, _make_map).
+ * The filter, all integer: fg = (image == foreground); the components of fg under `connectivity` (8:
+ * coordinates differ by at most 1 in both axes, cv2's default and the node's; 4: cells that share an edge); every cell of a
+ * component of fewer than min_area cells becomes `fill`.  The node's loop also visits cv2's label 0, the background: with B =
+ * the cells != foreground, 0 < B < min_area turns every one of them into `fill` too (background_filled = 1).  Every other
+ * cell is unchanged; the result is not examined again.  foreground and fill in 0 .. 255, min_area >= 0, connectivity 4 or 8:
+ * anything else is YM_ERR_INVALID before any launch.  width * height above 2^31 - 1: YM_ERR_UNSUPPORTED.  The output is the
+ * same from run to run.  Parity: the rules are the node's by definition; cv2's labelling itself is unpinned (only areas are used).
+ *   ym_image_despeckle                replaces slam_node_ros1:191-197 (static_only, cv2.connectedComponentsWithStats, the loop
+ *                                     over its statistics) for any byte image; `pitch` bytes between rows; opts null: the
+ *                                     node's 0 / 255 / 5 / 8.  `out` and `stats` are written only when the call succeeds.
+ *   ym_occupancy_create_clean         replaces slam_node_ros1:188-197: the three launches of ym_occupancy_create, then the filter
+ *                                     on the device image, then the single copy to the host.  ym_occupancy_get_info and
+ *                                     ym_occupancy_read serve its handle like any other.
+ *   ym_occupancy_get_despeckle_stats  what that filter counted (the node keeps no such figures; it replaces nothing of
+ *                                     slam_node_ros1 and is there for logs and tests).  Fails on a handle of the other creators.
+ * cleared_cells counts foreground cells only; the background rule's cells are background_cells when background_filled. */
+typedef struct ym_despeckle_opts { int32_t foreground, fill, min_area, connectivity; } ym_despeckle_opts;
+typedef struct ym_despeckle_stats { int64_t foreground_cells, components, removed_components, cleared_cells, background_cells;
+                                    int32_t background_filled, reserved; } ym_despeckle_stats;
+int ym_image_despeckle(int device, const uint8_t *image, int width, int height, int pitch,
+                       const ym_despeckle_opts *opts, uint8_t *out /* width*height */, ym_despeckle_stats *stats /* may be null */);
+ym_occupancy *ym_occupancy_create_clean(const ym_scan *const *scans, int n_scans, double resolution, double range_threshold,
+                                        const ym_despeckle_opts *opts /* null: the node's 0 / 255 / 5 / 8 */);
+int ym_occupancy_get_despeckle_stats(const ym_occupancy *og, ym_despeckle_stats *stats); /* fails on a handle of the other creators */
+
 /* ---- virtual scans from an occupancy image: the ray casting of the ROS node's "start in a prior map" path
  * (ingest_base_map -> map_to_graphslam -> map_to_graph, /root/reference/ros1/slam_node_ros1:131-147,
  * /root/reference/yag_slam/splicing.py:82-107).  ym_raymap_trace is run_raytracing_sweep (raytracing.py:91-92) for

@@ -25,7 +25,7 @@ EXPORTS = (
     "ym_profile_read", "ym_cache_stats", "ym_debug_counters",
     "ym_coarse_dims", "ym_match_slice_begin", "ym_match_slice_finish",
     "ym_occupancy_create", "ym_occupancy_create_counted", "ym_occupancy_get_info", "ym_occupancy_read", "ym_occupancy_read_counts",
-    "ym_occupancy_destroy",
+    "ym_occupancy_destroy", "ym_image_despeckle", "ym_occupancy_create_clean", "ym_occupancy_get_despeckle_stats",
     "ym_map_from_occupancy", "ym_map_from_grid", "ym_map_size", "ym_map_read", "ym_map_destroy", "ym_match_map",
     "ym_raymap_create", "ym_raymap_trace", "ym_raymap_trace_each", "ym_raymap_destroy",
     "ym_locator_create", "ym_locator_get_info", "ym_locator_read_level", "ym_locator_locate", "ym_locator_destroy",
@@ -94,6 +94,15 @@ class YmResult(C.Structure):
 class YmOccupancyInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("offset_x", C.c_double), ("offset_y", C.c_double),
                 ("resolution", C.c_double)]
+
+
+class YmDespeckleOpts(C.Structure):
+    _fields_ = [("foreground", C.c_int32), ("fill", C.c_int32), ("min_area", C.c_int32), ("connectivity", C.c_int32)]
+
+
+class YmDespeckleStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("foreground_cells", "components", "removed_components", "cleared_cells",
+                                        "background_cells")] + [("background_filled", C.c_int32), ("reserved", C.c_int32)]
 
 
 class YmMapSearch(C.Structure):
@@ -252,6 +261,11 @@ def lib():
     L.ym_occupancy_read_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int64]
     L.ym_occupancy_destroy.argtypes = [vp]
     L.ym_occupancy_destroy.restype = None
+    L.ym_image_despeckle.argtypes = [C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.POINTER(YmDespeckleOpts),
+                                     C.POINTER(C.c_uint8), C.POINTER(YmDespeckleStats)]
+    L.ym_occupancy_create_clean.restype = vp
+    L.ym_occupancy_create_clean.argtypes = [C.POINTER(vp), C.c_int, C.c_double, C.c_double, C.POINTER(YmDespeckleOpts)]
+    L.ym_occupancy_get_despeckle_stats.argtypes = [vp, C.POINTER(YmDespeckleStats)]
     L.ym_map_from_occupancy.restype = vp
     L.ym_map_from_occupancy.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int]
     L.ym_map_from_grid.restype = vp

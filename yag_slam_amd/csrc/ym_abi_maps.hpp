@@ -192,9 +192,82 @@ int ym_match_map(ym_matcher *m, const ym_map *mp, double ox, double oy, const ym
     return YM_OK;
 }
 
+// ---- the component area filter (ym_k_despeckle.hpp)
+static const ym_despeckle_opts kNodeDespeckle = {0, 255, 5, 8}; // ros1/slam_node_ros1:191-197
+
+static int despeckle_check_opts(const ym_despeckle_opts &o) {
+    if (o.foreground < 0 || o.foreground > 255) return set_err(YM_ERR_INVALID, "foreground %d: 0 .. 255", o.foreground);
+    if (o.fill < 0 || o.fill > 255) return set_err(YM_ERR_INVALID, "fill %d: 0 .. 255", o.fill);
+    if (o.min_area < 0) return set_err(YM_ERR_INVALID, "min_area %d: 0 or more", o.min_area);
+    if (o.connectivity != 4 && o.connectivity != 8) return set_err(YM_ERR_INVALID, "connectivity %d: 4 or 8", o.connectivity);
+    return YM_OK;
+}
+
+// d_image -> d_out (both dense [height][width] on the current device; they may be the same), the statistics to *stats.
+// Four launches on `stream` and one wait; the working memory is freed when the call ends, whatever its outcome.
+static int despeckle_run(const uint8_t *d_image, uint8_t *d_out, int width, int height, const ym_despeckle_opts &o, hipStream_t stream,
+                         ym_despeckle_stats *stats) {
+    const size_t n = (size_t)width * height;
+    DevBuf<unsigned> parent, size;
+    DevBuf<unsigned long long> d_stats;
+    int rc;
+    if ((rc = parent.alloc(n)) || (rc = size.alloc(n)) || (rc = d_stats.alloc(ym::kDspStatSlots))) return rc;
+    HIP_TRY(hipMemsetAsync(d_stats.p, 0, ym::kDspStatSlots * sizeof(unsigned long long), stream));
+    ym::DespeckleArgs a{};
+    a.image = d_image; a.out = d_out; a.width = width; a.height = height; a.nbx = (width + 63) / 64;
+    a.foreground = o.foreground; a.fill = o.fill; a.min_area = (unsigned)o.min_area;
+    a.parent = parent.p; a.size = size.p; a.stats = d_stats.p;
+    const dim3 grid((unsigned)((size_t)a.nbx * (size_t)((height + 15) / 16))); // (below 2^31: width * height is)
+    hipLaunchKernelGGL(ym::dsp_init_kernel, grid, dim3(256), 0, stream, a);
+    if (o.connectivity == 8) hipLaunchKernelGGL(ym::dsp_merge_kernel<8>, grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(ym::dsp_merge_kernel<4>, grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(ym::dsp_sizes_kernel, grid, dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(ym::dsp_apply_kernel, grid, dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    unsigned long long got[ym::kDspStatSlots];
+    HIP_TRY(hipMemcpyAsync(got, d_stats.p, sizeof got, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    if (got[ym::kDspErr]) return set_err(YM_ERR_HIP, "the component pass reached its retry cap (a fault of the library)");
+    if (stats) {
+        ym_despeckle_stats s{};
+        s.foreground_cells = (int64_t)got[ym::kDspFg]; s.background_cells = (int64_t)got[ym::kDspBg];
+        s.components = (int64_t)got[ym::kDspComponents]; s.removed_components = (int64_t)got[ym::kDspRemoved];
+        s.cleared_cells = (int64_t)got[ym::kDspCleared];
+        s.background_filled = s.background_cells > 0 && s.background_cells < (int64_t)o.min_area ? 1 : 0;
+        *stats = s;
+    }
+    return YM_OK;
+}
+
+int ym_image_despeckle(int device, const uint8_t *image, int width, int height, int pitch, const ym_despeckle_opts *opts, uint8_t *out,
+                       ym_despeckle_stats *stats) {
+    const ym_despeckle_opts o = opts ? *opts : kNodeDespeckle;
+    int rc;
+    if ((rc = despeckle_check_opts(o))) return rc;
+    if (!image || !out) return set_err(YM_ERR_INVALID, "image or out: null");
+    if (width < 1 || height < 1) return set_err(YM_ERR_INVALID, "image of %d x %d cells", width, height);
+    if (pitch < width) return set_err(YM_ERR_INVALID, "pitch %d: at least width (%d bytes)", pitch, width);
+    if ((int64_t)width * height > (int64_t)INT32_MAX)
+        return set_err(YM_ERR_UNSUPPORTED, "image of %d x %d cells: at most 2^31 - 1", width, height);
+    if ((rc = check_device(device))) return rc;
+    DEV_GUARD(device);
+    const size_t n = (size_t)width * height;
+    DevBuf<uint8_t> d_img;
+    if ((rc = d_img.alloc(n))) return rc;
+    HIP_TRY(hipMemcpy2D(d_img.p, (size_t)width, image, (size_t)pitch, (size_t)width, (size_t)height, hipMemcpyHostToDevice));
+    ym_despeckle_stats s{};
+    if ((rc = despeckle_run(d_img.p, d_img.p, width, height, o, nullptr, &s))) return rc;
+    // (the outputs are written only once the whole call has succeeded: `out` by the one copy that can still fail)
+    HIP_TRY(hipMemcpy(out, d_img.p, n, hipMemcpyDeviceToHost));
+    if (stats) *stats = s;
+    return YM_OK;
+}
+
 // ---- occupancy-grid rendering (karto_scanmatcher.create_occupancy_grid)
 // keep_counts (ym_occupancy_create_counted, a test hook): the pass and hit counts are copied to the host before they are freed
-static ym_occupancy *occupancy_render(const ym_scan *const *scans, int n_scans, double resolution, double range_threshold, bool keep_counts) {
+// clean (ym_occupancy_create_clean): the image goes through the component area filter on the device before its copy to the host
+static ym_occupancy *occupancy_render(const ym_scan *const *scans, int n_scans, double resolution, double range_threshold, bool keep_counts,
+                                      const ym_despeckle_opts *clean = nullptr) {
     if (!scans || n_scans <= 0) { set_err(YM_ERR_INVALID, "no scans"); return nullptr; }
     if (!(resolution > 0) || !(range_threshold > 0)) { set_err(YM_ERR_INVALID, "resolution and range_threshold must be > 0"); return nullptr; }
     const int device = scans[0] ? scans[0]->device : -1;
@@ -253,6 +326,11 @@ static ym_occupancy *occupancy_render(const ym_scan *const *scans, int n_scans, 
         HIP_TRY(hipGetLastError());
         og->info.width = width; og->info.height = height;
         og->info.offset_x = x0; og->info.offset_y = y0; og->info.resolution = resolution;
+        if (clean) {
+            if (n > (size_t)INT32_MAX) return set_err(YM_ERR_UNSUPPORTED, "occupancy grid of %d x %d cells: the filter takes at most 2^31 - 1", width, height);
+            if ((rc = despeckle_run(d_img.p, d_img.p, width, height, *clean, nullptr, &og->clean_stats))) return rc;
+            og->cleaned = true;
+        }
         og->image.resize(n);
         HIP_TRY(hipMemcpy(og->image.data(), d_img.p, n, hipMemcpyDeviceToHost));
         if (keep_counts) {
@@ -271,6 +349,20 @@ ym_occupancy *ym_occupancy_create(const ym_scan *const *scans, int n_scans, doub
 
 ym_occupancy *ym_occupancy_create_counted(const ym_scan *const *scans, int n_scans, double resolution, double range_threshold) {
     return occupancy_render(scans, n_scans, resolution, range_threshold, true);
+}
+
+ym_occupancy *ym_occupancy_create_clean(const ym_scan *const *scans, int n_scans, double resolution, double range_threshold,
+                                        const ym_despeckle_opts *opts) {
+    const ym_despeckle_opts o = opts ? *opts : kNodeDespeckle;
+    if (despeckle_check_opts(o) != YM_OK) return nullptr; // (the error text is set)
+    return occupancy_render(scans, n_scans, resolution, range_threshold, false, &o);
+}
+
+int ym_occupancy_get_despeckle_stats(const ym_occupancy *og, ym_despeckle_stats *stats) {
+    if (!og || !stats) return set_err(YM_ERR_INVALID, "null argument");
+    if (!og->cleaned) return set_err(YM_ERR_INVALID, "this grid was made without the filter: use ym_occupancy_create_clean");
+    *stats = og->clean_stats;
+    return YM_OK;
 }
 
 int ym_occupancy_get_info(const ym_occupancy *og, ym_occupancy_info *info) {

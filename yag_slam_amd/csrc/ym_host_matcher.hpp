@@ -12,6 +12,8 @@ struct ym_occupancy {
     ym_occupancy_info info;
     std::vector<uint8_t> image; // [height][width], row 0 = lowest y
     std::vector<uint32_t> counts; // ym_occupancy_create_counted only: pass [height][width], then hits [height][width]
+    bool cleaned = false;         // ym_occupancy_create_clean only: the image went through the component area filter,
+    ym_despeckle_stats clean_stats{}; // ... and this is what it counted
 };
 
 struct ym_batch {

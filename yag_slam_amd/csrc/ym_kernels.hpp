@@ -36,4 +36,5 @@
 #include "ym_k_locate.hpp"
 #include "ym_k_segments.hpp"
 #include "ym_k_segmenter.hpp"
+#include "ym_k_despeckle.hpp"
 #include "ym_k_posegraph.hpp"

@@ -259,6 +259,11 @@ class LoopClosingMapper(SequentialMapper):
         from .occupancy import create_occupancy_grid
         return create_occupancy_grid(self.scans, resolution, range_threshold, device=getattr(self.seq_matcher, "device", 0))
 
+    def make_ros_map(self, resolution=0.05, range_threshold=12):
+        """slam_node_ros1:187-209 (`_make_map`): that grid with its specks removed and the codes of nav_msgs/OccupancyGrid"""
+        from .occupancy import ros_map
+        return ros_map(self.scans, resolution, range_threshold, device=getattr(self.seq_matcher, "device", 0))
+
     def run_opt(self):
         """graph_slam.py:262-272; a no-op without an optimizer except for the spatial index refresh"""
         if self.opt is not None:
