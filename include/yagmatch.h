@@ -95,7 +95,8 @@ typedef struct ym_result {
     int32_t n_query_points; /* response normaliser */
     int32_t expansions;     /* response-expansion retries taken */
     int32_t status;         /* YM_OK or YM_ERR_RANGE for this item */
-    int32_t reserved;
+    int32_t reserved;       /* 0; ym_map_track: 1 when the step's correction was NOT applied (response < min_response: the scan
+                               keeps its odometry prior), status staying 0 */
 } ym_result;
 
 typedef struct ym_matcher ym_matcher;
@@ -263,6 +264,36 @@ typedef struct ym_map_search {
  * mean pose (x, y, heading); the caller moves every query by its difference to the uncorrected mean. */
 int ym_match_map(ym_matcher *m, const ym_map *map, double ox, double oy, const ym_scan *const *queries, int n_queries,
                  int penalize, int refine, const ym_map_search *coarse, ym_result *out);
+
+/* ---- localization mode: scans matched against a resident map without a graph.
+ *   ym_match_map_many   stands for n_items separate Scan2DMatcherPy.match_scan_sets_with_map calls on one map
+ *                       (/root/reference/yag_slam/scan_matching.py:124-173) in one enqueue and one wait: item i is the query set
+ *                       queries[set_offsets[i] .. set_offsets[i+1]) (1 to 64 scans; sets may differ in size and point count), and
+ *                       results[i] is byte for byte the ym_result of ym_match_map on that set alone -- response, pose, covariance,
+ *                       coarse_response, dims, hypotheses, n_query_points, status.  An item whose status is not 0 (no query point,
+ *                       empty lattice) leaves its neighbours alone.  The integer sums of both passes come from yag_map_kernel for
+ *                       lattices up to 64 positions per axis and from the pair-by-pair kernel for wider ones (ym_debug_counters
+ *                       [6], [7]).  The scratch of the call is bounded (256 MiB of volumes: 268 items with the reference's constants);
+ *                       more items run as consecutive chunks inside the call, and no result depends on the chunk length (debug
+ *                       option 47 forces it).  Uses the matcher's synchronous slot and stream; YM_SEM_YAGPY only; never throws.
+ *   ym_map_track        stands for the loop a localization-only node runs per incoming scan -- the odometry prior of
+ *                       GraphSlam.process_scan (/root/reference/yag_slam/graph_slam.py:320-324), then match_scan_sets_with_map([scan])
+ *                       -- for n_tracks scan streams in lock-step.  Track r is scans[track_offsets[r] .. track_offsets[r+1]); odom
+ *                       holds 3 doubles per scan, parallel to `scans`; the scans before `start` (>= 1) of a track carry their poses.
+ *                       Step i of all tracks that still have a scan i is ONE ym_match_map_many enqueue of single-scan items.  Per
+ *                       item: prior = pose[i-1] (+) ((-)odom[i-1] (+) odom[i]) with transform.py's operations on the host, the scan's
+ *                       pose is set to it and the set {scan i} is matched (its centre is the prior's position).  status != 0: the track
+ *                       ends, n_done[r] = i, the scan keeps the prior, the other tracks go on.  response < min_response: the scan keeps
+ *                       the prior and results[..].reserved = 1 (status stays 0).  Otherwise the pose becomes (R.x, R.y, prior.heading
+ *                       + R.heading): the rigid motion of a one-scan set about its own position.  results is parallel to `scans`
+ *                       (entries of scans that are not matched are zeroed); n_done[r] = the track's length when it ran to its end.
+ *                       Bit-identical to that loop made of ym_scan_set_pose and ym_match_map calls. */
+int ym_match_map_many(ym_matcher *m, const ym_map *map, double ox, double oy, const ym_scan *const *queries,
+                      const int32_t *set_offsets, int n_items, int penalize, int refine, const ym_map_search *coarse,
+                      ym_result *results);
+int ym_map_track(ym_matcher *m, const ym_map *map, double ox, double oy, ym_scan *const *scans, const double *odom,
+                 const int32_t *track_offsets, int n_tracks, int start, int penalize, int refine, const ym_map_search *coarse,
+                 double min_response, ym_result *results, int32_t *n_done);
 
 /* ---- occupancy-grid rendering: karto_scanmatcher.create_occupancy_grid(scans, resolution, range_threshold)
  * (/root/reference/yag_slam/graph_slam.py:341-342, /root/reference/ros1/slam_node_ros1:187-202).  Every scan is ray-traced
@@ -524,6 +555,9 @@ int ym_debug_grid_info(ym_matcher *m, int item, ym_grid_info *info);
 int ym_debug_grid(ym_matcher *m, int item, uint8_t *out, int64_t out_bytes); /* height*pitch bytes */
 /* integer correlation sums [itheta][iy][ix] of pass 0 (coarse) / 1 (fine) */
 int ym_debug_sums(ym_matcher *m, int item, int pass, uint32_t *out, int64_t out_count);
+/* test hook: the same of item `item` of the last MAP call (ym_match_map_many; ym_match_map: item 0), dense with the item's own nx,
+ * ny, nt: out_count >= nx ny nt.  A call of more than 128 items keeps the sums of its last chunk only. */
+int ym_debug_map_sums(ym_matcher *m, int item, int pass, uint32_t *out, int64_t out_count);
 /* query points in the sensor frame (xy interleaved), returns count via *n */
 int ym_debug_query_local(ym_matcher *m, int item, double *out_xy, int32_t cap, int32_t *n);
 /* window cell coordinates of the rasterised base points of `item`, per base scan slot:
@@ -574,6 +608,7 @@ int ym_debug_cells(ym_matcher *m, int item, int32_t *out, int64_t out_count, int
  *                                          provably form a lattice: ym_debug_counters; the fine pass's are taken row by row);
  *                                          2: the default, with the fine pass reading its rows byte by byte (the path of a row whose
  *                                          columns do not fit one 8-byte read)
+ *   47      n / 0                          items per chunk of ym_match_map_many whatever its scratch budget says / by the budget
  */
 int ym_debug_option(ym_matcher *m, int option, int value);
 
@@ -582,7 +617,9 @@ int ym_debug_option(ym_matcher *m, int option, int value);
  *   kernel (a rounding tie that falls differently along the lattice, a read outside the device window, an np.arange longer than the launch
  *   lattice), [2] (point, angle) pairs that needed the hypothesis-by-hypothesis check, [3] pairs that failed it;
  *   [4] single-query batches that found their pair lists in place (option 45);
- *   [5] the coarse correlate the LAST call launched: 0 correlate_kernel, 1 correlate_region_kernel, 2 gather_kernel, -1 none */
+ *   [5] the coarse correlate the LAST call launched: 0 correlate_kernel, 1 correlate_region_kernel, 2 gather_kernel, -1 none;
+ *   [6] items of ym_match_map_many whose sums came from yag_map_kernel, [7] items it left to the pair-by-pair kernel (a coarse
+ *   lattice of more than 64 positions on an axis) */
 #define YM_DEBUG_COUNTERS 8
 int ym_debug_counters(ym_matcher *m, int64_t *out, int32_t count);
 

@@ -27,6 +27,7 @@ EXPORTS = (
     "ym_occupancy_create", "ym_occupancy_create_counted", "ym_occupancy_get_info", "ym_occupancy_read", "ym_occupancy_read_counts",
     "ym_occupancy_destroy", "ym_image_despeckle", "ym_occupancy_create_clean", "ym_occupancy_get_despeckle_stats",
     "ym_map_from_occupancy", "ym_map_from_grid", "ym_map_size", "ym_map_read", "ym_map_destroy", "ym_match_map",
+    "ym_match_map_many", "ym_map_track", "ym_debug_map_sums",
     "ym_raymap_create", "ym_raymap_trace", "ym_raymap_trace_each", "ym_raymap_destroy",
     "ym_locator_create", "ym_locator_get_info", "ym_locator_read_level", "ym_locator_locate", "ym_locator_destroy",
     "ym_segments_create", "ym_segments_label_range", "ym_segments_stats", "ym_segments_boundaries", "ym_segments_pairs",
@@ -276,6 +277,11 @@ def lib():
     L.ym_map_destroy.restype = None
     L.ym_match_map.argtypes = [vp, vp, C.c_double, C.c_double, C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(YmMapSearch),
                                C.POINTER(YmResult)]
+    L.ym_match_map_many.argtypes = [vp, vp, C.c_double, C.c_double, C.POINTER(vp), ip, C.c_int, C.c_int, C.c_int, C.POINTER(YmMapSearch),
+                                    C.POINTER(YmResult)]
+    L.ym_map_track.argtypes = [vp, vp, C.c_double, C.c_double, C.POINTER(vp), dp, ip, C.c_int, C.c_int, C.c_int, C.c_int,
+                               C.POINTER(YmMapSearch), C.c_double, C.POINTER(YmResult), ip]
+    L.ym_debug_map_sums.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_int64]
     L.ym_raymap_create.restype = vp
     L.ym_raymap_create.argtypes = [C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int]
     L.ym_raymap_trace.argtypes = [vp, dp, C.c_int, dp, C.c_int, C.POINTER(C.c_float), dp, C.POINTER(C.c_int64)]

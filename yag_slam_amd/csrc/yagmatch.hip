@@ -41,6 +41,7 @@ extern "C" {
 #include "ym_abi_scans.hpp"
 #include "ym_abi_match.hpp"
 #include "ym_abi_maps.hpp"
+#include "ym_abi_maptrack.hpp"
 #include "ym_abi_rays.hpp"
 #include "ym_abi_locate.hpp"
 #include "ym_abi_segments.hpp"

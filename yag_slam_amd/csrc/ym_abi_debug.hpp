@@ -114,6 +114,7 @@ int ym_debug_option(ym_matcher *m, int option, int value) {
     else if (option == 45) { m->list_cache_on = value != 0; m->list_key_valid = false; }
     else if (option == 46) m->yag_fast = value < 0 ? 0 : value > 2 ? 1 : value;
     else if (option == 43) m->rg2_h = value;
+    else if (option == 47) m->map_chunk_forced = value > 0 ? value : 0;
     else if (option == 44) {
 #ifndef YM_EXPERIMENTAL
         return set_err(YM_ERR_UNSUPPORTED, "correlate_region2_kernel is compiled only into builds made with -DYM_EXPERIMENTAL");
@@ -209,14 +210,35 @@ int ym_debug_counters(ym_matcher *m, int64_t *out, int32_t count) {
     std::memset(v, 0, sizeof v);
     if (m->yag_counters.p) {
         DEV_GUARD(m->device);
-        unsigned long long c[4];
+        unsigned long long c[6];
         HIP_TRY(hipStreamSynchronize(m->stream));
         HIP_TRY(hipMemcpy(c, m->yag_counters.p, sizeof c, hipMemcpyDeviceToHost));
         for (int i = 0; i < 4; i++) v[i] = (int64_t)c[i];
+        v[6] = (int64_t)c[4]; v[7] = (int64_t)c[5];
     }
     v[4] = m->list_cache_hits;
     v[5] = m->last_corr_form;
+    v[7] += m->map_fallback_host;
     for (int i = 0; i < std::min<int>(count, YM_DEBUG_COUNTERS); i++) out[i] = v[i];
+    return YM_OK;
+}
+
+// the dense [k][iy][ix] integer sums of item `item`, pass `pass`, of the last map call (ym_match_map: item 0)
+int ym_debug_map_sums(ym_matcher *m, int item, int pass, uint32_t *out, int64_t out_count) {
+    if (!m || !out || pass < 0 || pass > 1) return set_err(YM_ERR_INVALID, "bad argument");
+    const ym_matcher::MapLast &ml = m->map_last;
+    if (m->last_valid || !ml.valid) return set_err(YM_ERR_INVALID, "the last call was not a map call");
+    if (item < 0 || item >= ml.n_items) return set_err(YM_ERR_INVALID, "no such item in the last map call");
+    if (pass >= ml.passes) return set_err(YM_ERR_INVALID, "pass %d did not run", pass);
+    if (item < ml.first_kept) return set_err(YM_ERR_INVALID, "the sums of item %d were overwritten: a call of this size keeps those from item %d on", item, ml.first_kept);
+    DEV_GUARD(m->device);
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    YmItemState s;
+    HIP_TRY(hipMemcpy(&s, m->states.p + item, sizeof s, hipMemcpyDeviceToHost));
+    const size_t n = (size_t)s.ydims[pass][0] * s.ydims[pass][1] * s.ydims[pass][2];
+    if (n > ml.vol) return set_err(YM_ERR_HIP, "item %d has a lattice larger than its volume (a fault of the library)", item);
+    if (out_count < 0 || (size_t)out_count < n) return set_err(YM_ERR_INVALID, "sums buffer too small: need %zu entries", n);
+    if (n) HIP_TRY(hipMemcpy(out, m->sums.p + ml.pass_offset[pass] + (size_t)(item - ml.first_kept) * ml.vol, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return YM_OK;
 }
 

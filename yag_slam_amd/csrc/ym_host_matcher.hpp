@@ -140,6 +140,12 @@ struct ym_matcher {
     int last_corr_form = -1; // which coarse correlate the last call launched: 0 correlate_kernel, 1 correlate_region_kernel, 2 gather_kernel, -1 none
     DevBuf<unsigned long long> yag_counters; // [0] items through the production kernels, [1] fallbacks, [2] pairs checked exhaustively, [3] pairs that failed
     DevBuf<double> yaxes;      // yagpy: xvals, yvals, tvals per item
+    // map batches (ym_match_map_many, ym_abi_maptrack.hpp)
+    int map_chunk_forced = 0;        // option 47: items per chunk whatever the scratch budget says (tests)
+    int64_t map_fallback_host = 0;   // items of chunks whose lattice is so wide that yag_map_kernel was not even launched
+    // what ym_debug_map_sums needs of the last map call: how many items, entries per item volume, where each pass starts in `sums`,
+    // the first item whose volume is still there (a call too large to keep them all keeps its last chunk's)
+    struct MapLast { bool valid = false; int n_items = 0, first_kept = 0, passes = 0; size_t vol = 0, pass_offset[2] = {0, 0}; } map_last;
     DevBuf<double2> yrot;      // yagpy: points rotated per angle
     DevBuf<double> seq_pose;   // device-chained sequences: [0..2] the next step's odometry prior, [4 + 3k ..] the pose step k of the segment found
     DevBuf<int32_t> seq_fault; // ... and the first step the host has to repeat (0: none)

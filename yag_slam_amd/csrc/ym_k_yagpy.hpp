@@ -51,7 +51,10 @@ struct YagArgs {
     size_t lsums_stride;
     int32_t fine_rows, n_items;     // pass 1: yag_fine_kernel scores the items whose fine lattice is at most YM_YAG_FINE_DIM wide (all of them)
     unsigned long long *counters; // [0] items whose coarse pass went through the production kernels, [1] items that fell back to yag_score_kernel,
-                                  // [2] (point, angle) pairs that needed the exhaustive check, [3] pairs that failed it
+                                  // [2] (point, angle) pairs that needed the exhaustive check, [3] pairs that failed it,
+                                  // [4] map items yag_map_kernel served, [5] map items it left to yag_score_kernel (a lattice wider than its limit)
+    int32_t map_dim, map_split;   // map batches: yag_map_kernel has scored the items whose lattice is at most map_dim wide per axis (0: it did
+                                  // not run); map_split > 1: that many blocks share the points of an (item, angle) and add their sums up in `sums`
 };
 
 // numpy.arange(start, stop, step) for float64: length and i-th value (DOUBLE_fill)
@@ -201,6 +204,7 @@ __global__ __launch_bounds__(256) void yag_score_kernel(YagArgs a) {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (k >= nt || c >= nx * ny) return;
     if (a.fine_rows && nx <= YM_YAG_FINE_DIM && ny <= YM_YAG_FINE_DIM) return; // (pass 1: yag_fine_kernel has scored this item)
+    if (a.map_dim && nx <= a.map_dim && ny <= a.map_dim) return;               // (map batches: yag_map_kernel has)
     const int iy = c / nx, ix = c - iy * nx;
     const double *ax = a.axes + (size_t)b * 3 * YM_YAG_MAX_DIM;
     const double xv = ax[ix], yv = ax[YM_YAG_MAX_DIM + iy], tv = ax[2 * YM_YAG_MAX_DIM + k];

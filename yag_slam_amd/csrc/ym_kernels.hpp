@@ -31,6 +31,7 @@
 #endif
 #include "ym_k_gather.hpp"
 #include "ym_k_yagpy.hpp"
+#include "ym_k_yagmap.hpp"
 #include "ym_k_occupancy.hpp"
 #include "ym_k_raytrace.hpp"
 #include "ym_k_locate.hpp"

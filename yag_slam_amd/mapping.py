@@ -336,3 +336,63 @@ class LoopClosingMapper(SequentialMapper):
         self.link_scans(scan, candidates[0], res.covariance)
         self.running_scans.append(scan)
         return res
+
+
+class MapLocalizer(object):
+    """Localization mode: follow a robot through a resident map without growing a graph (`ScanMatcher.track_in_map`,
+    `ym_map_track`).  No vertex, no constraint, no running chain: the map is the only thing scans are matched against.
+
+    matcher: a `ScanMatcher(..., semantics="yagpy")`; cmap: its resident CorrelationMap whose cell (0, 0) lies at world
+    (ox, oy); coarse: dict overriding the coarse pass of `match_scan_sets_with_map`; min_response: below it a step's
+    correction is not applied and the scan keeps its odometry prior (dead reckoning).
+
+    `last` is the last scan processed (its `corrected_pose` is the robot's pose in the map), `lost` the number of
+    consecutive steps whose correction was not applied, `results` every step's result."""
+
+    def __init__(self, matcher, cmap, ox, oy, coarse=None, min_response=0.0):
+        self.matcher, self.cmap, self.ox, self.oy = matcher, cmap, ox, oy
+        self.coarse, self.min_response = coarse, min_response
+        self.last = None
+        self.lost = 0
+        self.results = []
+
+    def start(self, scan, **locate_kw):
+        """The first scan.  With its pose known (`corrected_pose` and `odom_pose` set by the caller) it only becomes `last`;
+        with keywords for `ScanMatcher.locate_in_map` it is located in the map first (`relocalize`) and both poses are set
+        to the located, polished pose.  Returns the locate result, or None."""
+        res = None
+        if locate_kw:
+            res = self.matcher.locate_in_map(self.cmap, self.ox, self.oy, [scan], **locate_kw)
+            p = res.best_pose[0]
+            scan.odom_pose = Transform(p.x, p.y, 0.0, p.euler[-1])
+            scan.corrected_pose = Transform(p.x, p.y, 0.0, p.euler[-1])
+        self.last, self.lost = scan, 0
+        return res
+
+    def process_scan(self, scan):
+        """One step of one track: prior = last.corrected_pose + (scan.odom_pose - last.odom_pose), the match against the
+        map, `scan.corrected_pose` = the corrected pose (or the prior).  Returns the result (meta["accepted"]); the very
+        first scan only starts the track (None)."""
+        out = self.process_scans([scan])
+        return out[0] if out else None
+
+    def process_scans(self, scans):
+        """`process_scan` for several scans of the stream in ONE library call; the list of their results.  A scan the
+        matcher cannot serve (no valid reading) raises after the scans before it are done; it keeps its prior and the
+        track goes on from it."""
+        scans = list(scans)
+        if scans and self.last is None:
+            self.start(scans.pop(0))
+        if not scans:
+            return []
+        res, done = self.matcher.track_in_map(self.cmap, self.ox, self.oy, [self.last] + scans, 1, True, True, self.coarse,
+                                              self.min_response)
+        got = res[1:done]
+        for r in got:
+            self.lost = 0 if r.meta["accepted"] else self.lost + 1
+        self.results.extend(got)
+        self.last = ([self.last] + scans)[min(done, len(scans))]
+        if done <= len(scans):
+            raise ValueError("MapLocalizer: scan %d of the call could not be matched (no valid reading or an empty lattice); "
+                             "it keeps its odometry prior" % (done - 1))
+        return got

@@ -405,20 +405,129 @@ class ScanMatcher(object):
         r.meta["corrected_centre"] = (r.best_pose.x, r.best_pose.y, r.best_pose.euler[-1])
         return ScanMatcherResult(r.response, r.covariance, [q.corrected_pose + diff for q in query_scans], r.meta)
 
+    # ---- localization mode: many sets against one map, scan streams followed through it --------
+    @staticmethod
+    def _map_search(coarse):
+        if not coarse:
+            return None
+        return _capi.YmMapSearch(float(coarse.get("xy_search", 0.25)), float(coarse.get("xy_step", 0.01)),
+                                 float(coarse.get("angle_search", 0.1)), float(coarse.get("angle_step", 0.01)),
+                                 float(coarse.get("grid_resolution", 0.05)), int(bool(coarse.get("penalize", False))), 0)
+
+    def match_map_batch(self, cmap, ox, oy, query_sets, penalty=True, do_fine=True, coarse=None, strict=True):
+        """N independent `match_scan_sets_with_map` calls on one resident map in ONE enqueue (`ym_match_map_many`): item i
+        matches the scans of `query_sets[i]` (1 to 64 scans; sets may differ) as one point set.  Returns a list of
+        ScanMatcherResult, each built exactly as `match_scan_sets_with_map` builds its own for that set alone -- the same
+        bits, the same meta keys ("centre", "corrected_centre", ...), best_pose = the wrapper's pose list -- plus
+        meta["rigid_poses"]: the set moved rigidly about its centre (what `locate_in_map` returns).  An item the matcher cannot
+        serve (no query point, empty lattice) raises as the single call does, or with strict=False is None in the list; its
+        neighbours are unaffected.  Empty input or an empty set: ValueError before the library is touched."""
+        sets = [list(s) for s in query_sets]
+        if not sets:
+            raise ValueError("match_map_batch: no query set")
+        for i, s in enumerate(sets):
+            if not s:
+                raise ValueError("match_map_batch: query set %d is empty" % i)
+        if not isinstance(cmap, CorrelationMap):
+            raise TypeError("match_map_batch needs a resident CorrelationMap (correlation_grid_from_occupancy / upload_correlation_grid)")
+        flat, offs = [], [0]
+        for s in sets:
+            flat.extend(s)
+            offs.append(len(flat))
+        hs = (C.c_void_p * len(flat))(*[self._require_native(q) for q in flat])
+        co = (C.c_int32 * len(offs))(*offs)
+        cs = self._map_search(coarse)
+        per = (_capi.YmResult * len(sets))()
+        _capi.check(self._lib.ym_match_map_many(self._m, cmap._h, float(ox), float(oy), hs, co, len(sets), int(bool(penalty)),
+                                                int(bool(do_fine)), C.byref(cs) if cs else None, per))
+        out = []
+        for i, (s, res) in enumerate(zip(sets, per)):
+            if res.status != 0:
+                if strict:
+                    raise _capi.YmError(res.status, "empty search lattice or no query point (item %d)" % i)
+                out.append(None)
+                continue
+            out.append(_map_set_result(res, s))
+        return out
+
+    def track_in_map(self, cmap, ox, oy, tracks, start=1, penalty=True, do_fine=True, coarse=None, min_response=0.0):
+        """Follow scan streams through a resident map without growing a graph (`ym_map_track`).  `tracks`: a list of scans
+        (one stream) or a list of such lists (streams in lock-step: step i of every track that still has a scan i is one
+        enqueue).  Every scan carries `odom_pose`; the scans before `start` (>= 1) of a track carry their `corrected_pose`.
+        Per scan: prior = previous corrected pose + odometry increment (graph_slam.py:320-324), the one-scan set is matched
+        against the map, and `corrected_pose` becomes the set's rigid correction -- or stays the prior when the response is
+        below `min_response` (meta["accepted"] False) or when the matcher cannot serve the scan, which ends its track.
+        Returns per track (results, n_done): results[i] is None for the scans before `start` and from n_done on; a single
+        stream given as a plain list returns its one pair."""
+        tracks = list(tracks)
+        single = bool(tracks) and not isinstance(tracks[0], (list, tuple))
+        if single:
+            tracks = [tracks]
+        tracks = [list(t) for t in tracks]
+        if not tracks:
+            raise ValueError("track_in_map: no track")
+        for r, t in enumerate(tracks):
+            if not t:
+                raise ValueError("track_in_map: track %d is empty" % r)
+        if int(start) < 1:
+            raise ValueError("track_in_map: start must be at least 1 (scan 0 of a track carries its pose)")
+        if not isinstance(cmap, CorrelationMap):
+            raise TypeError("track_in_map needs a resident CorrelationMap")
+        flat, offs = [], [0]
+        for t in tracks:
+            flat.extend(t)
+            offs.append(len(flat))
+        n = len(flat)
+        hs = (C.c_void_p * n)(*[self._require_native(s) for s in flat])
+        odom = np.empty((n, 3), dtype=np.float64)
+        for i, s in enumerate(flat):
+            p = s.odom_pose
+            odom[i, 0], odom[i, 1], odom[i, 2] = p.x, p.y, p.euler[-1]
+        co = (C.c_int32 * len(offs))(*offs)
+        cs = self._map_search(coarse)
+        per = (_capi.YmResult * n)()
+        done = (C.c_int32 * len(tracks))()
+        rc = self._lib.ym_map_track(self._m, cmap._h, float(ox), float(oy), hs, odom.ctypes.data_as(C.POINTER(C.c_double)), co,
+                                    len(tracks), int(start), int(bool(penalty)), int(bool(do_fine)), C.byref(cs) if cs else None,
+                                    float(min_response), per, done)
+        # (the device twins hold what the call left, whatever its outcome: the Python side follows them)
+        pose = (C.c_double * 3)()
+        out = []
+        for r, t in enumerate(tracks):
+            nd = int(done[r]) if rc == 0 else len(t)
+            res = [None] * len(t)
+            for i in range(int(start), len(t)):
+                if i > nd:
+                    break
+                _capi.check(self._lib.ym_scan_get_pose(hs[offs[r] + i], pose))
+                t[i]._corrected_pose = Transform(pose[0], pose[1], 0.0, pose[2])
+                if i < nd and rc == 0:
+                    one = per[offs[r] + i]
+                    m_ = _result(one)
+                    m_.meta["accepted"] = one.reserved == 0
+                    res[i] = m_
+            out.append((res, nd))
+        if rc:
+            _capi.check(rc)
+        return out[0] if single else out
+
     # ---- locate a scan set anywhere in a map (ym_locator_*, DESIGN.md section 11) -------------------------------------
     def map_locator(self, cmap, levels=None, max_nodes=None):
         """A MapLocator over the resident CorrelationMap `cmap`: its max pyramid and search buffers on the device.
         levels: pyramid levels above the map (None: by the map's size); max_nodes: frontier entries per buffer (None: 2^25)."""
         return MapLocator(self, cmap, levels, max_nodes)
 
-    def locate_in_map(self, cmap, ox, oy, query_scans, refine=True, **kw):
+    def locate_in_map(self, cmap, ox, oy, query_scans, refine=True, polish_top=1, **kw):
         """One shot: where in the map `cmap` (cell (0, 0) at world (ox, oy)) were `query_scans` taken, as one rigid set?
         The exact best hypothesis over all cells and headings (`MapLocator.locate`, keywords passed on), then, with `refine`,
         polished: copies of the scans are moved to the located poses and matched with `match_scan_sets_with_map` (coarse
         window +-2 cells and +- one heading step, then its fine pass).  Returns a ScanMatcherResult whose best_pose holds one
         pose per query scan and whose meta["candidates"] is the located list.  The polish's correction is applied as a rigid
         motion about the set's centre (the wrapper's own list, which composes the correction in each scan's frame as the
-        reference does, is meta["wrapper_poses"]).  Raises ValueError when no hypothesis reaches min_response."""
+        reference does, is meta["wrapper_poses"]).  Raises ValueError when no hypothesis reaches min_response.
+        polish_top = K > 1: the first K located candidates are polished in one `match_map_batch`; the best polished response
+        wins, a tie going to the earlier candidate, and all K polished results are meta["polished"] (best_pose of each: its
+        rigid pose list)."""
         with self.map_locator(cmap) as loc:
             cands = loc.locate(query_scans, ox, oy, **kw)
             stats, step = loc.last_stats, loc.last_heading_step
@@ -428,12 +537,25 @@ class ScanMatcher(object):
         meta = {"candidates": cands, "stats": stats}
         if not refine:
             return ScanMatcherResult(best.response, None, list(best.poses), meta)
+        res = float(self.config.resolution)
+        if int(polish_top) > 1:
+            sets = []
+            for cand in cands[:int(polish_top)]:
+                moved = []
+                for q, p in zip(query_scans, cand.poses):
+                    c = q.copy()
+                    c.corrected_pose = p
+                    moved.append(c)
+                sets.append(moved)
+            rs = self.match_map_batch(cmap, ox, oy, sets, True, True,
+                                      coarse=dict(xy_search=2 * res, xy_step=res / 4, angle_search=step, angle_step=step / 20,
+                                                  grid_resolution=res))
+            return _pick_polished(rs, meta)
         moved = []
         for q, p in zip(query_scans, best.poses):
             c = q.copy()
             c.corrected_pose = p
             moved.append(c)
-        res = float(self.config.resolution)
         r = self.match_scan_sets_with_map(cmap, ox, oy, moved, True, True,
                                           coarse=dict(xy_search=2 * res, xy_step=res / 4, angle_search=step, angle_step=step / 20,
                                                       grid_resolution=res))
@@ -476,6 +598,13 @@ class ScanMatcher(object):
         _capi.check(self._lib.ym_debug_sums(self._m, item, pass_, buf.ctypes.data_as(C.POINTER(C.c_uint32)), buf.size))
         return buf
 
+    def debug_map_sums(self, pass_=0, item=0, dims=None):
+        """the [nt][ny][nx] integer sums of item `item` of the last map call (match_map_batch; match_scan_sets_with_map: item 0)"""
+        nx, ny, nt = dims
+        buf = np.zeros((nt, ny, nx), dtype=np.uint32)
+        _capi.check(self._lib.ym_debug_map_sums(self._m, int(item), int(pass_), buf.ctypes.data_as(C.POINTER(C.c_uint32)), buf.size))
+        return buf
+
     def debug_query_local(self, item=0, cap=8192):
         buf = np.zeros((cap, 2))
         n = C.c_int32()
@@ -510,7 +639,7 @@ class ScanMatcher(object):
         buf = (C.c_int64 * 8)()
         _capi.check(self._lib.ym_debug_counters(self._m, buf, 8))
         return dict(yag_fast_items=int(buf[0]), yag_fallback_items=int(buf[1]), yag_pairs_checked=int(buf[2]),
-                    yag_pairs_failed=int(buf[3]), list_cache_hits=int(buf[4]),
+                    yag_pairs_failed=int(buf[3]), list_cache_hits=int(buf[4]), map_kernel_items=int(buf[6]), map_fallback_items=int(buf[7]),
                     last_correlate={-1: None, 0: "correlate_kernel", 1: "correlate_region_kernel", 2: "gather_kernel"}[int(buf[5])])
 
     def profile(self, on=True):
@@ -546,6 +675,37 @@ class CorrelationMap(object):
             self.close()
         except Exception:
             pass
+
+
+def _map_set_result(res, query_scans):
+    """the ScanMatcherResult `match_scan_sets_with_map` builds from the library's ym_result of one set, and meta["rigid_poses"]"""
+    r = _result(res)
+    # scan_matching.py:136-139,167-173: the search centre is the mean query position with heading 0; every query is moved by
+    # (corrected centre - centre)
+    xs = [float(q.corrected_pose.x) for q in query_scans]
+    ys = [float(q.corrected_pose.y) for q in query_scans]
+    oxy = Transform.from_position_euler(sum(xs) / float(len(xs)), sum(ys) / float(len(ys)), 0, 0, 0, 0)
+    diff = r.best_pose - oxy
+    r.meta["centre"] = (oxy.x, oxy.y, 0.0)
+    r.meta["corrected_centre"] = (r.best_pose.x, r.best_pose.y, r.best_pose.euler[-1])
+    c0, c1 = r.meta["centre"], r.meta["corrected_centre"]
+    r.meta["rigid_poses"] = _move_rigidly([q.corrected_pose for q in query_scans], c0[0], c0[1], c1[0], c1[1], c1[2] - c0[2])
+    return ScanMatcherResult(r.response, r.covariance, [q.corrected_pose + diff for q in query_scans], r.meta)
+
+
+def _pick_polished(polished, meta):
+    """`locate_in_map(polish_top=K)`: the best of the K polished candidates (the first of equals), as the result locate_in_map returns"""
+    best = 0
+    for i, r in enumerate(polished):
+        if r.response > polished[best].response:
+            best = i
+    r = polished[best]
+    meta = dict(meta)
+    meta.update(r.meta)
+    meta["wrapper_poses"] = r.best_pose
+    meta["polished"] = [ScanMatcherResult(p.response, p.covariance, p.meta["rigid_poses"], p.meta) for p in polished]
+    meta["polished_index"] = best
+    return ScanMatcherResult(r.response, r.covariance, r.meta["rigid_poses"], meta)
 
 
 LocateCandidate = namedtuple("LocateCandidate", ["score", "response", "index", "k", "cx", "cy", "pose", "poses"])
