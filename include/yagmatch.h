@@ -345,6 +345,49 @@ ym_occupancy *ym_occupancy_create_clean(const ym_scan *const *scans, int n_scans
                                         const ym_despeckle_opts *opts /* null: the node's 0 / 255 / 5 / 8 */);
 int ym_occupancy_get_despeckle_stats(const ym_occupancy *og, ym_despeckle_stats *stats); /* fails on a handle of the other creators */
 
+/* ---- the live occupancy grid: the counts of that rendering kept on the device and changed by exactly the rays that changed
+ * (DESIGN.md section 14).  A publish then costs the new scans' rays plus threshold, filter and copy of the image, not the log.
+ * The lattice: an ANCHOR fixed once (given at creation, or the bounding-box minimum of the first add) and never moved; a world
+ * coordinate's cell is Round((p - anchor) / resolution).  The WINDOW is what is reported: per axis origin = Round((min - anchor) /
+ * resolution) and size = Round((max - min) / resolution) of the running bounding box of everything ever added; cell (0, 0) of
+ * every read is lattice cell (origin_x, origin_y), at world offset = anchor + origin * resolution.  With the anchor at the offset
+ * of ym_occupancy_create's grid of the same scans, width, height, offset, counts and image are that grid's, bit for bit, in
+ * whatever order and batches the scans were added.  The memory holds every cell a ray of an added scan can touch, also outside
+ * today's window (rays clipped at the range threshold leave it), plus slack_cells on every side whenever it has to grow.
+ *   ym_occmap_accumulate   adds (sign +1) or subtracts (sign -1) the rays of n scans traced at poses[n][3] (x, y, heading), or at
+ *                          the scans' own poses when poses is null.  The library keeps no membership: a caller subtracts what it
+ *                          added, at the pose it added it at.  Subtraction never shrinks window or memory.
+ *   ym_occmap_clear        zero counts, no bounding box; the anchor and the memory stay.
+ *   ym_occmap_read         the window's image [height][width] (codes as above), through the component filter when clean is not
+ *                          null (stats, nullable, then receives its figures).  bytes must be width * height.
+ *   ym_occmap_read_counts  the window's pass and hit counts, cells = width * height each.
+ *   ym_occmap_debug_option development: option 1 = the form of the trace kernel, 0 a wave per ray (default), 1 a thread per ray.
+ * Refused with YM_ERR_INVALID: null or foreign-device scans, n <= 0, a sign other than +-1, a subtraction or a read before any
+ * add (or after a clear), sizes that are not the window's.  YM_ERR_UNSUPPORTED: a window without width or height on a read (adds
+ * to it are fine), more than 2 * 10^9 cells, more than 2^31 - 1 where the filter runs, range_threshold / resolution >= 2^24,
+ * coordinates more than 2^30 cells from the anchor.  Every entry is synchronous. */
+typedef struct ym_occmap ym_occmap;
+typedef struct ym_occmap_info {
+    int32_t width, height;                  /* the window */
+    double offset_x, offset_y, resolution;  /* offset = anchor + origin * resolution */
+    double anchor_x, anchor_y;
+    int32_t origin_x, origin_y;             /* the window's first cell in the anchor's lattice */
+    int32_t alloc_width, alloc_height;      /* cells that have memory ... */
+    int32_t alloc_origin_x, alloc_origin_y; /* ... from this lattice cell on */
+    int64_t reallocations;                  /* times the counts moved into a larger buffer (the first allocation is not one) */
+    int32_t has_anchor, added;              /* the anchor is decided; something was added since creation or the last clear */
+} ym_occmap_info;
+ym_occmap *ym_occmap_create(int device, double resolution, double range_threshold,
+                            const double *anchor_xy /* null: the first add decides */, int slack_cells);
+int ym_occmap_accumulate(ym_occmap *om, const ym_scan *const *scans, const double *poses /* [n][3] or null */, int n, int sign);
+int ym_occmap_clear(ym_occmap *om);
+int ym_occmap_get_info(const ym_occmap *om, ym_occmap_info *info);
+int ym_occmap_read(ym_occmap *om, uint8_t *image, int64_t bytes, const ym_despeckle_opts *clean /* or null */,
+                   ym_despeckle_stats *stats /* or null */);
+int ym_occmap_read_counts(ym_occmap *om, uint32_t *pass, uint32_t *hits, int64_t cells);
+int ym_occmap_debug_option(ym_occmap *om, int option, int value);
+void ym_occmap_destroy(ym_occmap *om);
+
 /* ---- virtual scans from an occupancy image: the ray casting of the ROS node's "start in a prior map" path
  * (ingest_base_map -> map_to_graphslam -> map_to_graph, /root/reference/ros1/slam_node_ros1:131-147,
  * /root/reference/yag_slam/splicing.py:82-107).  ym_raymap_trace is run_raytracing_sweep (raytracing.py:91-92) for

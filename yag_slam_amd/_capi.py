@@ -26,6 +26,8 @@ EXPORTS = (
     "ym_coarse_dims", "ym_match_slice_begin", "ym_match_slice_finish",
     "ym_occupancy_create", "ym_occupancy_create_counted", "ym_occupancy_get_info", "ym_occupancy_read", "ym_occupancy_read_counts",
     "ym_occupancy_destroy", "ym_image_despeckle", "ym_occupancy_create_clean", "ym_occupancy_get_despeckle_stats",
+    "ym_occmap_create", "ym_occmap_accumulate", "ym_occmap_clear", "ym_occmap_get_info", "ym_occmap_read", "ym_occmap_read_counts",
+    "ym_occmap_debug_option", "ym_occmap_destroy",
     "ym_map_from_occupancy", "ym_map_from_grid", "ym_map_size", "ym_map_read", "ym_map_destroy", "ym_match_map",
     "ym_match_map_many", "ym_map_track", "ym_debug_map_sums",
     "ym_raymap_create", "ym_raymap_trace", "ym_raymap_trace_each", "ym_raymap_destroy",
@@ -104,6 +106,13 @@ class YmDespeckleOpts(C.Structure):
 class YmDespeckleStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("foreground_cells", "components", "removed_components", "cleared_cells",
                                         "background_cells")] + [("background_filled", C.c_int32), ("reserved", C.c_int32)]
+
+
+class YmOccmapInfo(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("offset_x", C.c_double), ("offset_y", C.c_double),
+                ("resolution", C.c_double), ("anchor_x", C.c_double), ("anchor_y", C.c_double), ("origin_x", C.c_int32),
+                ("origin_y", C.c_int32), ("alloc_width", C.c_int32), ("alloc_height", C.c_int32), ("alloc_origin_x", C.c_int32),
+                ("alloc_origin_y", C.c_int32), ("reallocations", C.c_int64), ("has_anchor", C.c_int32), ("added", C.c_int32)]
 
 
 class YmMapSearch(C.Structure):
@@ -267,6 +276,16 @@ def lib():
     L.ym_occupancy_create_clean.restype = vp
     L.ym_occupancy_create_clean.argtypes = [C.POINTER(vp), C.c_int, C.c_double, C.c_double, C.POINTER(YmDespeckleOpts)]
     L.ym_occupancy_get_despeckle_stats.argtypes = [vp, C.POINTER(YmDespeckleStats)]
+    L.ym_occmap_create.restype = vp
+    L.ym_occmap_create.argtypes = [C.c_int, C.c_double, C.c_double, dp, C.c_int]
+    L.ym_occmap_accumulate.argtypes = [vp, C.POINTER(vp), dp, C.c_int, C.c_int]
+    L.ym_occmap_clear.argtypes = [vp]
+    L.ym_occmap_get_info.argtypes = [vp, C.POINTER(YmOccmapInfo)]
+    L.ym_occmap_read.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int64, C.POINTER(YmDespeckleOpts), C.POINTER(YmDespeckleStats)]
+    L.ym_occmap_read_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_int64]
+    L.ym_occmap_debug_option.argtypes = [vp, C.c_int, C.c_int]
+    L.ym_occmap_destroy.argtypes = [vp]
+    L.ym_occmap_destroy.restype = None
     L.ym_map_from_occupancy.restype = vp
     L.ym_map_from_occupancy.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int, C.c_int]
     L.ym_map_from_grid.restype = vp

@@ -22,11 +22,12 @@
 
 #include "../../include/yagmatch.h"
 #include "ym_kernels.hpp"
+#include "ym_occlive_window.hpp" // the live occupancy grid's window arithmetic (no HIP in it)
 
 // The host runtime in units (one translation unit: the kernels are templates and inline functions of ym_kernels.hpp):
 #include "ym_host_types.hpp"    // error text, device guard, buffers, Call / CallPlan / Slot
 #include "ym_host_pool.hpp"     // ym_scan, the per-device scan pool
-#include "ym_host_matcher.hpp"  // ym_map, ym_occupancy, ym_batch, ym_matcher
+#include "ym_host_matcher.hpp"  // ym_map, ym_occupancy, ym_occmap, ym_batch, ym_matcher
 
 namespace {
 #include "ym_host_setup.hpp"    // config -> geometry, tables, lattices, profiling events
@@ -41,6 +42,7 @@ extern "C" {
 #include "ym_abi_scans.hpp"
 #include "ym_abi_match.hpp"
 #include "ym_abi_maps.hpp"
+#include "ym_abi_occlive.hpp"
 #include "ym_abi_maptrack.hpp"
 #include "ym_abi_rays.hpp"
 #include "ym_abi_locate.hpp"

@@ -1,4 +1,4 @@
-// ym_host_matcher.hpp -- host runtime: ym_map, ym_occupancy, ym_batch, ym_matcher (workspace, caches, options)
+// ym_host_matcher.hpp -- host runtime: ym_map, ym_occupancy, ym_occmap, ym_batch, ym_matcher (workspace, caches, options)
 // Part of yagmatch.hip (included at file scope); not a header of its own.
 struct ym_map {
     int device;
@@ -14,6 +14,21 @@ struct ym_occupancy {
     std::vector<uint32_t> counts; // ym_occupancy_create_counted only: pass [height][width], then hits [height][width]
     bool cleaned = false;         // ym_occupancy_create_clean only: the image went through the component area filter,
     ym_despeckle_stats clean_stats{}; // ... and this is what it counted
+};
+
+// the live occupancy grid (ym_abi_occlive.hpp): counts resident on the device, in the lattice of an anchor that never moves
+struct ym_occmap {
+    int device = 0;
+    double resolution = 0, range_threshold = 0, scale = 0;
+    bool has_anchor = false, added = false; // added: a scan has been added since creation or the last clear
+    double anchor[2] = {0, 0};
+    double box[4] = {0, 0, 0, 0};           // the running bounding box of everything added (valid while `added`)
+    ymw::Rect window, reach, alloc;         // lattice cells (ym_occlive_window.hpp)
+    int slack = 0;
+    int64_t reallocations = 0;
+    int trace_form = 0;                     // development: 1 = occ_live_trace_thread_kernel
+    DevBuf<unsigned> cnt;                   // pass [alloc.h][alloc.w], then hits [alloc.h][alloc.w]
+    DevBuf<uint8_t> img;                    // the window's image between its kernel and its copy to the host
 };
 
 struct ym_batch {

@@ -33,6 +33,7 @@
 #include "ym_k_yagpy.hpp"
 #include "ym_k_yagmap.hpp"
 #include "ym_k_occupancy.hpp"
+#include "ym_k_occlive.hpp"
 #include "ym_k_raytrace.hpp"
 #include "ym_k_locate.hpp"
 #include "ym_k_segments.hpp"

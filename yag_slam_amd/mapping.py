@@ -264,6 +264,20 @@ class LoopClosingMapper(SequentialMapper):
         from .occupancy import ros_map
         return ros_map(self.scans, resolution, range_threshold, device=getattr(self.seq_matcher, "device", 0))
 
+    def live_ros_map(self, resolution=0.05, range_threshold=12, **filter_opts):
+        """make_ros_map from counts that stay on the device (occupancy.LiveOccupancyGrid): only the
+        scans added or moved since the last call are traced.  The grid is made on first use, and anew when the resolution or
+        the threshold changes; its lattice is anchored at the first call's bounding-box minimum, so its origin is not the one
+        make_ros_map would give (a fraction of a cell apart)."""
+        from .occupancy import LiveOccupancyGrid
+        live = getattr(self, "live_grid", None)
+        if live is None or (live.resolution, live.range_threshold) != (float(resolution), float(range_threshold)):
+            if live is not None:
+                live.close()
+            live = self.live_grid = LiveOccupancyGrid(resolution, range_threshold, device=getattr(self.seq_matcher, "device", 0))
+        live.sync(self.scans)
+        return live.ros_map(**filter_opts)
+
     def run_opt(self):
         """graph_slam.py:262-272; a no-op without an optimizer except for the spatial index refresh"""
         if self.opt is not None:
