@@ -606,6 +606,30 @@ int ym_debug_query_local(ym_matcher *m, int item, double *out_xy, int32_t cap, i
 /* window cell coordinates of the rasterised base points of `item`, per base scan slot:
  * out[(slot*max_n + i)*2 + {0,1}] = wx, wy  or (INT32_MIN, INT32_MIN) for filtered points */
 int ym_debug_cells(ym_matcher *m, int item, int32_t *out, int64_t out_count, int32_t *max_n);
+/* the region correlate's pair lists of query slot `slot` of the last call, as bin_kernel left them ("The pair-list
+ * contract"), with the geometry they were built for and what the builder read of the slot's representative item `qrep`.
+ * YM_ERR_INVALID: the last call built no such lists (its correlate was not correlate_region_kernel), or no such slot;
+ * YM_ERR_UNSUPPORTED: the lists have the one-part layout of the experimental forms.  Lists reused from an earlier call (option 45)
+ * are read like freshly built ones.  With all five arrays NULL only *info is filled (the sizes to allocate); otherwise all five
+ * are written, and nothing is written when the call fails:
+ *   ctrig   [nt][2]                 cos, sin of qrep's coarse angles
+ *   starts  [lparts][nbins + 1]     first entry of bin region * lnw + (angle - part * lnw), positions in `entries`
+ *   flags   [lparts]                padded total of the part, or -1: the part has no list (its entries are unspecified)
+ *   entries [lparts][entries_pstride]
+ *   rbox    [nregions][lparts]      rmin | rmax << 8 | xmin << 16 | xmax << 24 of the patch origins inside the region */
+typedef struct ym_pair_list_info {
+    int32_t nt, lnw, lparts, nbins;  /* coarse angles; angles per list part, parts; bins per part = nregions * lnw */
+    int32_t nrx, nry, nregions;      /* regions along x and y of class space */
+    int32_t rg_h, rg_cls, rg_zero;   /* class rows per region, LDS bytes per class image, LDS offset of the all-zero patch */
+    int32_t ng;                      /* sets of 16-bit sums per (item, angle) */
+    int32_t qrep, cx0, cy0, nq;      /* the item that stands for the slot; its first hypothesis cell; its valid readings */
+    int32_t n_slots;                 /* query slots of the call */
+    int64_t entries_pstride;         /* entries a part has room for */
+    double off_x, off_y;             /* qrep's grid offset */
+    double ylat[2];                  /* qrep's lattice origin ("yagpy" semantics: the addends of the lookup cells) */
+} ym_pair_list_info;
+int ym_debug_pair_lists(ym_matcher *m, int slot, ym_pair_list_info *info, double *ctrig, int32_t *starts, int32_t *flags,
+                        uint16_t *entries, uint32_t *rbox);
 
 /* Switches of the parity tests: every row names a path the tests force so that each kernel and each host decision is compared with
  * the oracle (or with the default path) bit for bit.  None changes a result.  Development and timing switches that no test uses

@@ -30,6 +30,7 @@ def test_struct_layouts_match_the_header():
     assert C.sizeof(_capi.YmScanDesc) == 8 + 8 + 6 * 8 + 3 * 8
     assert C.sizeof(_capi.YmResult) == 8 + 24 + 72 + 8 + 8 + 12 + 12 + 4 * 4
     assert C.sizeof(_capi.YmGridInfo) == 12 * 4 + 16
+    assert C.sizeof(_capi.YmPairListInfo) == 16 * 4 + 8 + 4 * 8
 
 
 def test_no_device_fails_loudly():

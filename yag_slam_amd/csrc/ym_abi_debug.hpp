@@ -70,6 +70,52 @@ int ym_debug_cells(ym_matcher *m, int item, int32_t *out, int64_t out_count, int
     return YM_OK;
 }
 
+// the pair lists bin_kernel built (or a call with the same key left in the buffers: option 45) for one query slot of the last call
+int ym_debug_pair_lists(ym_matcher *m, int slot, ym_pair_list_info *info, double *ctrig, int32_t *starts, int32_t *flags, uint16_t *entries,
+                        uint32_t *rbox) {
+    if (!m || !info) return set_err(YM_ERR_INVALID, "null argument");
+    const ym_matcher::ListsLast &ll = m->lists_last;
+    if (!m->last_valid || !ll.valid) return set_err(YM_ERR_INVALID, "the last call built no region pair lists");
+    if (ll.whole) return set_err(YM_ERR_UNSUPPORTED, "the one-part lists of the experimental forms are not read back");
+    if (slot < 0 || slot >= (int)ll.qrep.size()) return set_err(YM_ERR_INVALID, "no such query slot in the last call");
+    const int n_out = (ctrig != nullptr) + (starts != nullptr) + (flags != nullptr) + (entries != nullptr) + (rbox != nullptr);
+    if (n_out != 0 && n_out != 5) return set_err(YM_ERR_INVALID, "all five arrays or none");
+    const int b = ll.qrep[slot];
+    if (b < 0 || b >= m->last_B) return set_err(YM_ERR_HIP, "query slot %d names item %d (a fault of the library)", slot, b);
+    ym_pair_list_info o;
+    std::memset(&o, 0, sizeof o);
+    o.nt = ll.nt; o.lnw = ll.lnw; o.lparts = ll.lparts; o.nbins = ll.nbins; o.nrx = ll.nrx; o.nry = ll.nry; o.nregions = ll.nregions;
+    o.rg_h = ll.rg_h; o.rg_cls = ll.rg_cls; o.rg_zero = ll.rg_zero; o.ng = ll.ng; o.qrep = b; o.n_slots = (int32_t)ll.qrep.size();
+    o.entries_pstride = (int64_t)ll.entries_pstride;
+    YmItemState s;
+    int32_t c0[2];
+    DEV_GUARD(m->device);
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    HIP_TRY(hipMemcpy(&s, m->states.p + b, sizeof s, hipMemcpyDeviceToHost));
+    const int32_t *hc = m->hypcell.p + (size_t)b * 2 * m->last_dim_stride;
+    HIP_TRY(hipMemcpy(&c0[0], hc, sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&c0[1], hc + m->last_dim_stride, sizeof(int32_t), hipMemcpyDeviceToHost));
+    o.cx0 = c0[0]; o.cy0 = c0[1]; o.nq = s.nq; o.off_x = s.off_x; o.off_y = s.off_y; o.ylat[0] = s.ylat[0]; o.ylat[1] = s.ylat[1];
+    if (n_out == 0) { *info = o; return YM_OK; }
+    // (into buffers of the library's own first: a copy that fails leaves the caller's arrays as they were)
+    const size_t n_starts = (size_t)ll.lparts * (ll.nbins + 1), n_entries = (size_t)ll.lparts * ll.entries_pstride, n_rbox = (size_t)ll.nregions * ll.lparts;
+    std::vector<double> h_trig((size_t)2 * ll.nt);
+    std::vector<int32_t> h_starts(n_starts + ll.lparts);
+    std::vector<uint16_t> h_entries(n_entries);
+    std::vector<uint32_t> h_rbox(n_rbox);
+    HIP_TRY(hipMemcpy(h_trig.data(), m->ctrig.p + (size_t)b * m->last_nt_stride, sizeof(double) * 2 * ll.nt, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_starts.data(), m->rg_starts.p + (size_t)slot * ll.starts_stride, sizeof(int32_t) * h_starts.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_entries.data(), m->rg_entries.p + (size_t)slot * ll.entries_stride, sizeof(uint16_t) * n_entries, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_rbox.data(), m->rg_rbox.p + (size_t)slot * ll.rbox_stride, sizeof(uint32_t) * n_rbox, hipMemcpyDeviceToHost));
+    *info = o;
+    std::memcpy(ctrig, h_trig.data(), sizeof(double) * h_trig.size());
+    std::memcpy(starts, h_starts.data(), sizeof(int32_t) * n_starts);
+    std::memcpy(flags, h_starts.data() + n_starts, sizeof(int32_t) * ll.lparts);
+    std::memcpy(entries, h_entries.data(), sizeof(uint16_t) * n_entries);
+    std::memcpy(rbox, h_rbox.data(), sizeof(uint32_t) * n_rbox);
+    return YM_OK;
+}
+
 // The options the parity tests use are tabulated in include/yagmatch.h.  The others -- development and timing switches:
 //    2  rasterise every tile of the window                      3  beams in flight per lane in the direct correlate (16 / 32 / 48)
 //    4  extra dynamic LDS bytes per direct-correlate block        5  beam chunks per angle of the direct correlate

@@ -10,6 +10,7 @@ int launch_call_body(ym_matcher *m, Slot &slot) {
     int rc;
     mark(0);
     m->last_corr_form = -1;
+    m->lists_last.valid = false;
     if ((rc = plan_sizes(m, slot, P))) return rc;
     mark(1);
     // a resident batch again, no scan moved, no cache slot changed hands, nothing was left to fill: last time's plan holds
@@ -105,6 +106,16 @@ int launch_call_body(ym_matcher *m, Slot &slot) {
     m->last_sums_stride[0] = P.yag ? P.yvol : (m->keep_sums || (P.B < 8 && P.sums_c <= 65536)) ? P.sums_c : 0;
     m->last_sums_stride[1] = slot.call.refine ? (P.yag ? P.yvol : P.sums_f) : 0;
     m->last_valid = true;
+    if (P.region26 && P.k_end > P.k_begin) { // (ym_debug_pair_lists: the lists' geometry, a handful of integers per enqueue)
+        const ym::RegionArgs r = region_args(m, P);
+        ym_matcher::ListsLast &ll = m->lists_last;
+        ll.whole = P.rg_ws || P.rg2 || P.rg_item || P.rg_pool;
+        ll.nt = P.lc.nt; ll.lnw = r.lnw; ll.lparts = r.lparts; ll.nbins = r.nbins; ll.nrx = r.nrx; ll.nry = r.nry; ll.nregions = r.nregions;
+        ll.rg_h = r.rg_h; ll.rg_cls = r.rg_cls; ll.rg_zero = r.rg_zero; ll.ng = r.ng;
+        ll.entries_pstride = r.entries_pstride; ll.entries_stride = r.entries_stride; ll.starts_stride = r.starts_stride; ll.rbox_stride = r.rbox_stride;
+        ll.qrep.swap(P.qrep); // (the plan ends here: no copy)
+        ll.valid = true;
+    }
     return YM_OK;
 }
 

@@ -217,6 +217,14 @@ struct ym_matcher {
     size_t last_grid_stride = 0, last_sums_stride[2] = {0, 0};
     size_t sums_pass_offset[2] = {0, 0};
     bool last_valid = false;
+    // what ym_debug_pair_lists needs of the last call whose correlate was correlate_region_kernel: the geometry its pair lists were built
+    // for (the plan does not outlive the enqueue) and the item that stands for each query slot
+    struct ListsLast {
+        bool valid = false, whole = false; // whole: the one-part layout of the experimental forms
+        int32_t nt = 0, lnw = 0, lparts = 0, nbins = 0, nrx = 0, nry = 0, nregions = 0, rg_h = 0, rg_cls = 0, rg_zero = 0, ng = 0;
+        size_t entries_pstride = 0, entries_stride = 0, starts_stride = 0, rbox_stride = 0;
+        std::vector<int32_t> qrep;
+    } lists_last;
     // profiling
     bool profiling = false;
     ProfEvents prof[3];

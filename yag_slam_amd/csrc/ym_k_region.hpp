@@ -187,6 +187,7 @@ __device__ __forceinline__ bool region_entry(const RegionArgs &a, int2 cell, int
 // never meets a ragged group.  A part whose padded list would not fit -- its share of the buffer, one angle's share of the ng sets of
 // 16-bit sums the gather may fill, or more regions with work than a correlate block can list -- gets its flag = -1 and the
 // correlate block of those angles takes the per-cell path.
+// (The contract, clause by clause: DESIGN.md section 4, "The pair-list contract"; ym_debug_pair_lists reads the lists back for the tests.)
 // YAG: the lookup cells of the reference's Python matcher (items yag_lattice_kernel proved regular; ym_k_common.hpp, lookup_cell_sem).
 // MAXP: pairs per thread the instantiation has registers for (18: scans of up to 1152 readings at eight angles per part; 32: up to 2047).
 #define YM_BINP_THREADS 512

@@ -620,6 +620,27 @@ class ScanMatcher(object):
                                              C.byref(max_n)))
         return buf.reshape(-1, 2), max_n.value
 
+    def debug_pair_lists(self, slot=0):
+        """The region correlate's pair lists of query slot `slot` of the last call (include/yagmatch.h, ym_debug_pair_lists): a dict
+        of the geometry they were built for (ints), `ctrig` [nt][2], `starts` [lparts][nbins + 1], `flags` [lparts], `entries`
+        [lparts][entries_pstride] and `rbox` [nregions][lparts][4] = rmin, rmax, xmin, xmax."""
+        info = _capi.YmPairListInfo()
+        none = (None,) * 5
+        _capi.check(self._lib.ym_debug_pair_lists(self._m, int(slot), C.byref(info), *none))
+        ctrig = np.zeros((info.nt, 2))
+        starts = np.zeros((info.lparts, info.nbins + 1), dtype=np.int32)
+        flags = np.zeros(info.lparts, dtype=np.int32)
+        entries = np.zeros((info.lparts, info.entries_pstride), dtype=np.uint16)
+        rbox = np.zeros((info.nregions, info.lparts), dtype=np.uint32)
+        _capi.check(self._lib.ym_debug_pair_lists(self._m, int(slot), C.byref(info), ctrig.ctypes.data_as(C.POINTER(C.c_double)),
+                                                  starts.ctypes.data_as(C.POINTER(C.c_int32)), flags.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  entries.ctypes.data_as(C.POINTER(C.c_uint16)), rbox.ctypes.data_as(C.POINTER(C.c_uint32))))
+        out = {n: int(getattr(info, n)) for n, _ in _capi.YmPairListInfo._fields_[:17]}
+        out.update(slot=int(slot), off_x=info.off_x, off_y=info.off_y, ylat=(info.ylat[0], info.ylat[1]), ctrig=ctrig, starts=starts,
+                   flags=flags, entries=entries,
+                   rbox=np.stack([rbox & 255, (rbox >> 8) & 255, (rbox >> 16) & 255, rbox >> 24], axis=-1).astype(np.int32))
+        return out
+
     def debug_option(self, option, value):
         _capi.check(self._lib.ym_debug_option(self._m, int(option), int(value)))
 
