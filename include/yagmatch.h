@@ -249,6 +249,36 @@ ym_map *ym_map_from_grid(ym_matcher *m, const double *cgrid, int width, int heig
 int ym_map_size(const ym_map *map, int *width, int *height);
 int ym_map_read(const ym_map *map, double *out, int64_t out_count); /* the float grid, width*height entries */
 void ym_map_destroy(ym_map *map);
+/* ---- maps that take scans: the reference's add_scan_to_grid (yag_slam/helpers.py:105-131) into a map
+ * that stays on the device, so that a map can start empty or a prior map can be kept current while scans are tracked in it.
+ *   ym_map_create_empty  a map of zeros; the size limits and the YM_SEM_YAGPY-only rule of the two creators above.
+ *   ym_map_add_scans     every point reading of every scan at the scan's current pose (LocalizedRangeScan.points(): the readings
+ *                        that are neither NaN nor above the scan's range threshold; no view-point filter, as
+ *                        occupancy_grid_map_to_correlation_grid has none) goes to the cell gx = rint((x - ox) / res),
+ *                        gy = rint((y - oy) / res) -- world_to_grid, helpers.py:82-83: fp64 division, round half to even; res is the
+ *                        matcher's resolution, (ox, oy) the world position of cell (0, 0).  Inside the map the cell becomes 1.0 and every
+ *                        tap (sx, sy) of the matcher's float kernel raises cell (gy + sy - half, gx + sx - half) to max(current,
+ *                        kernel[sy][sx]) where that cell exists; a reading outside the map, or whose quotient is not finite, is
+ *                        dropped and counted.  Every write is a maximum, so the map does not depend on the order of points, of
+ *                        scans or of calls: it is bit for bit what the reference's sequential loop leaves, and what
+ *                        ym_map_from_occupancy makes of the image whose occupied pixels are the stamped cells.  The map must hold
+ *                        values in [0, 1] (what all three creators give).  Both forms of the map -- the float grid ym_map_read
+ *                        returns and the bytes every match reads -- are current when the call returns.  Runs on the matcher's
+ *                        stream, synchronous, never throws.  n_scans == 0 (scans may then be null) and scans without a valid
+ *                        reading change nothing.  stats (nullable): the readings seen, stamped and dropped, and a rectangle
+ *                        [x0, x1) x [y0, y1) that holds every changed cell (all 0 when nothing was stamped).
+ *                        A ym_locator copies the map when it is created: one made before an add does not see it.
+ *   ym_map_clear         every cell back to zero.
+ * YM_ERR_INVALID: a null argument, a negative n_scans, a null scan, a scan or a map on another device than the matcher.
+ * YM_ERR_UNSUPPORTED: a matcher that is not YM_SEM_YAGPY. */
+typedef struct ym_map_add_stats {
+    int64_t points, stamped, dropped; /* points = stamped + dropped */
+    int32_t x0, y0, x1, y1;           /* cells changed lie inside [x0, x1) x [y0, y1); empty: all 0 */
+} ym_map_add_stats;
+ym_map *ym_map_create_empty(ym_matcher *m, int width, int height);
+int ym_map_add_scans(ym_matcher *m, ym_map *map, double ox, double oy, const ym_scan *const *scans, int n_scans,
+                     ym_map_add_stats *stats /* or null */);
+int ym_map_clear(ym_matcher *m, ym_map *map);
 /* one find_best_pose_non_symmetric pass (/root/reference/yag_slam/helpers.py:434-573) */
 typedef struct ym_map_search {
     double xy_search, xy_step;       /* +- metres around the centre, lattice step */

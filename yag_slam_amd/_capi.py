@@ -30,6 +30,7 @@ EXPORTS = (
     "ym_occmap_debug_option", "ym_occmap_destroy",
     "ym_map_from_occupancy", "ym_map_from_grid", "ym_map_size", "ym_map_read", "ym_map_destroy", "ym_match_map",
     "ym_match_map_many", "ym_map_track", "ym_debug_map_sums",
+    "ym_map_create_empty", "ym_map_add_scans", "ym_map_clear",
     "ym_raymap_create", "ym_raymap_trace", "ym_raymap_trace_each", "ym_raymap_destroy",
     "ym_locator_create", "ym_locator_get_info", "ym_locator_read_level", "ym_locator_locate", "ym_locator_destroy",
     "ym_segments_create", "ym_segments_label_range", "ym_segments_stats", "ym_segments_boundaries", "ym_segments_pairs",
@@ -118,6 +119,10 @@ class YmOccmapInfo(C.Structure):
 class YmMapSearch(C.Structure):
     _fields_ = [("xy_search", C.c_double), ("xy_step", C.c_double), ("angle_search", C.c_double), ("angle_step", C.c_double),
                 ("grid_resolution", C.c_double), ("penalize", C.c_int32), ("reserved", C.c_int32)]
+
+
+class YmMapAddStats(C.Structure):
+    _fields_ = [("points", C.c_int64), ("stamped", C.c_int64), ("dropped", C.c_int64)] + [(n, C.c_int32) for n in ("x0", "y0", "x1", "y1")]
 
 
 class YmGridInfo(C.Structure):
@@ -308,6 +313,10 @@ def lib():
     L.ym_map_track.argtypes = [vp, vp, C.c_double, C.c_double, C.POINTER(vp), dp, ip, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.POINTER(YmMapSearch), C.c_double, C.POINTER(YmResult), ip]
     L.ym_debug_map_sums.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_int64]
+    L.ym_map_create_empty.restype = vp
+    L.ym_map_create_empty.argtypes = [vp, C.c_int, C.c_int]
+    L.ym_map_add_scans.argtypes = [vp, vp, C.c_double, C.c_double, C.POINTER(vp), C.c_int, C.POINTER(YmMapAddStats)]
+    L.ym_map_clear.argtypes = [vp, vp]
     L.ym_raymap_create.restype = vp
     L.ym_raymap_create.argtypes = [C.c_int, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_int]
     L.ym_raymap_trace.argtypes = [vp, dp, C.c_int, dp, C.c_int, C.POINTER(C.c_float), dp, C.POINTER(C.c_int64)]

@@ -81,6 +81,102 @@ void ym_map_destroy(ym_map *mp) {
     delete mp;
 }
 
+// ---- maps that take scans (ym_k_mapgrow.hpp)
+static int map_clear(ym_matcher *m, ym_map *mp) {
+    const size_t n = (size_t)mp->width * mp->height;
+    hipLaunchKernelGGL(ym::map_clear_kernel, dim3((unsigned)((n + 2047) / 2048)), dim3(256), 0, m->stream, mp->d_cgrid.p, mp->d_g8.p, n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    return YM_OK;
+}
+
+ym_map *ym_map_create_empty(ym_matcher *m, int width, int height) {
+    DevGuard guard(m ? m->device : 0);
+    ym_map *mp = map_alloc(m, width, height);
+    if (!mp) return nullptr;
+    if (map_clear(m, mp) != YM_OK) { delete mp; return nullptr; } // (the error text is set)
+    return mp;
+}
+
+int ym_map_clear(ym_matcher *m, ym_map *mp) {
+    if (!m || !mp) return set_err(YM_ERR_INVALID, "null argument");
+    if (m->cfg.semantics != YM_SEM_YAGPY) return set_err(YM_ERR_UNSUPPORTED, "ym_map_clear needs a YM_SEM_YAGPY matcher");
+    if (mp->device != m->device) return set_err(YM_ERR_INVALID, "map lives on another device");
+    DEV_GUARD(m->device);
+    return map_clear(m, mp);
+}
+
+// scans of one launch: the cells of every beam take 4 bytes, grid.y stays far below its limit
+static const int kMapGrowChunk = 4096;
+
+int ym_map_add_scans(ym_matcher *m, ym_map *mp, double ox, double oy, const ym_scan *const *scans, int n_scans, ym_map_add_stats *stats) {
+    if (!m || !mp || (!scans && n_scans != 0)) return set_err(YM_ERR_INVALID, "null argument");
+    if (m->cfg.semantics != YM_SEM_YAGPY) return set_err(YM_ERR_UNSUPPORTED, "ym_map_add_scans needs a YM_SEM_YAGPY matcher");
+    if (n_scans < 0) return set_err(YM_ERR_INVALID, "n_scans must not be negative");
+    if (mp->device != m->device) return set_err(YM_ERR_INVALID, "map lives on another device");
+    int max_n = 1;
+    for (int i = 0; i < n_scans; i++) {
+        if (!scans[i] || scans[i]->device != m->device) return set_err(YM_ERR_INVALID, "scan %d is null or lives on another device", i);
+        max_n = std::max(max_n, scans[i]->n);
+    }
+    ym_map_add_stats s;
+    std::memset(&s, 0, sizeof s);
+    if (n_scans == 0) {
+        if (stats) *stats = s;
+        return YM_OK;
+    }
+    const int ks = 2 * m->geom.half_kernel + 1, half = m->geom.half_kernel;
+    if ((double)max_n * ks * ks > 2.0e9) return set_err(YM_ERR_UNSUPPORTED, "%d beams x %d x %d taps: more than one launch holds", max_n, ks, ks);
+    DEV_GUARD(m->device);
+    hipStream_t st = m->stream;
+    const int chunk = std::min(n_scans, kMapGrowChunk);
+    int rc;
+    if ((rc = m->grow_scans.ensure((size_t)chunk)) || (rc = m->grow_cells.ensure((size_t)chunk * max_n)) ||
+        (rc = m->grow_stats.ensure(ym::kMgStatSlots)) || (rc = m->kernel_f_dev.ensure(m->kernel_f.size())))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(m->kernel_f_dev.p, m->kernel_f.data(), m->kernel_f.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    // (what the copies of this call read on the host -- `init`, `hs` -- stays as it is until the wait at the end)
+    const unsigned long long init[ym::kMgStatSlots] = {0, 0, 0, ~0ull, ~0ull, 0, 0};
+    unsigned long long got[ym::kMgStatSlots];
+    HIP_TRY(hipMemcpyAsync(m->grow_stats.p, init, sizeof init, hipMemcpyHostToDevice, st));
+    std::vector<YmScanRef> all((size_t)n_scans);
+    std::memset(all.data(), 0, sizeof(YmScanRef) * (size_t)n_scans);
+    ym::MapGrowArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.scans = m->grow_scans.p; a.max_n = max_n; a.width = mp->width; a.height = mp->height;
+    a.ox = ox; a.oy = oy; a.res = m->cfg.resolution;
+    a.cells = m->grow_cells.p; a.stats = m->grow_stats.p; a.kernel = m->kernel_f_dev.p; a.ksize = ks;
+    a.cgrid = mp->d_cgrid.p; a.g8 = mp->d_g8.p;
+    const dim3 taps((unsigned)(((size_t)max_n * ks * ks + 255) / 256));
+    for (int c0 = 0; c0 < n_scans; c0 += chunk) {
+        const int B = std::min(chunk, n_scans - c0);
+        YmScanRef *hs = all.data() + c0;
+        for (int i = 0; i < B; i++) {
+            const ym_scan *q = scans[c0 + i];
+            scan_resolve(q);
+            hs[i].ranges = q->d_ranges; hs[i].n = q->n;
+            hs[i].min_angle = q->min_angle; hs[i].angle_inc = q->angle_inc; hs[i].min_range = q->min_range;
+            hs[i].range_threshold = q->range_threshold;
+            hs[i].pose[0] = q->pose[0]; hs[i].pose[1] = q->pose[1]; hs[i].pose[2] = q->pose[2];
+        }
+        HIP_TRY(hipMemcpyAsync(m->grow_scans.p, hs, sizeof(YmScanRef) * (size_t)B, hipMemcpyHostToDevice, st));
+        a.n_scans = B;
+        hipLaunchKernelGGL(ym::map_grow_cells_kernel, dim3(B), dim3(1024), 0, st, a);
+        hipLaunchKernelGGL(ym::map_grow_smear_kernel<false>, dim3(taps.x, B), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(ym::map_grow_smear_kernel<true>, dim3(taps.x, B), dim3(256), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(got, m->grow_stats.p, sizeof got, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    s.points = (int64_t)got[ym::kMgPoints]; s.stamped = (int64_t)got[ym::kMgStamped]; s.dropped = (int64_t)got[ym::kMgDropped];
+    if (s.stamped > 0) { // the stamped cells' box, widened by the taps' reach and cut to the map
+        s.x0 = std::max(0, (int)got[ym::kMgX0] - half); s.y0 = std::max(0, (int)got[ym::kMgY0] - half);
+        s.x1 = std::min(mp->width, (int)got[ym::kMgX1] + half + 1); s.y1 = std::min(mp->height, (int)got[ym::kMgY1] + half + 1);
+    }
+    if (stats) *stats = s;
+    return YM_OK;
+}
+
 int ym_match_map(ym_matcher *m, const ym_map *mp, double ox, double oy, const ym_scan *const *queries, int n_queries,
                  int penalize, int refine, const ym_map_search *coarse, ym_result *out) {
     if (!m || !mp || !queries || !out) return set_err(YM_ERR_INVALID, "null argument");

@@ -61,6 +61,9 @@ struct ym_matcher {
     std::vector<double> kernel_f; // yagpy: the float kernel (helpers.py:86-97), for maps built from occupancy images
     DevBuf<double> kernel_f_dev;
     DevBuf<double2> map_pts;      // match against a map: the query point set
+    DevBuf<YmScanRef> grow_scans; // ym_map_add_scans: the scans of one chunk, ...
+    DevBuf<int32_t> grow_cells;   // ... the cell of every beam (ym_k_mapgrow.hpp) ...
+    DevBuf<unsigned long long> grow_stats; // ... and the counts and the box of the call
     int z2max = 0;               // largest squared cell distance whose kernel value is 100
     DevBuf<uint8_t> ktab;
     DevBuf<uint8_t> rowtab;   // the raster's row-pass tables (upload_lut)

@@ -32,6 +32,7 @@
 #include "ym_k_gather.hpp"
 #include "ym_k_yagpy.hpp"
 #include "ym_k_yagmap.hpp"
+#include "ym_k_mapgrow.hpp"
 #include "ym_k_occupancy.hpp"
 #include "ym_k_occlive.hpp"
 #include "ym_k_raytrace.hpp"

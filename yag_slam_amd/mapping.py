@@ -410,3 +410,85 @@ class MapLocalizer(object):
             raise ValueError("MapLocalizer: scan %d of the call could not be matched (no valid reading or an empty lattice); "
                              "it keeps its odometry prior" % (done - 1))
         return got
+
+
+class MapBuilder(object):
+    """Mapping mode over a resident map: every scan is tracked in the map (`MapLocalizer`'s step, one
+    `ScanMatcher.track_in_map` call on [last, scan]) and the scans that moved far enough are then added to it
+    (`CorrelationMap.add_scans`), so the robot can leave what the map showed when it started.  No graph, no running chain.
+
+    matcher: a `ScanMatcher(..., semantics="yagpy")`; cmap: an empty map (`matcher.empty_correlation_map`) or a prior map that
+    is to be kept current, its cell (0, 0) at world (ox, oy); coarse, min_response: as in `MapLocalizer`; min_distance
+    (metres), min_rotation (radians): a tracked scan is added when its pose differs from the last added scan's by at least
+    one of the two -- the ROS node's keyframe rule (slam_node_ros1:299-301) negated.  A step whose correction was not applied
+    is never added: its pose is dead reckoning.
+
+    `last` is the last scan processed, `last_added` the last one added, `added` every scan in the map (in order), `lost` the
+    number of consecutive steps whose correction was not applied, `results` every step's result."""
+
+    def __init__(self, matcher, cmap, ox, oy, coarse=None, min_response=0.0, min_distance=0.0, min_rotation=0.0):
+        self.matcher, self.cmap, self.ox, self.oy = matcher, cmap, ox, oy
+        self.coarse, self.min_response = coarse, min_response
+        self.min_distance, self.min_rotation = min_distance, min_rotation
+        self.last = None
+        self.last_added = None
+        self.added = []
+        self.lost = 0
+        self.results = []
+
+    def _add(self, scan):
+        stats = self.cmap.add_scans(self.ox, self.oy, [scan])
+        self.added.append(scan)
+        self.last_added = scan
+        return stats
+
+    def start(self, scan):
+        """The first scan: its pose is known (`corrected_pose` and `odom_pose` set by the caller).  It is added to the map and
+        becomes `last` and `last_added`.  Returns the add's MapAddStats."""
+        stats = self._add(scan)
+        self.last, self.lost = scan, 0
+        return stats
+
+    def _is_keyframe(self, scan):
+        p, l = scan.corrected_pose, self.last_added.corrected_pose
+        near = ((p.x - l.x) ** 2 + (p.y - l.y) ** 2 < self.min_distance ** 2 and
+                abs(p.euler[-1] - l.euler[-1]) < self.min_rotation)
+        return not near
+
+    def process_scan(self, scan):
+        """One step: prior = last.corrected_pose + (scan.odom_pose - last.odom_pose), the match against the map as it is,
+        `scan.corrected_pose` = the corrected pose (or the prior); then, if the correction was applied and the keyframe rule
+        holds, the scan is added to the map.  Returns the result (meta["accepted"], meta["added"]); the very first scan only
+        starts the map (None).  A scan the matcher cannot serve (no valid reading) raises; it keeps its prior, is not added,
+        and the track goes on from it."""
+        if self.last is None:
+            self.start(scan)
+            return None
+        res, done = self.matcher.track_in_map(self.cmap, self.ox, self.oy, [self.last, scan], 1, True, True, self.coarse,
+                                              self.min_response)
+        self.last = scan
+        if done < 2:
+            raise ValueError("MapBuilder: the scan could not be matched (no valid reading or an empty lattice); "
+                             "it keeps its odometry prior")
+        r = res[1]
+        self.lost = 0 if r.meta["accepted"] else self.lost + 1
+        r.meta["added"] = bool(r.meta["accepted"] and self._is_keyframe(scan))
+        if r.meta["added"]:
+            self._add(scan)
+        self.results.append(r)
+        return r
+
+    def process_scans(self, scans):
+        """`process_scan` for each scan in turn (every step needs the map as the step before left it); the list of results."""
+        out = []
+        for s in scans:
+            r = self.process_scan(s)
+            if r is not None:
+                out.append(r)
+        return out
+
+    def rebuild(self):
+        """Clear the map and add every scan of `added` at its current pose, in one library call: after an optimiser moved
+        them (a maximum cannot be undone scan by scan).  Returns the add's MapAddStats."""
+        self.cmap.clear()
+        return self.cmap.add_scans(self.ox, self.oy, list(self.added))

@@ -371,6 +371,13 @@ class ScanMatcher(object):
             raise _capi.YmError(-1, _capi.last_error())
         return CorrelationMap(self, h)
 
+    def empty_correlation_map(self, width, height):
+        """A resident CorrelationMap of `height` x `width` zeros, to be filled with `CorrelationMap.add_scans`."""
+        h = self._lib.ym_map_create_empty(self._m, int(width), int(height))
+        if not h:
+            raise _capi.YmError(-1, _capi.last_error())
+        return CorrelationMap(self, h)
+
     def match_scan_sets_with_map(self, cgrid, ox, oy, query_scans, penalty=True, do_fine=True, coarse=None):
         """The reference's signature (scan_matching.py:124): the point readings of all `query_scans` are matched as one
         set against the map `cgrid` (CorrelationMap or 2-D float array) whose cell (0, 0) lies at world (ox, oy).
@@ -672,14 +679,39 @@ class ScanMatcher(object):
         return ms.value, n.value
 
 
+MapAddStats = namedtuple("MapAddStats", ["points", "stamped", "dropped", "x0", "y0", "x1", "y1"])
+
+
 class CorrelationMap(object):
-    """A correlation grid resident on the device (ym_map): built from an occupancy image or uploaded."""
+    """A correlation grid resident on the device (ym_map): built from an occupancy image, uploaded, or made empty and
+    filled with `add_scans`.  `revision` starts at 0 and goes up by one with every `add_scans` that stamped something and
+    with every `clear`: what was derived from the map (a MapLocator) compares it with the revision it was made at."""
 
     def __init__(self, matcher, handle):
         self.m, self._h = matcher, handle
         w, h = C.c_int32(), C.c_int32()
         _capi.check(matcher._lib.ym_map_size(handle, C.byref(w), C.byref(h)))
         self.shape = (h.value, w.value)
+        self.revision = 0
+
+    def add_scans(self, ox, oy, scans):
+        """The reference's `add_scan_to_grid` (helpers.py:105-131) on the device (`ym_map_add_scans`): every point reading
+        `scan.points()` yields at the scan's current pose is stamped into the map whose cell (0, 0) lies at world (ox, oy)
+        and max-smeared with the matcher's kernel; readings outside the map are dropped and counted.  The map does not
+        depend on the order of scans or calls.  Returns MapAddStats(points, stamped, dropped, x0, y0, x1, y1): the changed
+        cells lie inside [x0, x1) x [y0, y1)."""
+        scans = list(scans)
+        hs = (C.c_void_p * max(1, len(scans)))(*[self.m._require_native(q) for q in scans])
+        st = _capi.YmMapAddStats()
+        _capi.check(self.m._lib.ym_map_add_scans(self.m._m, self._h, float(ox), float(oy), hs, len(scans), C.byref(st)))
+        if st.stamped > 0:
+            self.revision += 1
+        return MapAddStats(st.points, st.stamped, st.dropped, st.x0, st.y0, st.x1, st.y1)
+
+    def clear(self):
+        """every cell back to zero (`ym_map_clear`)"""
+        _capi.check(self.m._lib.ym_map_clear(self.m._m, self._h))
+        self.revision += 1
 
     def to_numpy(self):
         out = np.empty(self.shape, dtype=np.float64)
@@ -767,6 +799,8 @@ class MapLocator(object):
         _capi.check(matcher._lib.ym_locator_get_info(self._h, C.byref(info)))
         self.shape, self.levels, self.max_nodes, self.bytes = (info.height, info.width), info.levels, info.max_nodes, info.bytes
         self.last_stats, self.last_points, self.last_heading_step = None, None, None
+        # the pyramid holds a copy of the map as it is now: a map that takes scans afterwards leaves it stale
+        self._cmap, self._revision = cmap, getattr(cmap, "revision", 0)
 
     def read_level(self, level):
         """test hook: level `level` of the pyramid over the map's own cells"""
@@ -781,6 +815,7 @@ class MapLocator(object):
         heading 0 -- to `pose`), best first, ties by ascending index.  headings: explicit angles (default 2 pi k / n_angles).
         min_separation = (metres, radians): the device's best 64 are filtered greedily (filter_min_separation) before the
         first top_k are returned.  `.last_stats`: dict(nq, chunks, nodes and survivors per level, probe_nodes); `.last_points`: the point set."""
+        self._check_revision()
         if headings is None:
             headings = 2.0 * np.pi * np.arange(int(n_angles)) / float(int(n_angles))
         headings = np.ascontiguousarray(headings, dtype=np.float64).reshape(-1)
@@ -812,6 +847,12 @@ class MapLocator(object):
         if min_separation is not None:
             cands = filter_min_separation(cands, float(min_separation[0]), float(min_separation[1]))[:int(top_k)]
         return cands
+
+    def _check_revision(self):
+        now = getattr(self._cmap, "revision", 0)
+        if now != self._revision:
+            raise ValueError("MapLocator: the map has changed since this locator was made (revision %d, now %d): "
+                             "make a new locator with map_locator(cmap)" % (self._revision, now))
 
     def close(self):
         if getattr(self, "_h", None):
