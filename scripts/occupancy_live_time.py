@@ -79,7 +79,7 @@ def measure(scans, held, reps):
         if form == 0:
             row["identical_to_full"] = identical
             row["e_ros_map_alone_ms"], _ = timed(live.ros_map, reps)
-            row["e_grid_alone_ms"], _ = timed(live.grid, reps)
+            row["e_grid_alone_ms"], row["e_grid_alone_all"] = timed(live.grid, reps)
             row["e_remove_ms"], _ = timed(lambda: live.remove(new), reps, before=lambda: new[0] in live or live.add(new))
             if new[0] not in live:
                 live.add(new)
@@ -111,8 +111,8 @@ def measure(scans, held, reps):
     for slack in (0, 64):
         live = occupancy.LiveOccupancyGrid(RES, RT, anchor=(full.origin.x, full.origin.y), slack_cells=slack)
         live.add(scans)
-        ms, _ = timed(lambda: live.add(scans), reps, before=lambda: live.remove(scans))
-        row["f_add_all_by_slack"][str(slack)] = dict(ms=ms, pitch=live.info["alloc_width"])
+        ms, every = timed(lambda: live.add(scans), reps, before=lambda: live.remove(scans))
+        row["f_add_all_by_slack"][str(slack)] = dict(ms=ms, all=every, pitch=live.info["alloc_width"])
         live.close()
     row["b_live_publish_ms"] = row["bd_publish_wave_per_ray_ms"]
     row["speedup_b_over_a"] = round(row["a_full_ros_map_ms"] / row["b_live_publish_ms"], 2)

@@ -126,6 +126,30 @@ def test_contended_cells_lose_no_count():
     assert np.array_equal(many.passes, 64 * alone.passes) and np.array_equal(many.hits, 64 * alone.hits)
 
 
+def test_more_scans_than_one_launch_has_rows_of_blocks():
+    """65 537 times one scan of 17 beams in one call (the call only reads its scans, so one object serves): a launch has at most
+    65 535 rows of blocks, so the trace goes out in several.  Exactly 65 537 times the counts of the scan alone, on the same grid;
+    the largest count, 17 * 65 537, is far below 2^32.  The image is the rule (tests/occupancy_ref.py) on those counts: the single
+    rendering's wherever that one had its more than two passes -- hits / passes is the same quotient -- and decided by the same
+    quotient where one or two passes left the single rendering unknown."""
+    from tests import occupancy_ref as ref
+    scans, res, rt = fixture("ragged_a_0.25")
+    one = scans[1]
+    assert len(one.ranges) == 17
+    n = 65537
+    alone = _render([one], res, rt)
+    many = _render([one] * n, res, rt)
+    assert many.image.shape == alone.image.shape and many.offset == alone.offset
+    assert int(alone.passes.max()) > 1 and int(alone.hits.sum()) > 0 and int(alone.passes.max()) * n < 2 ** 32
+    assert np.array_equal(many.passes, n * alone.passes) and np.array_equal(many.hits, n * alone.hits)
+    decided = alone.passes > ref.MIN_PASS
+    assert decided.any() and np.array_equal(many.image[decided], alone.image[decided])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        occupied = alone.hits.astype(np.float64) / alone.passes.astype(np.float64) > ref.OCC_RATIO
+    want = np.where(alone.passes == 0, ref.UNKNOWN, np.where(occupied, ref.OCCUPIED, ref.FREE)).astype(np.uint8)
+    assert np.array_equal(many.image, want), int((many.image != want).sum())
+
+
 def test_rendering_is_repeatable():
     scans, res, rt = fixture("ragged_b_0.05")
     a, b = _render(scans, res, rt), _render(scans, res, rt)

@@ -221,6 +221,40 @@ def test_ray_lengths_around_the_wave_width(form):
     assert not g.passes.any() and not g.hits.any()
 
 
+@functools.lru_cache(maxsize=None)
+def _many_copies():
+    """-> (the full renderer's counted grid of one scan of 17 beams, 32 769 copies of that scan created in bulk, res, rt)"""
+    from yag_slam_amd.models import native_many
+    from yag_slam_amd.occupancy import create_occupancy_grid
+    scans, res, rt = fixture("ragged_a_0.25")
+    one = scans[1]
+    assert len(one.ranges) == 17
+    alone = create_occupancy_grid([one], res, rt, counts=True)
+    copies = [one.copy() for _ in range(32769)]   # (the grid refuses a scan that is in a list twice)
+    native_many(copies)
+    return alone, copies, res, rt
+
+
+@pytest.mark.parametrize("form", (0, 1))
+def test_more_scans_than_one_launch_takes(form):
+    """32 769 times one scan of 17 beams in one add, one more than a launch of the trace takes: exactly 32 769 times the full
+    rendering's counts of the scan alone (the largest, 17 * 32 769, is far below 2^31), and after one remove of them all every
+    count is zero"""
+    alone, copies, res, rt = _many_copies()
+    n = len(copies)
+    live = _live(res, rt, anchor=(alone.offset.x, alone.offset.y))
+    live._set_trace_form(form)
+    live.add(copies)
+    g = _counted(live)
+    assert g.image.shape == alone.image.shape and (g.offset.x, g.offset.y) == (alone.offset.x, alone.offset.y)
+    assert int(alone.passes.max()) > 1 and int(alone.hits.sum()) > 0
+    assert np.array_equal(g.passes, n * alone.passes) and np.array_equal(g.hits, n * alone.hits)
+    live.remove(copies)
+    g = _counted(live)
+    assert g.image.shape == alone.image.shape and not g.passes.any() and not g.hits.any()
+    live.close()
+
+
 # ------------------------------------------------------------------------------------------ 4. remove and move
 @pytest.mark.parametrize("name", sorted(REMOVE_CASES))
 def test_remove_leaves_the_rest_in_the_unshrunk_window(name):

@@ -138,15 +138,7 @@ int ym_locator_locate(ym_locator *lc, double ox, double oy, const ym_scan *const
     // ---- the point set, exactly as ym_match_map builds it: every query's readings at its own pose minus the mean query position
     const double ox_real = sx / (double)n_queries, oy_real = sy / (double)n_queries;
     std::vector<YmScanRef> hs(n_queries);
-    std::memset(hs.data(), 0, sizeof(YmScanRef) * n_queries);
-    for (int i = 0; i < n_queries; i++) {
-        const ym_scan *q = queries[i];
-        scan_resolve(q);
-        hs[i].ranges = q->d_ranges; hs[i].n = q->n;
-        hs[i].min_angle = q->min_angle; hs[i].angle_inc = q->angle_inc; hs[i].min_range = q->min_range;
-        hs[i].range_threshold = q->range_threshold;
-        hs[i].pose[0] = q->pose[0]; hs[i].pose[1] = q->pose[1]; hs[i].pose[2] = q->pose[2];
-    }
+    for (int i = 0; i < n_queries; i++) hs[i] = scan_ref(queries[i]);
     if ((rc = lc->scans_dev.ensure(sizeof(YmScanRef) * n_queries)) || (rc = lc->pts.ensure((size_t)std::max(total, 1))) ||
         (rc = lc->dirs.ensure((size_t)n_angles)))
         return rc;

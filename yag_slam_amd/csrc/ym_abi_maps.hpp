@@ -140,7 +140,6 @@ int ym_map_add_scans(ym_matcher *m, ym_map *mp, double ox, double oy, const ym_s
     unsigned long long got[ym::kMgStatSlots];
     HIP_TRY(hipMemcpyAsync(m->grow_stats.p, init, sizeof init, hipMemcpyHostToDevice, st));
     std::vector<YmScanRef> all((size_t)n_scans);
-    std::memset(all.data(), 0, sizeof(YmScanRef) * (size_t)n_scans);
     ym::MapGrowArgs a;
     std::memset(&a, 0, sizeof a);
     a.scans = m->grow_scans.p; a.max_n = max_n; a.width = mp->width; a.height = mp->height;
@@ -151,14 +150,7 @@ int ym_map_add_scans(ym_matcher *m, ym_map *mp, double ox, double oy, const ym_s
     for (int c0 = 0; c0 < n_scans; c0 += chunk) {
         const int B = std::min(chunk, n_scans - c0);
         YmScanRef *hs = all.data() + c0;
-        for (int i = 0; i < B; i++) {
-            const ym_scan *q = scans[c0 + i];
-            scan_resolve(q);
-            hs[i].ranges = q->d_ranges; hs[i].n = q->n;
-            hs[i].min_angle = q->min_angle; hs[i].angle_inc = q->angle_inc; hs[i].min_range = q->min_range;
-            hs[i].range_threshold = q->range_threshold;
-            hs[i].pose[0] = q->pose[0]; hs[i].pose[1] = q->pose[1]; hs[i].pose[2] = q->pose[2];
-        }
+        for (int i = 0; i < B; i++) hs[i] = scan_ref(scans[c0 + i]);
         HIP_TRY(hipMemcpyAsync(m->grow_scans.p, hs, sizeof(YmScanRef) * (size_t)B, hipMemcpyHostToDevice, st));
         a.n_scans = B;
         hipLaunchKernelGGL(ym::map_grow_cells_kernel, dim3(B), dim3(1024), 0, st, a);
@@ -224,14 +216,7 @@ int ym_match_map(ym_matcher *m, const ym_map *mp, double ox, double oy, const ym
     slot.desc_live_bytes = 0; // (the slot's pinned descriptor buffer is rewritten here)
     YmScanRef *hs = reinterpret_cast<YmScanRef *>(slot.desc.p);
     std::memset(hs, 0, scans_bytes);
-    for (int i = 0; i < n_queries; i++) {
-        const ym_scan *q = queries[i];
-        scan_resolve(q);
-        hs[i].ranges = q->d_ranges; hs[i].n = q->n;
-        hs[i].min_angle = q->min_angle; hs[i].angle_inc = q->angle_inc; hs[i].min_range = q->min_range;
-        hs[i].range_threshold = q->range_threshold;
-        hs[i].pose[0] = q->pose[0]; hs[i].pose[1] = q->pose[1]; hs[i].pose[2] = q->pose[2];
-    }
+    for (int i = 0; i < n_queries; i++) hs[i] = scan_ref(queries[i]);
     YmItemState *st0 = reinterpret_cast<YmItemState *>(slot.desc.p + scans_bytes);
     std::memset(st0, 0, sizeof *st0);
     st0->pose[0] = st0->center[0] = ox_real; st0->pose[1] = st0->center[1] = oy_real;
@@ -362,6 +347,40 @@ int ym_image_despeckle(int device, const uint8_t *image, int width, int height, 
 }
 
 // ---- occupancy-grid rendering (karto_scanmatcher.create_occupancy_grid)
+// Shared with the live occupancy grid (ym_abi_occlive.hpp); both run on the null stream.
+// The bounding boxes (LocalizedRangeScan::Update) of a device scan table, joined into box[4] = xmin, ymin, xmax, ymax, which the
+// caller initialises: the box OccupancyGrid::ComputeDimensions sizes the grid by.  d_boxes: the caller's device memory for
+// [n_scans][4] doubles, allocated with the caller's other buffers and freed with them.  (Measured: allocated and freed in here, so
+// before the counts are allocated, a trace of 500 to 2000 scans ran 13 % faster to 7 % slower through unchanged kernels and an add
+// of five scans 12 us slower -- profiles/map_side_fold_time.json; where the counts lie decides the rate of their atomics.)
+static int occ_join_boxes(const YmScanRef *d_scans, int n_scans, int max_n, double range_threshold, double *d_boxes, double box[4]) {
+    ym::OccArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.scans = d_scans; a.n_scans = n_scans; a.max_n = max_n; a.range_threshold = range_threshold; a.boxes = d_boxes;
+    hipLaunchKernelGGL(ym::occ_bbox_kernel, dim3(n_scans), dim3(256), 0, nullptr, a);
+    HIP_TRY(hipGetLastError());
+    std::vector<double> boxes((size_t)4 * n_scans);
+    HIP_TRY(hipMemcpy(boxes.data(), d_boxes, sizeof(double) * boxes.size(), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n_scans; i++) {
+        box[0] = std::min(box[0], boxes[4 * i]); box[1] = std::min(box[1], boxes[4 * i + 1]);
+        box[2] = std::max(box[2], boxes[4 * i + 2]); box[3] = std::max(box[3], boxes[4 * i + 3]);
+    }
+    return YM_OK;
+}
+
+// The rays of a device scan table into the counts `a` describes (everything but a.scans and a.n_scans is the caller's).
+// form 1: a thread per ray; 0: a wave per ray, which needs range_threshold * scale < 2^24 (ym_occmap_create checks it)
+static int occ_trace(ym::OccArgs a, const YmScanRef *d_scans, int n_scans, int form) {
+    for (int first = 0; first < n_scans; first += 32768) { // (a launch has at most 65535 rows of blocks)
+        const int count = std::min(n_scans - first, 32768);
+        a.scans = d_scans + first; a.n_scans = count;
+        if (form == 1) hipLaunchKernelGGL(ym::occ_trace_thread_kernel, dim3((a.max_n + 255) / 256, count), dim3(256), 0, nullptr, a);
+        else hipLaunchKernelGGL(ym::occ_trace_wave_kernel, dim3((a.max_n + 3) / 4, count), dim3(256), 0, nullptr, a);
+        HIP_TRY(hipGetLastError());
+    }
+    return YM_OK;
+}
+
 // keep_counts (ym_occupancy_create_counted, a test hook): the pass and hit counts are copied to the host before they are freed
 // clean (ym_occupancy_create_clean): the image goes through the component area filter on the device before its copy to the host
 static ym_occupancy *occupancy_render(const ym_scan *const *scans, int n_scans, double resolution, double range_threshold, bool keep_counts,
@@ -377,15 +396,7 @@ static ym_occupancy *occupancy_render(const ym_scan *const *scans, int n_scans, 
     DevGuard guard(device);
     if (guard.status() != YM_OK) return nullptr;
     std::vector<YmScanRef> hs(n_scans);
-    std::memset(hs.data(), 0, sizeof(YmScanRef) * n_scans);
-    for (int i = 0; i < n_scans; i++) {
-        const ym_scan *q = scans[i];
-        scan_resolve(q);
-        hs[i].ranges = q->d_ranges; hs[i].n = q->n;
-        hs[i].min_angle = q->min_angle; hs[i].angle_inc = q->angle_inc; hs[i].min_range = q->min_range;
-        hs[i].range_threshold = q->max_range; // the laser's MAXIMUM range travels in this field (see occ_trace_kernel)
-        hs[i].pose[0] = q->pose[0]; hs[i].pose[1] = q->pose[1]; hs[i].pose[2] = q->pose[2];
-    }
+    for (int i = 0; i < n_scans; i++) hs[i] = scan_ref(scans[i], nullptr, true);
     DevBuf<YmScanRef> d_scans;
     DevBuf<double> d_boxes;
     DevBuf<unsigned> d_cnt;
@@ -396,34 +407,28 @@ static ym_occupancy *occupancy_render(const ym_scan *const *scans, int n_scans, 
         int rc;
         if ((rc = d_scans.alloc(n_scans)) || (rc = d_boxes.alloc((size_t)4 * n_scans))) return rc;
         HIP_TRY(hipMemcpy(d_scans.p, hs.data(), sizeof(YmScanRef) * n_scans, hipMemcpyHostToDevice));
-        ym::OccArgs a;
-        std::memset(&a, 0, sizeof a);
-        a.scans = d_scans.p; a.n_scans = n_scans; a.max_n = max_n; a.range_threshold = range_threshold; a.boxes = d_boxes.p;
-        hipLaunchKernelGGL(ym::occ_bbox_kernel, dim3(n_scans), dim3(256), 0, nullptr, a);
-        HIP_TRY(hipGetLastError());
-        std::vector<double> boxes((size_t)4 * n_scans);
-        HIP_TRY(hipMemcpy(boxes.data(), d_boxes.p, sizeof(double) * boxes.size(), hipMemcpyDeviceToHost));
         // OccupancyGrid::ComputeDimensions: the scans' bounding boxes joined, width = Round(size * scale)
-        double x0 = 1e300, y0 = 1e300, x1 = -1e300, y1 = -1e300;
-        for (int i = 0; i < n_scans; i++) {
-            x0 = std::min(x0, boxes[4 * i]); y0 = std::min(y0, boxes[4 * i + 1]);
-            x1 = std::max(x1, boxes[4 * i + 2]); y1 = std::max(y1, boxes[4 * i + 3]);
-        }
+        double box[4] = {1e300, 1e300, -1e300, -1e300};
+        if ((rc = occ_join_boxes(d_scans.p, n_scans, max_n, range_threshold, d_boxes.p, box))) return rc;
         const double scale = 1.0 / resolution;
-        const int width = (int)kt_round_h((x1 - x0) * scale), height = (int)kt_round_h((y1 - y0) * scale);
+        const int width = (int)kt_round_h((box[2] - box[0]) * scale), height = (int)kt_round_h((box[3] - box[1]) * scale);
         if (width <= 0 || height <= 0 || (double)width * height > 2.0e9)
             return set_err(YM_ERR_UNSUPPORTED, "occupancy grid of %d x %d cells", width, height);
         const size_t n = (size_t)width * height;
         if ((rc = d_cnt.alloc(2 * n)) || (rc = d_img.alloc(n))) return rc;
         HIP_TRY(hipMemset(d_cnt.p, 0, 2 * n * sizeof(unsigned)));
-        a.scale = scale; a.off_x = x0; a.off_y = y0; a.width = width; a.height = height;
+        // the live grid's kernels with the lattice anchored at the box's minimum, the memory at the lattice's origin and as wide as
+        // the grid, every ray added, and all of it read
+        ym::OccArgs a;
+        std::memset(&a, 0, sizeof a);
+        a.max_n = max_n; a.range_threshold = range_threshold; a.scale = scale; a.anchor_x = box[0]; a.anchor_y = box[1];
+        a.width = a.win_w = width; a.height = a.win_h = height; a.pitch = width; a.sign = 1u;
         a.pass = d_cnt.p; a.hits = d_cnt.p + n; a.image = d_img.p;
-        hipLaunchKernelGGL(ym::occ_trace_kernel, dim3((max_n + 255) / 256, n_scans), dim3(256), 0, nullptr, a);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(ym::occ_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, a);
+        if ((rc = occ_trace(a, d_scans.p, n_scans, 1))) return rc; // (a launch over many scans: a thread per ray)
+        hipLaunchKernelGGL(ym::occ_update_kernel, dim3((unsigned)((width + 255) / 256), (unsigned)std::min(height, 65535)), dim3(256), 0, nullptr, a);
         HIP_TRY(hipGetLastError());
         og->info.width = width; og->info.height = height;
-        og->info.offset_x = x0; og->info.offset_y = y0; og->info.resolution = resolution;
+        og->info.offset_x = box[0]; og->info.offset_y = box[1]; og->info.resolution = resolution;
         if (clean) {
             if (n > (size_t)INT32_MAX) return set_err(YM_ERR_UNSUPPORTED, "occupancy grid of %d x %d cells: the filter takes at most 2^31 - 1", width, height);
             if ((rc = despeckle_run(d_img.p, d_img.p, width, height, *clean, nullptr, &og->clean_stats))) return rc;

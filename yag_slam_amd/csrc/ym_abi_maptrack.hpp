@@ -77,14 +77,7 @@ int ym_match_map_many(ym_matcher *m, const ym_map *mp, double ox, double oy, con
     slot.desc_live_bytes = 0; // (the slot's pinned descriptor buffer is rewritten here)
     YmScanRef *hs = reinterpret_cast<YmScanRef *>(slot.desc.p);
     std::memset(hs, 0, scans_bytes);
-    for (int i = 0; i < n_scans; i++) {
-        const ym_scan *q = queries[s0 + i];
-        scan_resolve(q);
-        hs[i].ranges = q->d_ranges; hs[i].n = q->n;
-        hs[i].min_angle = q->min_angle; hs[i].angle_inc = q->angle_inc; hs[i].min_range = q->min_range;
-        hs[i].range_threshold = q->range_threshold;
-        hs[i].pose[0] = q->pose[0]; hs[i].pose[1] = q->pose[1]; hs[i].pose[2] = q->pose[2];
-    }
+    for (int i = 0; i < n_scans; i++) hs[i] = scan_ref(queries[s0 + i]);
     std::memcpy(slot.desc.p + scans_bytes, items.data(), sizeof(ym::MapItemDesc) * (size_t)n_items);
     YmItemState *st0 = reinterpret_cast<YmItemState *>(slot.desc.p + scans_bytes + items_bytes);
     std::memset(st0, 0, states_bytes);

@@ -1,5 +1,5 @@
-// ym_abi_occlive.hpp -- C ABI: the live occupancy grid (ym_occmap_*; kernels in ym_k_occlive.hpp, window and growth arithmetic in
-// ym_occlive_window.hpp)
+// ym_abi_occlive.hpp -- C ABI: the live occupancy grid (ym_occmap_*; kernels in ym_k_occupancy.hpp and their launch helpers in
+// ym_abi_maps.hpp, both shared with the full renderer; window and growth arithmetic in ym_occlive_window.hpp)
 // Part of yagmatch.hip (included inside its extern "C" block); not a header of its own.
 // Everything runs on the null stream and every entry returns with its work complete, like occupancy_render: a scan may be destroyed
 // as soon as the call that read it has returned.
@@ -8,7 +8,7 @@ static int occmap_check(const ym_occmap *om) { return om ? YM_OK : set_err(YM_ER
 ym_occmap *ym_occmap_create(int device, double resolution, double range_threshold, const double *anchor_xy, int slack_cells) {
     if (!(resolution > 0) || !(range_threshold > 0)) { set_err(YM_ERR_INVALID, "resolution and range_threshold must be > 0"); return nullptr; }
     const double scale = 1.0 / resolution;
-    // (the wave-per-ray trace multiplies two ray lengths in cells: ym_k_occlive.hpp proves its bound from this one)
+    // (the wave-per-ray trace multiplies two ray lengths in cells: ym_k_occupancy.hpp proves its bound from this one)
     if (!(range_threshold * scale < 16777216.0)) { set_err(YM_ERR_UNSUPPORTED, "range_threshold / resolution must be below 2^24 cells"); return nullptr; }
     if (slack_cells < 0) { set_err(YM_ERR_INVALID, "slack_cells %d: 0 or more", slack_cells); return nullptr; }
     if (anchor_xy && !(std::isfinite(anchor_xy[0]) && std::isfinite(anchor_xy[1]))) { set_err(YM_ERR_INVALID, "anchor: not finite"); return nullptr; }
@@ -48,21 +48,12 @@ int ym_occmap_accumulate(ym_occmap *om, const ym_scan *const *scans, const doubl
     }
     DEV_GUARD(om->device);
     std::vector<YmScanRef> hs(n);
-    std::memset(hs.data(), 0, sizeof(YmScanRef) * n);
-    for (int i = 0; i < n; i++) {
-        const ym_scan *q = scans[i];
-        scan_resolve(q);
-        const double *p = poses ? poses + 3 * (size_t)i : q->pose;
-        hs[i].ranges = q->d_ranges; hs[i].n = q->n;
-        hs[i].min_angle = q->min_angle; hs[i].angle_inc = q->angle_inc; hs[i].min_range = q->min_range;
-        hs[i].range_threshold = q->max_range; // the laser's MAXIMUM range travels in this field (see occ_trace_kernel)
-        hs[i].pose[0] = p[0]; hs[i].pose[1] = p[1]; hs[i].pose[2] = p[2];
-    }
+    for (int i = 0; i < n; i++) hs[i] = scan_ref(scans[i], poses ? poses + 3 * (size_t)i : nullptr, true);
     int rc;
     DevBuf<YmScanRef> d_scans;
     if ((rc = d_scans.alloc(n))) return rc;
     HIP_TRY(hipMemcpy(d_scans.p, hs.data(), sizeof(YmScanRef) * n, hipMemcpyHostToDevice));
-    ym::OccLiveArgs a;
+    ym::OccArgs a;
     std::memset(&a, 0, sizeof a);
     a.scans = d_scans.p; a.n_scans = n; a.max_n = max_n; a.range_threshold = om->range_threshold; a.scale = om->scale;
     a.sign = sign > 0 ? 1u : 0xFFFFFFFFu;
@@ -71,19 +62,9 @@ int ym_occmap_accumulate(ym_occmap *om, const ym_scan *const *scans, const doubl
         DevBuf<double> d_boxes;
         DevBuf<int32_t> d_reach;
         if ((rc = d_boxes.alloc((size_t)4 * n)) || (rc = d_reach.alloc((size_t)4 * n))) return rc;
-        ym::OccArgs ba;
-        std::memset(&ba, 0, sizeof ba);
-        ba.scans = d_scans.p; ba.n_scans = n; ba.max_n = max_n; ba.range_threshold = om->range_threshold; ba.boxes = d_boxes.p;
-        hipLaunchKernelGGL(ym::occ_bbox_kernel, dim3(n), dim3(256), 0, nullptr, ba);
-        HIP_TRY(hipGetLastError());
-        std::vector<double> boxes((size_t)4 * n);
-        HIP_TRY(hipMemcpy(boxes.data(), d_boxes.p, sizeof(double) * boxes.size(), hipMemcpyDeviceToHost));
         double box[4] = {1e300, 1e300, -1e300, -1e300};
         if (om->added) std::memcpy(box, om->box, sizeof box);
-        for (int i = 0; i < n; i++) {
-            box[0] = std::min(box[0], boxes[4 * i]); box[1] = std::min(box[1], boxes[4 * i + 1]);
-            box[2] = std::max(box[2], boxes[4 * i + 2]); box[3] = std::max(box[3], boxes[4 * i + 3]);
-        }
+        if ((rc = occ_join_boxes(d_scans.p, n, max_n, om->range_threshold, d_boxes.p, box))) return rc;
         double anchor[2] = {om->anchor[0], om->anchor[1]};
         if (!om->has_anchor) { anchor[0] = box[0]; anchor[1] = box[1]; } // the first add decides
         ymw::Rect window;
@@ -93,7 +74,7 @@ int ym_occmap_accumulate(ym_occmap *om, const ym_scan *const *scans, const doubl
             return set_err(YM_ERR_UNSUPPORTED, "occupancy grid of %lld x %lld cells", (long long)window.w, (long long)window.h);
         // the cells the new rays can touch
         a.anchor_x = anchor[0]; a.anchor_y = anchor[1]; a.reach = d_reach.p;
-        hipLaunchKernelGGL(ym::occ_live_reach_kernel, dim3(n), dim3(256), 0, nullptr, a);
+        hipLaunchKernelGGL(ym::occ_reach_kernel, dim3(n), dim3(256), 0, nullptr, a);
         HIP_TRY(hipGetLastError());
         std::vector<int32_t> rr((size_t)4 * n);
         HIP_TRY(hipMemcpy(rr.data(), d_reach.p, sizeof(int32_t) * rr.size(), hipMemcpyDeviceToHost));
@@ -134,13 +115,7 @@ int ym_occmap_accumulate(ym_occmap *om, const ym_scan *const *scans, const doubl
     a.org_x = (int32_t)om->alloc.x0; a.org_y = (int32_t)om->alloc.y0; a.width = (int32_t)om->alloc.w; a.height = (int32_t)om->alloc.h;
     a.pitch = om->alloc.w;
     a.pass = om->cnt.p; a.hits = om->cnt.p + (size_t)om->alloc.cells();
-    for (int first = 0; first < n; first += 32768) { // (a launch has at most 65535 rows of blocks)
-        const int count = std::min(n - first, 32768);
-        a.scans = d_scans.p + first; a.n_scans = count;
-        if (om->trace_form == 1) hipLaunchKernelGGL(ym::occ_live_trace_thread_kernel, dim3((max_n + 255) / 256, count), dim3(256), 0, nullptr, a);
-        else hipLaunchKernelGGL(ym::occ_live_trace_kernel, dim3((max_n + 3) / 4, count), dim3(256), 0, nullptr, a);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = occ_trace(a, d_scans.p, n, om->trace_form))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return YM_OK;
 }
@@ -188,13 +163,13 @@ int ym_occmap_read(ym_occmap *om, uint8_t *image, int64_t bytes, const ym_despec
         return set_err(YM_ERR_UNSUPPORTED, "occupancy grid of %lld x %lld cells: the filter takes at most 2^31 - 1", (long long)om->window.w, (long long)om->window.h);
     DEV_GUARD(om->device);
     if ((rc = om->img.ensure(n))) return rc;
-    ym::OccLiveArgs a;
+    ym::OccArgs a;
     std::memset(&a, 0, sizeof a);
     a.pitch = om->alloc.w; a.pass = om->cnt.p; a.hits = om->cnt.p + (size_t)om->alloc.cells();
     a.win_x = (int32_t)(om->window.x0 - om->alloc.x0); a.win_y = (int32_t)(om->window.y0 - om->alloc.y0);
     a.win_w = (int32_t)om->window.w; a.win_h = (int32_t)om->window.h;
     a.image = om->img.p;
-    hipLaunchKernelGGL(ym::occ_live_update_kernel, dim3((unsigned)((a.win_w + 255) / 256), (unsigned)std::min(a.win_h, 65535)), dim3(256), 0, nullptr, a);
+    hipLaunchKernelGGL(ym::occ_update_kernel, dim3((unsigned)((a.win_w + 255) / 256), (unsigned)std::min(a.win_h, 65535)), dim3(256), 0, nullptr, a);
     HIP_TRY(hipGetLastError());
     ym_despeckle_stats s{};
     if (clean && (rc = despeckle_run(om->img.p, om->img.p, a.win_w, a.win_h, *clean, nullptr, &s))) return rc;

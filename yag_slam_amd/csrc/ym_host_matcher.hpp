@@ -26,7 +26,7 @@ struct ym_occmap {
     ymw::Rect window, reach, alloc;         // lattice cells (ym_occlive_window.hpp)
     int slack = 0;
     int64_t reallocations = 0;
-    int trace_form = 0;                     // development: 1 = occ_live_trace_thread_kernel
+    int trace_form = 0;                     // development: 1 = occ_trace_thread_kernel
     DevBuf<unsigned> cnt;                   // pass [alloc.h][alloc.w], then hits [alloc.h][alloc.w]
     DevBuf<uint8_t> img;                    // the window's image between its kernel and its copy to the host
 };

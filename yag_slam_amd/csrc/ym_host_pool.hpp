@@ -276,4 +276,20 @@ inline void scan_resolve(const ym_scan *s) {
     DevGuard guard(s->device);
     stage_wait(p, *s->stage);
 }
+
+// A scan-table entry for the kernels that read scans by table (maps, tracking, locate, occupancy): the resolved scan's device ranges
+// and sensor geometry, placed at `pose` (null: the scan's own), everything else zero.  The range_threshold FIELD carries the scan's
+// range threshold, except for the occupancy kernels (ym_k_occupancy.hpp), which get the rendering's threshold as an argument and
+// read the laser's MAXIMUM range here -- the range from which AddScan ignores a reading: `max_range_in_threshold`.
+inline YmScanRef scan_ref(const ym_scan *s, const double *pose = nullptr, bool max_range_in_threshold = false) {
+    scan_resolve(s);
+    if (!pose) pose = s->pose;
+    YmScanRef r;
+    std::memset(&r, 0, sizeof r);
+    r.ranges = s->d_ranges; r.n = s->n;
+    r.min_angle = s->min_angle; r.angle_inc = s->angle_inc; r.min_range = s->min_range;
+    r.range_threshold = max_range_in_threshold ? s->max_range : s->range_threshold;
+    r.pose[0] = pose[0]; r.pose[1] = pose[1]; r.pose[2] = pose[2];
+    return r;
+}
 }  // namespace

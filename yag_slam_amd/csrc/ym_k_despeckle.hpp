@@ -3,8 +3,8 @@
 // (ros1/slam_node_ros1:191-197, there with cv2.connectedComponentsWithStats).  The rules are DESIGN.md section 12; they are
 // pinned by tests/despeckle_ref.py.  Only component AREAS are used, so no label numbering exists here.
 //
-// The component stage follows the segmenter's (ym_k_segmenter.hpp, seg_cc_*): a union-find with atomicMin towards the lowest
-// raster index, so the root of a component is its first cell whatever the order of arrival.  The tiling is the segmenter's too:
+// The component stage shares its union-find with the segmenter's (ym_k_unionfind.hpp: atomicMin towards the lowest
+// raster index, so the root of a component is its first cell whatever the order of arrival).  The tiling is the segmenter's too:
 // a block of 256 threads takes 64 columns x 16 rows, wave w rows 4 w .. 4 w + 3, a lane one column.  The grid is
 // one-dimensional (nbx blocks per row of tiles) so that an image of any shape within 2^31 - 1 cells can be launched.
 //
@@ -29,7 +29,7 @@
 // dsp_apply_kernel   out = fill where (foreground and size[root] < min_area) or (not foreground and the background rule
 //                    fired: 0 < other cells < min_area), else the input byte.  Counts components, removed components and
 //                    cleared cells.  `out` may be the input image.
-// Every loop has a bound: the walk to a root follows strictly decreasing indices, a union retries at most kDspUnionCap times
+// Every loop has a bound: the walk to a root follows strictly decreasing indices, a union retries at most kUnionCap times
 // and then raises stats[kDspErr], and the host fails the call.  Stages depend on each other only across launches.  All sums
 // that cross threads are integer sums: the output is the same from run to run.  No kernel uses scratch or LDS.  Plain C++
 // and vector memory operations only.  Part of ym_kernels.hpp.
@@ -37,7 +37,6 @@
 
 namespace ym {
 
-constexpr unsigned kDspUnionCap = 1u << 22; // retries of one union (each one means another thread linked the same root)
 enum { kDspFg = 0, kDspBg = 1, kDspComponents = 2, kDspRemoved = 3, kDspCleared = 4, kDspErr = 5, kDspStatSlots = 8 };
 
 struct DespeckleArgs {
@@ -85,32 +84,8 @@ __global__ __launch_bounds__(256) void dsp_init_kernel(DespeckleArgs a) {
     }
 }
 
-// the root of i: parents only ever decrease, so the walk ends within i steps
-__device__ __forceinline__ unsigned dsp_find(const DespeckleArgs &a, unsigned i) {
-    unsigned p = a.parent[i];
-    while (p < i) { // (bounded: a strictly decreasing index)
-        i = p;
-        p = a.parent[i];
-    }
-    return i;
-}
-
-__device__ inline void dsp_union(const DespeckleArgs &a, unsigned i, unsigned j) {
-#pragma unroll 1
-    for (unsigned it = 0; it < kDspUnionCap; it++) {
-        i = dsp_find(a, i);
-        j = dsp_find(a, j);
-        if (i == j) return;
-        if (i < j) {
-            const unsigned s = i;
-            i = j;
-            j = s;
-        }
-        const unsigned old = atomicMin(&a.parent[i], j); // i > j: link the higher root under the lower
-        if (old == i) return;
-        i = old; // i was linked meanwhile: go on from where it points
-    }
-    atomicOr(&a.stats[kDspErr], 1ull);
+__device__ __forceinline__ void dsp_union(const DespeckleArgs &a, unsigned i, unsigned j) {
+    if (!uf_union(a.parent, i, j)) atomicOr(&a.stats[kDspErr], 1ull);
 }
 
 // grid as dsp_init_kernel.  kConn: 4 or 8
@@ -142,29 +117,13 @@ __global__ __launch_bounds__(256) void dsp_merge_kernel(DespeckleArgs a) {
 
 // grid as dsp_init_kernel
 __global__ __launch_bounds__(256) void dsp_sizes_kernel(DespeckleArgs a) {
-    const int lane = threadIdx.x & 63, x = dsp_tile_x(a);
+    const int x = dsp_tile_x(a);
 #pragma unroll 1
     for (int j = 0; j < 4; j++) {
         const int y = dsp_tile_y(a, j);
         if (y >= a.height) break;
         const bool fg = x < a.width && a.image[(size_t)y * a.width + x] == a.foreground;
-        unsigned long long todo = __ballot(fg);
-        if (!todo) continue;
-        unsigned root = 0;
-        if (fg) {
-            const unsigned i = (unsigned)((size_t)y * a.width + x);
-            root = dsp_find(a, i);
-            a.parent[i] = root; // (the forest is final: a reader sees the old parent or the root, both lead to the root)
-        }
-        // one atomic per distinct root of the wave's 64 cells
-#pragma unroll 1
-        for (int it = 0; it < 64 && todo; it++) {
-            const int leader = __ffsll((long long)todo) - 1;
-            const unsigned r = (unsigned)__shfl((int)root, leader, 64);
-            const unsigned long long same = __ballot(fg && root == r) & todo;
-            if (lane == leader) atomicAdd(&a.size[r], (unsigned)__popcll(same));
-            todo &= ~same;
-        }
+        uf_wave_sizes(fg, (unsigned)((size_t)y * a.width + x), a.parent, a.size);
     }
 }
 

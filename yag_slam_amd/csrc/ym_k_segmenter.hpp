@@ -19,7 +19,7 @@
 //                       leave as at most 75 64-bit global atomics per block.
 // seg_centres_kernel    C.6: centres with pixels move to their pixels' mean, into the other centre buffer.
 // seg_cc_init_kernel, seg_cc_merge_kernel, seg_cc_sizes_kernel
-//                       D: union-find over equal 4-neighbours with atomicMin towards the lowest raster index, so the root
+//                       D: union-find (ym_k_unionfind.hpp) over equal 4-neighbours, so the root
 //                       of a component is its first pixel whatever the order.  Parents start at the start of the pixel's
 //                       run within its wave's 64 columns; the merge pass joins runs across rows and across 64-column
 //                       borders; the sizes pass flattens every pixel to its root and counts.
@@ -36,7 +36,6 @@ constexpr int kClosePitch = 128;   // LDS row (>= kCloseTile + 4 kCloseMaxR)
 constexpr int kCloseRows = kCloseTile + 4 * kCloseMaxR;
 constexpr int kSegPart = 64;       // a block of the cell kernels takes at most kSegPart x kSegPart pixels of one cell
 constexpr int kSegScanChunk = 4096; // items per block of the prefix sum
-constexpr unsigned kSegUnionCap = 1u << 22; // retries of one union (each one means another thread linked the same root)
 enum { kSegErrLoop = 0, kSegChanged = 1, kSegTotal = 2, kSegErrSlots = 4 };
 enum { kSeeds = 0, kRoots = 1 };
 
@@ -390,36 +389,9 @@ __global__ __launch_bounds__(256) void seg_cc_init_kernel(SegmenterArgs a) {
     }
 }
 
-// the root of i: parents only ever decrease, so the walk ends within i steps; the explicit cap is the count of pixels
-__device__ __forceinline__ unsigned seg_find(const SegmenterArgs &a, unsigned i) {
-    unsigned p = a.parent[i];
-    while (p < i) { // (bounded: a strictly decreasing index)
-        i = p;
-        p = a.parent[i];
-    }
-    return i;
-}
-
-__device__ inline void seg_union(const SegmenterArgs &a, unsigned i, unsigned j) {
-#pragma unroll 1
-    for (unsigned it = 0; it < kSegUnionCap; it++) {
-        i = seg_find(a, i);
-        j = seg_find(a, j);
-        if (i == j) return;
-        if (i < j) {
-            const unsigned s = i;
-            i = j;
-            j = s;
-        }
-        const unsigned old = atomicMin(&a.parent[i], j); // i > j: link the higher root under the lower
-        if (old == i) return;
-        i = old; // i was linked meanwhile: go on from where it points
-    }
-    atomicOr(&a.err[kSegErrLoop], 1u);
-}
-
 // grid as seg_cc_init_kernel.  Within a wave's 64 columns a run is one tree already, so a pixel joins its upper neighbour only
 // where a run starts (its own, or the upper row's above it), and its left neighbour only across a 64-column border.
+// (uf_union: ym_k_unionfind.hpp)
 __global__ __launch_bounds__(256) void seg_cc_merge_kernel(SegmenterArgs a) {
     const int lane = threadIdx.x & 63, x = blockIdx.x * 64 + lane;
     if (x >= a.width) return;
@@ -432,8 +404,9 @@ __global__ __launch_bounds__(256) void seg_cc_merge_kernel(SegmenterArgs a) {
         if (v == 0) continue;
         const unsigned i = (unsigned)((size_t)y * a.width + x);
         const bool left_same = x > 0 && row[x - 1] == v;
-        if (left_same && lane == 0) seg_union(a, i, i - 1u);
-        if (y > 0 && row[x - a.pitch] == v && (lane == 0 || !left_same || row[x - 1 - a.pitch] != v)) seg_union(a, i, i - (unsigned)a.width);
+        if (left_same && lane == 0 && !uf_union(a.parent, i, i - 1u)) atomicOr(&a.err[kSegErrLoop], 1u);
+        if (y > 0 && row[x - a.pitch] == v && (lane == 0 || !left_same || row[x - 1 - a.pitch] != v) && !uf_union(a.parent, i, i - (unsigned)a.width))
+            atomicOr(&a.err[kSegErrLoop], 1u);
     }
 }
 
@@ -445,22 +418,7 @@ __global__ __launch_bounds__(256) void seg_cc_sizes_kernel(SegmenterArgs a) {
         const int y = blockIdx.y * 16 + (threadIdx.x >> 6) * 4 + j;
         if (y >= a.height) break;
         const bool live = x < a.width && a.assign[(size_t)y * a.pitch + x] != 0;
-        unsigned root = 0;
-        if (live) {
-            const unsigned i = (unsigned)((size_t)y * a.width + x);
-            root = seg_find(a, i);
-            a.parent[i] = root; // (the forest is final: a reader sees the old parent or the root, both lead to the root)
-        }
-        // one atomic per distinct root of the wave's 64 pixels
-        unsigned long long todo = __ballot(live);
-#pragma unroll 1
-        for (int it = 0; it < 64 && todo; it++) {
-            const int leader = __ffsll((long long)todo) - 1;
-            const unsigned r = (unsigned)__shfl((int)root, leader, 64);
-            const unsigned long long same = __ballot(live && root == r) & todo;
-            if (lane == leader) atomicAdd(&a.size[r], (unsigned)__popcll(same));
-            todo &= ~same;
-        }
+        uf_wave_sizes(live, (unsigned)((size_t)y * a.width + x), a.parent, a.size);
     }
 }
 

@@ -34,10 +34,10 @@
 #include "ym_k_yagmap.hpp"
 #include "ym_k_mapgrow.hpp"
 #include "ym_k_occupancy.hpp"
-#include "ym_k_occlive.hpp"
 #include "ym_k_raytrace.hpp"
 #include "ym_k_locate.hpp"
 #include "ym_k_segments.hpp"
+#include "ym_k_unionfind.hpp"
 #include "ym_k_segmenter.hpp"
 #include "ym_k_despeckle.hpp"
 #include "ym_k_posegraph.hpp"
