@@ -6,6 +6,13 @@
 // kernel would need for its 93 M patches per launch of 4096 items if nothing but this loop ran.
 //   variant 0: the kernel's loop (rg_gather4: four patches per trip, pairs share a funnel)
 //   variant 1: misalignment-indexed accumulator sets (no funnel in the loop), software-pipelined by the compiler
+//   variant 2: the v_perm funnel (round 4), entries read from LDS
+//   variant 3: variant 2's body with the entries in a register pair, two v_readlane per quad: the kernel's loop since round 5
+//   variant 4: variant 3 with the run's lane base and selectors carried over the loop (rg_run): per quad four vector adds
+//              with a scalar operand, a scalar class test, and variant 3's body only for a quad that straddles two runs;
+//              run by run: an outer loop per run, an inner loop of the run's quads
+//   variant 5: one loop and ONE body: a state for the quad's first pair and one for its second, each recomputed when its
+//              pair's class changes (a scalar compare of both classes at once) -- no straddling case at all
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
@@ -91,6 +98,45 @@ __device__ __forceinline__ void rg_gather4_perm(uint32_t (&acc)[8], uint32_t lan
     }
 }
 
+// variant 4: what a lane needs of the class `em` (entry & 3) of the run being gathered.  (lane_off + entry) & ~3 =
+// ((lane_off + em) & ~3) - em + entry for every entry of the class, and the funnel's byte offset is (lane_off + em) & 3.
+struct rg_run { uint32_t base, selE, selO; };
+__device__ __forceinline__ void rg_run_set(rg_run &s, uint32_t lane_off, uint32_t em) {
+    const uint32_t a = lane_off + em;
+    s.base = (a & ~3u) - em;
+    s.selE = (a & 3u) * 0x00010001u + 0x0c020c00u;
+    s.selO = s.selE + 0x00010001u;
+}
+__device__ __forceinline__ void rg_perm_pair_sel(const rg_u32x2 &pa, const rg_u32x2 &qa, const rg_u32x2 &pb, const rg_u32x2 &qb, uint32_t selE, uint32_t selO,
+                                                 uint32_t (&e)[4], uint32_t (&o)[4]) {
+    const uint32_t s0 = pa.x + pb.x, s1 = pa.y + pb.y, s2 = qa.x + qb.x, s3 = qa.y + qb.y;
+    e[0] = __builtin_amdgcn_perm(s1, s0, selE); o[0] = __builtin_amdgcn_perm(s1, s0, selO);
+    e[1] = __builtin_amdgcn_perm(s2, s1, selE); o[1] = __builtin_amdgcn_perm(s2, s1, selO);
+    e[2] = __builtin_amdgcn_perm(s3, s2, selE); o[2] = __builtin_amdgcn_perm(s3, s2, selO);
+    e[3] = __builtin_amdgcn_perm(0u, s3, selE);
+}
+__device__ __forceinline__ void rg_gather4_run(uint32_t (&acc)[8], const rg_run &s, const rg_run &t, uint32_t ex, uint32_t ey /* scalars: a pair of s's class, a pair of t's */) {
+    const uint32_t ad0 = s.base + (ex & 0xffffu), ad1 = s.base + (ex >> 16), ad2 = t.base + (ey & 0xffffu), ad3 = t.base + (ey >> 16);
+    rg_u32x2 p0, q0, p1, q1, p2, q2, p3, q3;
+    asm volatile("ds_read2_b32 %0, %8 offset1:1\n\tds_read2_b32 %1, %8 offset0:2 offset1:3\n\t"
+                 "ds_read2_b32 %2, %9 offset1:1\n\tds_read2_b32 %3, %9 offset0:2 offset1:3\n\t"
+                 "ds_read2_b32 %4, %10 offset1:1\n\tds_read2_b32 %5, %10 offset0:2 offset1:3\n\t"
+                 "ds_read2_b32 %6, %11 offset1:1\n\tds_read2_b32 %7, %11 offset0:2 offset1:3\n\t"
+                 "s_waitcnt lgkmcnt(4)"
+                 : "=&v"(p0), "=&v"(q0), "=&v"(p1), "=&v"(q1), "=&v"(p2), "=&v"(q2), "=&v"(p3), "=&v"(q3)
+                 : "v"(ad0), "v"(ad1), "v"(ad2), "v"(ad3)
+                 : "memory");
+    uint32_t e[2][4], o[2][4];
+    rg_perm_pair_sel(p0, q0, p1, q1, s.selE, s.selO, e[0], o[0]);
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(p2), "+v"(q2), "+v"(p3), "+v"(q3) : : "memory");
+    rg_perm_pair_sel(p2, q2, p3, q3, t.selE, t.selO, e[1], o[1]);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        acc[2 * j] = acc[2 * j] + e[0][j] + e[1][j];
+        if (j < 3) acc[2 * j + 1] = acc[2 * j + 1] + o[0][j] + o[1][j];
+    }
+}
+
 struct Args {
     const uint16_t *entries; // [waves in the grid][Q]: LDS offsets of patch origins, sorted by misalignment in runs of even length
     const uint16_t *runs;    // [waves in the grid][4]: first PAIR of the runs with misalignment 1, 2, 3 and the pair count
@@ -124,7 +170,61 @@ __global__ __launch_bounds__(64 * NW) void proto(Args a) {
     const int row = lane & 31, half = lane >> 5;
     const bool job = row < 26;
     const uint32_t lds0 = (uint32_t)(size_t)region;
-    if (VAR == 2) {
+    if (VAR >= 3) {
+        const uint32_t lane_off = lds0 + (uint32_t)((job ? row : 0) * RG_PITCH + half * RG_G);
+        uint32_t acc[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) acc[j] = 0u;
+        uint2 cev = make_uint2(0u, 0u); // lane i = entries 4 i .. 4 i + 3 (Q <= 256)
+        if (4 * lane < Q) cev = src[lane];
+        const int n4 = Q >> 2;
+        for (int r = 0; r < a.R; r++) {
+            if (VAR == 3) {
+                for (int c = 0; c < n4; c++)
+                    rg_gather4_perm(acc, lane_off, make_uint2(__builtin_amdgcn_readlane(cev.x, c), __builtin_amdgcn_readlane(cev.y, c)));
+            } else if (VAR == 5) {
+                constexpr uint64_t CLS = 0x0000000300000003ull;
+                uint64_t cur = ~0ull; // (no class)
+                rg_run ra = {0u, 0u, 0u}, rb = {0u, 0u, 0u};
+                for (int c = 0; c < n4; c++) {
+                    const uint32_t ex = __builtin_amdgcn_readlane(cev.x, c), ey = __builtin_amdgcn_readlane(cev.y, c);
+                    const uint64_t cls = ((uint64_t)ey << 32 | ex) & CLS;
+                    if (__builtin_expect(cls != cur, 0)) {
+                        if ((uint32_t)cls != (uint32_t)cur) rg_run_set(ra, lane_off, (uint32_t)cls);
+                        if ((uint32_t)(cls >> 32) != (uint32_t)(cur >> 32)) rg_run_set(rb, lane_off, (uint32_t)(cls >> 32));
+                        cur = cls;
+                    }
+                    rg_gather4_run(acc, ra, rb, ex, ey);
+                }
+            } else {
+                // run by run: the outer loop sets the run's state (or takes variant 3's body for a quad that straddles two runs),
+                // the inner loop is the run's quads and nothing else
+                constexpr uint64_t CLS = 0x0000000300000003ull;
+                int c = 0;
+                while (c < n4) {
+                    uint32_t ex = __builtin_amdgcn_readlane(cev.x, c), ey = __builtin_amdgcn_readlane(cev.y, c);
+                    const uint64_t cls = ((uint64_t)ey << 32 | ex) & CLS;
+                    if ((uint32_t)cls != (uint32_t)(cls >> 32)) {
+                        rg_gather4_perm(acc, lane_off, make_uint2(ex, ey));
+                        c++;
+                        continue;
+                    }
+                    rg_run run;
+                    rg_run_set(run, lane_off, (uint32_t)cls);
+                    for (;;) {
+                        rg_gather4_run(acc, run, run, ex, ey);
+                        c++; // (one exit: past the end counts as another class; lane select c & 63, whatever it reads there is not used)
+                        ex = __builtin_amdgcn_readlane(cev.x, c); ey = __builtin_amdgcn_readlane(cev.y, c);
+                        const uint64_t next = (((uint64_t)ey << 32 | ex) & CLS) | (c < n4 ? 0u : 4u);
+                        if (next != cls) break;
+                    }
+                }
+            }
+            if (a.barrier) __syncthreads();
+        }
+#pragma unroll
+        for (int j = 0; j < RG_G; j++) a.out[((size_t)gw * 64 + lane) * RG_G + j] = (acc[2 * (j >> 2) + (j & 1)] >> (16 * ((j >> 1) & 1))) & 0xffffu;
+    } else if (VAR == 2) {
         const uint32_t lane_off = lds0 + (uint32_t)((job ? row : 0) * RG_PITCH + half * RG_G);
         uint32_t acc[8];
 #pragma unroll
@@ -277,22 +377,22 @@ int main(int argc, char **argv) {
         }
         runs[(size_t)w * 4 + 3] = (uint16_t)pairs;
     }
-    uint16_t *d_ent, *d_runs; uint32_t *d_out[3];
+    uint16_t *d_ent, *d_runs; uint32_t *d_out[6];
     hipMalloc(&d_ent, ent.size() * 2); hipMalloc(&d_runs, runs.size() * 2);
     hipMemcpy(d_ent, ent.data(), ent.size() * 2, hipMemcpyHostToDevice);
     hipMemcpy(d_runs, runs.data(), runs.size() * 2, hipMemcpyHostToDevice);
     const size_t out_n = (size_t)nwaves * 64 * RG_G;
-    for (int v = 0; v < 3; v++) { hipMalloc(&d_out[v], out_n * 4); hipMemset(d_out[v], 0, out_n * 4); }
-    std::vector<uint32_t> h[3];
+    for (int v = 0; v < 6; v++) { hipMalloc(&d_out[v], out_n * 4); hipMemset(d_out[v], 0, out_n * 4); }
+    std::vector<uint32_t> h[6];
     printf("# %s, %d CUs, %d blocks of %d waves, Q = %d patches per wave and round, R = %d rounds\n", prop.gcnArchName, cus, blocks, NW, Q, R);
     printf("%-48s %10s %12s %14s\n", "variant", "blocks/CU", "us", "CU clk/patch");
     const size_t base_lds = ((RG_LDS_BYTES + 15) & ~15) + NW * 64 * 8;
-    for (int var = 0; var < 3; var++)
+    for (int var = 0; var < 6; var++)
         for (int per_cu : {3, 2})
             for (int barrier : {0, 1}) {
                 Args a{d_ent, d_runs, d_out[var], Q, R, barrier, 0};
                 const size_t lds = std::max(base_lds, (size_t)(160 * 1024 / per_cu - 1024)) ;
-                auto k = var == 0 ? proto<8, 0> : var == 1 ? proto<8, 1> : proto<8, 2>;
+                auto k = var == 0 ? proto<8, 0> : var == 1 ? proto<8, 1> : var == 2 ? proto<8, 2> : var == 3 ? proto<8, 3> : var == 4 ? proto<8, 4> : proto<8, 5>;
                 hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 hipEvent_t e0, e1;
                 hipEventCreate(&e0); hipEventCreate(&e1);
@@ -306,24 +406,29 @@ int main(int argc, char **argv) {
                 const double patches = (double)nwaves * Q * R;
                 printf("%-48s %10d %12.1f %14.2f\n", var == 0 ? (barrier ? "kernel's loop, barrier per round" : "kernel's loop") :
                        var == 2 ? (barrier ? "perm funnel + widen, barrier per round" : "perm funnel + widen") :
+                       var == 3 ? (barrier ? "perm, entries by v_readlane, barrier per round" : "perm, entries by v_readlane") :
+                       var == 4 ? (barrier ? "carried state, run by run, barrier per round" : "carried state, run by run") :
+                       var == 5 ? (barrier ? "carried state per pair slot, barrier per round" : "carried state per pair slot") :
                        (barrier ? "misalignment sets, barrier per round" : "misalignment sets"), per_cu, ms * 1e3, ms * 1e-3 * 2.4e9 * cus / patches);
                 hipEventDestroy(e0); hipEventDestroy(e1);
             }
-    for (int var = 0; var < 3; var++) { // one round: the 16-bit sums hold Q patches
+    for (int var = 0; var < 6; var++) { // one round: the 16-bit sums hold Q patches
         Args a{d_ent, d_runs, d_out[var], Q, 1, 0, 0};
-        auto k = var == 0 ? proto<8, 0> : var == 1 ? proto<8, 1> : proto<8, 2>;
+        auto k = var == 0 ? proto<8, 0> : var == 1 ? proto<8, 1> : var == 2 ? proto<8, 2> : var == 3 ? proto<8, 3> : var == 4 ? proto<8, 4> : proto<8, 5>;
         hipLaunchKernelGGL(k, dim3(blocks), dim3(64 * NW), base_lds, 0, a);
     }
     hipDeviceSynchronize();
-    for (int v = 0; v < 3; v++) { h[v].resize(out_n); hipMemcpy(h[v].data(), d_out[v], out_n * 4, hipMemcpyDeviceToHost); }
+    for (int v = 0; v < 6; v++) { h[v].resize(out_n); hipMemcpy(h[v].data(), d_out[v], out_n * 4, hipMemcpyDeviceToHost); }
     size_t bad = 0;
     for (size_t i = 0; i < out_n; i++) {
         const int lane = (int)((i / RG_G) % 64);
         if ((lane & 31) >= 26) continue;
         // (R rounds of the same patches: the 16-bit sums wrap the same way in both variants only while they do not overflow --
         //  compare modulo 2^16)
-        if ((h[0][i] & 0xffffu) != (h[1][i] & 0xffffu) || (h[0][i] & 0xffffu) != (h[2][i] & 0xffffu)) { if (bad < 5) printf("  differ at %zu: %u vs %u vs %u\n", i, h[0][i], h[1][i], h[2][i]); bad++; }
+        bool same = true;
+        for (int v = 1; v < 6; v++) same = same && (h[0][i] & 0xffffu) == (h[v][i] & 0xffffu);
+        if (!same) { if (bad < 5) printf("  differ at %zu: %u vs %u %u %u %u %u\n", i, h[0][i], h[1][i], h[2][i], h[3][i], h[4][i], h[5][i]); bad++; }
     }
-    printf("# sums of the three variants differ in %zu of %zu places\n", bad, out_n);
+    printf("# sums of the six variants differ in %zu of %zu places\n", bad, out_n);
     return 0;
 }

@@ -376,15 +376,19 @@ typedef unsigned int rg_u32x2 __attribute__((ext_vector_type(2)));
 // constant 0), (rr + 1, 0x0c, rr + 3, 0x0c) the odd ones: 14 v_perm per pair of patches instead of 8 v_alignbyte + 8 v_and +
 // 6 v_lshrrev, and the odd sums are clean 16-bit fields like the even ones.  The loop alone: 11.5 -> 10.1 CU clocks per patch
 // (scripts/exp/rg_proto.hip variant 2, profiles/r04_rg_proto.txt).
-__device__ __forceinline__ void rg_perm_pair(const rg_u32x2 &pa, const rg_u32x2 &qa, const rg_u32x2 &pb, const rg_u32x2 &qb, uint32_t rr,
-                                             uint32_t (&e)[4], uint32_t (&o)[4]) {
+__device__ __forceinline__ void rg_perm_pair_sel(const rg_u32x2 &pa, const rg_u32x2 &qa, const rg_u32x2 &pb, const rg_u32x2 &qb, uint32_t selE, uint32_t selO,
+                                                 uint32_t (&e)[4], uint32_t (&o)[4]) {
     const uint32_t s0 = pa.x + pb.x, s1 = pa.y + pb.y, s2 = qa.x + qb.x, s3 = qa.y + qb.y; // raw dwords of two patches: bytes <= 200
-    const uint32_t selE = rr * 0x00010001u + 0x0c020c00u, selO = selE + 0x00010001u;
     e[0] = __builtin_amdgcn_perm(s1, s0, selE); o[0] = __builtin_amdgcn_perm(s1, s0, selO);
     e[1] = __builtin_amdgcn_perm(s2, s1, selE); o[1] = __builtin_amdgcn_perm(s2, s1, selO);
     e[2] = __builtin_amdgcn_perm(s3, s2, selE); o[2] = __builtin_amdgcn_perm(s3, s2, selO);
     e[3] = __builtin_amdgcn_perm(0u, s3, selE); // byte 12 (the 13th hypothesis) is at most byte 15 of the four dwords
     o[3] = 0u;                                  // (acc[7] would hold hypotheses 13 and 15 of the lane: there are only 13)
+}
+__device__ __forceinline__ void rg_perm_pair(const rg_u32x2 &pa, const rg_u32x2 &qa, const rg_u32x2 &pb, const rg_u32x2 &qb, uint32_t rr,
+                                             uint32_t (&e)[4], uint32_t (&o)[4]) {
+    const uint32_t selE = rr * 0x00010001u + 0x0c020c00u, selO = selE + 0x00010001u;
+    rg_perm_pair_sel(pa, qa, pb, qb, selE, selO, e, o);
 }
 // All eight reads of the four patches are issued at once; the first pair is funnelled while the second pair's reads are
 // still in flight (LDS reads return in order: lgkmcnt(4) = the first four are back).
@@ -411,6 +415,61 @@ __device__ __forceinline__ void rg_gather4(uint32_t (&acc)[8], uint32_t lane_off
     // (the second pair's registers are written by the LDS until here: they pass through this statement and nothing else)
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(p2), "+v"(q2), "+v"(p3), "+v"(q3) : : "memory");
     rg_perm_pair(p2, q2, p3, q3, ad2 & 3u, e[1], o[1]);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        acc[2 * j] = acc[2 * j] + e[0][j] + e[1][j];
+        if (j < 3) acc[2 * j + 1] = acc[2 * j + 1] + o[0][j] + o[1][j];
+    }
+}
+
+// The gather loop's carried state (profiles/region_loop_study.md).  Of the 45 vector instructions rg_gather4 spends on a quad, 29
+// are the work (8 raw adds, 14 v_perm, 7 three-operand adds) and two fetch the entries; the other 14 -- four address adds, four
+// `& ~3`, two `& 3`, four for the selector pairs -- depend only on the lane (fixed for the kernel's life) and on the pair's class
+// em = entry & 3, and the pair lists hand a bin's entries over sorted by class, in runs of even length.  rg_run is what a lane
+// needs of a class:
+//   base   (lane_off + entry) & ~3 == ((lane_off + em) & ~3) - em + entry for EVERY entry of the class (the carry into the
+//          dword address -- the second half of a lattice row sits 13 bytes in, so its lanes carry at class 3 -- is in the first
+//          term): base + the raw entry, a scalar, is the dword below the patch's origin: one v_add with a scalar operand;
+//   selE   rg_perm_pair's even selector for rr = (lane_off + em) & 3 (the odd one is selE + 0x00010001, one v_add per pair:
+//          carrying it too spills two registers to scratch at the 80 VGPRs three blocks per CU allow).
+// The gather keeps TWO states, one for a quad's first pair and one for its second, each recomputed (five vector instructions)
+// when the class in its slot changes; whether either did is ONE scalar compare per quad of both classes at once.  A quad that
+// straddles two runs is then nothing special and the loop has ONE body.  (A bin of the metric's workload is 14 quads in 3.8 runs,
+// one quad in ten straddles.  The form with one state and rg_gather4 for the straddling quads has two bodies in the loop, and the
+// compiler joins their accumulators with five register copies per quad, or, written run by run, eight per run: it lost to the
+// old loop at 44 patches per round, scripts/exp/rg_proto.hip variant 4 against 5.)  37 vector instructions per quad instead of 45,
+// 13 scalar ones instead of 10.  rg_gather4 stays as it was for the entries past the first 256 of a wave's segment: they arrive as
+// per-lane loads, not in scalar registers, and a segment that long is rare.
+struct rg_run { uint32_t base, selE; };
+__device__ __forceinline__ void rg_run_set(rg_run &s, uint32_t lane_off, uint32_t em /* wave-uniform */) {
+    const uint32_t a = lane_off + em;
+    s.base = (a & ~3u) - em;
+    s.selE = (a & 3u) * 0x00010001u + 0x0c020c00u;
+}
+// rg_gather4 with the addresses and selectors taken from the states: ex = a pair of s's class, ey = a pair of t's (scalars).
+// The same reads, the same sums.  (The rule about asm statements that only issue reads: above rg_gather4.  Here the first pair's
+// funnel passes through the waiting statement too: that pins it between the two waits, where the second pair's reads hide it --
+// left alone, the compiler moves all of it behind the second wait.)
+__device__ __forceinline__ void rg_gather4_run(uint32_t (&acc)[8], const rg_run &s, const rg_run &t, uint32_t ex, uint32_t ey) {
+    const uint32_t ad0 = s.base + (ex & 0xffffu), ad1 = s.base + (ex >> 16), ad2 = t.base + (ey & 0xffffu), ad3 = t.base + (ey >> 16);
+#if YM_RG_ABLATE & 1
+    acc[0] += ad0 ^ ad1 ^ ad2 ^ ad3; // (the entries are still read)
+    return;
+#endif
+    rg_u32x2 p0, q0, p1, q1, p2, q2, p3, q3;
+    asm volatile("ds_read2_b32 %0, %8 offset1:1\n\tds_read2_b32 %1, %8 offset0:2 offset1:3\n\t"
+                 "ds_read2_b32 %2, %9 offset1:1\n\tds_read2_b32 %3, %9 offset0:2 offset1:3\n\t"
+                 "ds_read2_b32 %4, %10 offset1:1\n\tds_read2_b32 %5, %10 offset0:2 offset1:3\n\t"
+                 "ds_read2_b32 %6, %11 offset1:1\n\tds_read2_b32 %7, %11 offset0:2 offset1:3\n\t"
+                 "s_waitcnt lgkmcnt(4)"
+                 : "=&v"(p0), "=&v"(q0), "=&v"(p1), "=&v"(q1), "=&v"(p2), "=&v"(q2), "=&v"(p3), "=&v"(q3)
+                 : "v"(ad0), "v"(ad1), "v"(ad2), "v"(ad3)
+                 : "memory");
+    uint32_t e[2][4], o[2][4];
+    rg_perm_pair_sel(p0, q0, p1, q1, s.selE, s.selE + 0x00010001u, e[0], o[0]);
+    // (the second pair's registers are written by the LDS until here: they pass through this statement and nothing else)
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(p2), "+v"(q2), "+v"(p3), "+v"(q3), "+v"(e[0][0]), "+v"(e[0][1]), "+v"(e[0][2]), "+v"(e[0][3]), "+v"(o[0][0]), "+v"(o[0][1]), "+v"(o[0][2]) : : "memory");
+    rg_perm_pair_sel(p2, q2, p3, q3, t.selE, t.selE + 0x00010001u, e[1], o[1]);
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         acc[2 * j] = acc[2 * j] + e[0][j] + e[1][j];
@@ -629,13 +688,27 @@ __global__ __launch_bounds__(64 * NW, NW <= 8 ? (3 * NW + 3) / 4 : 1 /* three bl
 #endif
             if (lo < lds_hi) {
                 const int n4 = (lds_hi - lo) >> 2;
-                for (int c = 0; c < n4; c++) { // (c is wave-uniform: the lane select of v_readlane is a scalar register)
-                    rg_gather4(acc, lane_off, make_uint2(__builtin_amdgcn_readlane(cev.x, c), __builtin_amdgcn_readlane(cev.y, c)));
-                    in_set += 4;
+                constexpr uint64_t CLS = 0x0000000300000003ull; // the classes of a quad's two pairs (a pair shares its class)
+                uint64_t cur = ~0ull;                           // ... the ones ra and rb stand for: none yet
+                rg_run ra = {0u, 0u}, rb = {0u, 0u};
+                for (int c = 0; c < n4;) { // (c is wave-uniform: the lane select of v_readlane is a scalar register)
+                    // up to the end or to the quad that fills the set: the patches are counted per stretch, not per quad
+                    const int stop = min(n4, c + ((YM_RG_FLUSH - in_set) >> 2));
+                    in_set += 4 * (stop - c);
+                    for (; c < stop; c++) {
+                        const uint32_t ex = __builtin_amdgcn_readlane(cev.x, c), ey = __builtin_amdgcn_readlane(cev.y, c);
+                        const uint64_t cls = ((uint64_t)ey << 32 | ex) & CLS;
+                        if (__builtin_expect(cls != cur, 0)) { // at most four times per slot and bin
+                            if ((uint32_t)cls != (uint32_t)cur) rg_run_set(ra, lane_off, (uint32_t)cls);
+                            if ((uint32_t)(cls >> 32) != (uint32_t)(cur >> 32)) rg_run_set(rb, lane_off, (uint32_t)(cls >> 32));
+                        }
+                        cur = cls; // (outside the branch: the registers of cls become those of cur, no copy on the likely path)
+                        rg_gather4_run(acc, ra, rb, ex, ey);
+                    }
                     if (in_set == YM_RG_FLUSH) flush();
                 }
             }
-            for (int c = lds_hi; c < hi; c += 4) { // (a very long segment)
+            for (int c = lds_hi; c < hi; c += 4) { // (a very long segment: per-lane loads, not scalars -- the old function)
                 rg_gather4(acc, lane_off, entries4[c >> 2]);
                 in_set += 4;
                 if (in_set == YM_RG_FLUSH) flush();
