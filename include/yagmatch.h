@@ -279,6 +279,42 @@ ym_map *ym_map_create_empty(ym_matcher *m, int width, int height);
 int ym_map_add_scans(ym_matcher *m, ym_map *map, double ox, double oy, const ym_scan *const *scans, int n_scans,
                      ym_map_add_stats *stats /* or null */);
 int ym_map_clear(ym_matcher *m, ym_map *map);
+/* ---- maps that forget.  A maximum cannot be undone, so a map that is to let scans go keeps counts.
+ *   ym_map_create_counted  an empty map like ym_map_create_empty's (the same size limits, YM_SEM_YAGPY only) that also holds
+ *                        uint32 stamps[height][width], the number of readings currently stamped in each cell, and whose origin
+ *                        (ox, oy) -- the world position of cell (0, 0) -- is fixed here.  Standing invariant: the float grid and the
+ *                        bytes are what ym_map_from_occupancy makes of the image stamps > 0, bit for bit.  The maps of the other three
+ *                        creators are not counted and behave as before.
+ *   on a counted map     ym_map_add_scans also adds 1 to the count of every stamped reading's cell; ox, oy other than the map's give
+ *                        YM_ERR_INVALID and change nothing.  ym_map_clear zeroes the counts too.
+ *   ym_map_update_scans  takes remove[i] out at remove_poses[i] -- the pose it was ADDED at, which need not be its current one
+ *                        (ym_occmap_accumulate takes poses the same way) -- and then adds add[j] at its current pose; a scan in both
+ *                        lists is moved.  A removed reading takes its cell's count down by one; the cells whose count reaches zero are
+ *                        released, and exactly the cells within the taps' reach of a released cell are recomputed from the counts (the
+ *                        largest tap over the stamped cells that reach them, 1.0 on a stamped cell), after the added readings are in.
+ *                        Everything else is left as it is: the call costs what the released cells reach, not what the map holds.  A
+ *                        removed reading outside the map is dropped, as it was when it was added.  One that meets a count of zero --
+ *                        the scan was not added at that pose: the caller's error -- changes nothing and is counted in
+ *                        stats->unmatched; no count ever goes below zero and the invariant holds whatever is removed.  Runs on the
+ *                        matcher's stream, synchronous, never throws; both forms of the map are current on return.  Either list
+ *                        may be empty (its pointers may then be null).
+ *   ym_map_counted       1 for a counted map, else 0 (a null map: 0).
+ *   ym_map_read_stamps   the counts, width * height entries (a test hook).
+ * YM_ERR_INVALID: a null argument, a negative count, a null scan, a scan or a map on another device than the matcher.
+ * YM_ERR_UNSUPPORTED: a map that is not counted, a matcher that is not YM_SEM_YAGPY, taps so wide that a 64 x 4 tile with their
+ * reach around it exceeds 64 KiB of LDS (more than 221 x 221; removal only).  A refused call changes nothing. */
+typedef struct ym_map_update_stats {
+    int64_t removed, added;   /* readings taken out of and stamped into the map */
+    int64_t dropped;          /* readings of either list outside the map */
+    int64_t unmatched;        /* removed readings that met a count of zero */
+    int64_t released, gained; /* cells whose count fell to zero, cells whose count rose from zero */
+    int32_t x0, y0, x1, y1;   /* cells changed lie inside [x0, x1) x [y0, y1); empty: all 0 */
+} ym_map_update_stats;
+ym_map *ym_map_create_counted(ym_matcher *m, int width, int height, double ox, double oy);
+int ym_map_update_scans(ym_matcher *m, ym_map *map, const ym_scan *const *remove, const double *remove_poses /* [n_remove][3] */,
+                        int n_remove, const ym_scan *const *add, int n_add, ym_map_update_stats *stats /* or null */);
+int ym_map_counted(const ym_map *map);
+int ym_map_read_stamps(const ym_map *map, uint32_t *out, int64_t out_count);
 /* one find_best_pose_non_symmetric pass (/root/reference/yag_slam/helpers.py:434-573) */
 typedef struct ym_map_search {
     double xy_search, xy_step;       /* +- metres around the centre, lattice step */

@@ -86,6 +86,10 @@ static int map_clear(ym_matcher *m, ym_map *mp) {
     const size_t n = (size_t)mp->width * mp->height;
     hipLaunchKernelGGL(ym::map_clear_kernel, dim3((unsigned)((n + 2047) / 2048)), dim3(256), 0, m->stream, mp->d_cgrid.p, mp->d_g8.p, n);
     HIP_TRY(hipGetLastError());
+    if (mp->counted) { // (the flags are zero between calls; a call that failed half way may have left some)
+        HIP_TRY(hipMemsetAsync(mp->d_stamps.p, 0, n * sizeof(uint32_t), m->stream));
+        HIP_TRY(hipMemsetAsync(mp->d_dirty.p, 0, n, m->stream));
+    }
     HIP_TRY(hipStreamSynchronize(m->stream));
     return YM_OK;
 }
@@ -96,6 +100,31 @@ ym_map *ym_map_create_empty(ym_matcher *m, int width, int height) {
     if (!mp) return nullptr;
     if (map_clear(m, mp) != YM_OK) { delete mp; return nullptr; } // (the error text is set)
     return mp;
+}
+
+ym_map *ym_map_create_counted(ym_matcher *m, int width, int height, double ox, double oy) {
+    DevGuard guard(m ? m->device : 0);
+    ym_map *mp = map_alloc(m, width, height);
+    if (!mp) return nullptr;
+    const size_t n = (size_t)width * height;
+    mp->counted = true; mp->ox = ox; mp->oy = oy;
+    if (mp->d_stamps.alloc(n) != YM_OK || mp->d_dirty.alloc(n) != YM_OK || map_clear(m, mp) != YM_OK) { // (the error text is set)
+        delete mp;
+        return nullptr;
+    }
+    return mp;
+}
+
+int ym_map_counted(const ym_map *mp) { return mp && mp->counted ? 1 : 0; }
+
+int ym_map_read_stamps(const ym_map *mp, uint32_t *out, int64_t out_count) {
+    if (!mp || !out) return set_err(YM_ERR_INVALID, "null argument");
+    if (!mp->counted) return set_err(YM_ERR_UNSUPPORTED, "this map keeps no counts: use ym_map_create_counted");
+    const size_t n = (size_t)mp->width * mp->height;
+    if (out_count < 0 || (size_t)out_count < n) return set_err(YM_ERR_INVALID, "buffer too small: need %zu entries", n);
+    DEV_GUARD(mp->device);
+    HIP_TRY(hipMemcpy(out, mp->d_stamps.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return YM_OK;
 }
 
 int ym_map_clear(ym_matcher *m, ym_map *mp) {
@@ -109,11 +138,151 @@ int ym_map_clear(ym_matcher *m, ym_map *mp) {
 // scans of one launch: the cells of every beam take 4 bytes, grid.y stays far below its limit
 static const int kMapGrowChunk = 4096;
 
+// A counted map's one way to change (ym_map_update_scans, and ym_map_add_scans with nothing to remove): `remove` out at remove_poses,
+// `add` in at the scans' own poses.  The caller has checked m, mp, the semantics and the map's device.
+static int map_update(ym_matcher *m, ym_map *mp, const ym_scan *const *remove, const double *remove_poses, int n_remove,
+                      const ym_scan *const *add, int n_add, ym_map_update_stats *stats) {
+    int max_n = 1;
+    size_t remove_beams = 0;
+    for (int i = 0; i < n_remove; i++) {
+        if (!remove[i] || remove[i]->device != m->device) return set_err(YM_ERR_INVALID, "removed scan %d is null or lives on another device", i);
+        max_n = std::max(max_n, remove[i]->n);
+        remove_beams += (size_t)remove[i]->n;
+    }
+    for (int i = 0; i < n_add; i++) {
+        if (!add[i] || add[i]->device != m->device) return set_err(YM_ERR_INVALID, "scan %d is null or lives on another device", i);
+        max_n = std::max(max_n, add[i]->n);
+    }
+    ym_map_update_stats s;
+    std::memset(&s, 0, sizeof s);
+    if (n_remove == 0 && n_add == 0) {
+        if (stats) *stats = s;
+        return YM_OK;
+    }
+    const int ks = 2 * m->geom.half_kernel + 1, half = m->geom.half_kernel;
+    if ((double)max_n * ks * ks > 2.0e9) return set_err(YM_ERR_UNSUPPORTED, "%d beams x %d x %d taps: more than one launch holds", max_n, ks, ks);
+    const size_t halo_bytes = (size_t)(ym::kMfTileW + ks - 1) * (size_t)(ym::kMfTileH + ks - 1);
+    if (n_remove > 0 && halo_bytes > 65536)
+        return set_err(YM_ERR_UNSUPPORTED, "%d x %d taps: the recompute's tile and halo (%zu bytes) do not fit 64 KiB of LDS", ks, ks, halo_bytes);
+    DEV_GUARD(m->device);
+    hipStream_t st = m->stream;
+    const size_t n_cells = (size_t)mp->width * mp->height;
+    const int chunk = std::min(std::max(n_remove, n_add), kMapGrowChunk);
+    enum { kRem = 0, kAdd = ym::kMgStatSlots, kUpd = 2 * ym::kMgStatSlots, kSlots = 2 * ym::kMgStatSlots + ym::kMuStatSlots };
+    int rc;
+    if ((rc = m->grow_scans.ensure((size_t)chunk)) || (rc = m->grow_cells.ensure((size_t)chunk * max_n)) ||
+        (rc = m->grow_stats.ensure(kSlots)) || (rc = m->kernel_f_dev.ensure(m->kernel_f.size())) ||
+        (rc = m->grow_released.ensure(std::min(remove_beams, n_cells))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(m->kernel_f_dev.p, m->kernel_f.data(), m->kernel_f.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    // (what the copies of this call read on the host -- `init`, `all` -- stays as it is until the wait at the end)
+    unsigned long long init[kSlots], got[kSlots];
+    for (int i = 0; i < kSlots; i++) init[i] = 0;
+    init[kRem + ym::kMgX0] = init[kRem + ym::kMgY0] = init[kAdd + ym::kMgX0] = init[kAdd + ym::kMgY0] = ~0ull;
+    init[kUpd + ym::kMuX0] = init[kUpd + ym::kMuY0] = ~0ull;
+    HIP_TRY(hipMemcpyAsync(m->grow_stats.p, init, sizeof init, hipMemcpyHostToDevice, st));
+    std::vector<YmScanRef> all((size_t)n_remove + (size_t)n_add);
+    ym::MapGrowArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.scans = m->grow_scans.p; a.max_n = max_n; a.width = mp->width; a.height = mp->height;
+    a.ox = mp->ox; a.oy = mp->oy; a.res = m->cfg.resolution;
+    a.cells = m->grow_cells.p; a.kernel = m->kernel_f_dev.p; a.ksize = ks;
+    a.cgrid = mp->d_cgrid.p; a.g8 = mp->d_g8.p;
+    ym::MapForgetArgs f;
+    std::memset(&f, 0, sizeof f);
+    f.cells = m->grow_cells.p; f.max_n = max_n; f.width = mp->width; f.height = mp->height;
+    f.stamps = mp->d_stamps.p; f.released = m->grow_released.p; f.stats = m->grow_stats.p + kUpd; f.dirty = mp->d_dirty.p;
+    f.kernel = m->kernel_f_dev.p; f.ksize = ks; f.cgrid = mp->d_cgrid.p; f.g8 = mp->d_g8.p;
+    const dim3 beams((unsigned)((max_n + 255) / 256)), taps((unsigned)(((size_t)max_n * ks * ks + 255) / 256));
+    // the removes first, all of them: a count falls to zero at most once in a call
+    a.stats = m->grow_stats.p + kRem;
+    for (int c0 = 0; c0 < n_remove; c0 += chunk) {
+        const int B = std::min(chunk, n_remove - c0);
+        YmScanRef *hs = all.data() + c0;
+        for (int i = 0; i < B; i++) hs[i] = scan_ref(remove[c0 + i], remove_poses + 3 * (size_t)(c0 + i));
+        HIP_TRY(hipMemcpyAsync(m->grow_scans.p, hs, sizeof(YmScanRef) * (size_t)B, hipMemcpyHostToDevice, st));
+        a.n_scans = B;
+        hipLaunchKernelGGL(ym::map_grow_cells_kernel, dim3(B), dim3(1024), 0, st, a);
+        hipLaunchKernelGGL(ym::map_count_kernel<true>, dim3(beams.x, B), dim3(256), 0, st, f);
+        HIP_TRY(hipGetLastError());
+    }
+    a.stats = m->grow_stats.p + kAdd;
+    for (int c0 = 0; c0 < n_add; c0 += chunk) {
+        const int B = std::min(chunk, n_add - c0);
+        YmScanRef *hs = all.data() + n_remove + c0;
+        for (int i = 0; i < B; i++) hs[i] = scan_ref(add[c0 + i]);
+        HIP_TRY(hipMemcpyAsync(m->grow_scans.p, hs, sizeof(YmScanRef) * (size_t)B, hipMemcpyHostToDevice, st));
+        a.n_scans = B;
+        hipLaunchKernelGGL(ym::map_grow_cells_kernel, dim3(B), dim3(1024), 0, st, a);
+        hipLaunchKernelGGL(ym::map_count_kernel<false>, dim3(beams.x, B), dim3(256), 0, st, f);
+        hipLaunchKernelGGL(ym::map_grow_smear_kernel<false>, dim3(taps.x, B), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(ym::map_grow_smear_kernel<true>, dim3(taps.x, B), dim3(256), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(got, m->grow_stats.p, sizeof got, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const unsigned long long *gr = got + kRem, *ga = got + kAdd, *gu = got + kUpd;
+    s.unmatched = (int64_t)gu[ym::kMuUnmatched]; s.released = (int64_t)gu[ym::kMuReleased]; s.gained = (int64_t)gu[ym::kMuGained];
+    s.removed = (int64_t)gr[ym::kMgStamped] - s.unmatched; s.added = (int64_t)ga[ym::kMgStamped];
+    s.dropped = (int64_t)gr[ym::kMgDropped] + (int64_t)ga[ym::kMgDropped];
+    int x0 = INT32_MAX, y0 = INT32_MAX, x1 = 0, y1 = 0; // the changed cells' box: both boxes widened by the taps' reach and cut to the map
+    if (s.added > 0) {
+        x0 = std::max(0, (int)ga[ym::kMgX0] - half); y0 = std::max(0, (int)ga[ym::kMgY0] - half);
+        x1 = std::min(mp->width, (int)ga[ym::kMgX1] + half + 1); y1 = std::min(mp->height, (int)ga[ym::kMgY1] + half + 1);
+    }
+    if (s.released > 0) {
+        // the recompute: a launch of its own after the smear's atomics, so the counts and the cells it reads are complete
+        const int rx0 = std::max(0, (int)gu[ym::kMuX0] - half), ry0 = std::max(0, (int)gu[ym::kMuY0] - half);
+        const int rx1 = std::min(mp->width, (int)gu[ym::kMuX1] + half + 1), ry1 = std::min(mp->height, (int)gu[ym::kMuY1] + half + 1);
+        const int piece = (int)(2147483647u / (unsigned)(ks * ks)); // released cells of one mark launch
+        for (int64_t r0 = 0; r0 < s.released; r0 += piece) {
+            f.first = (int)r0; f.count = (int)std::min<int64_t>(piece, s.released - r0);
+            hipLaunchKernelGGL(ym::map_forget_mark_kernel, dim3((unsigned)(((size_t)f.count * ks * ks + 255) / 256)), dim3(256), 0, st, f);
+        }
+        f.bx0 = rx0 / ym::kMfTileW * ym::kMfTileW; f.by0 = ry0 / ym::kMfTileH * ym::kMfTileH; f.bx1 = rx1; f.by1 = ry1;
+        const dim3 tiles((unsigned)((f.bx1 - f.bx0 + ym::kMfTileW - 1) / ym::kMfTileW), (unsigned)((f.by1 - f.by0 + ym::kMfTileH - 1) / ym::kMfTileH));
+        for (unsigned ty = 0; ty < tiles.y; ty += 65535u) { // (a launch has at most 65535 rows of blocks)
+            ym::MapForgetArgs g = f;
+            g.by0 = f.by0 + (int)ty * ym::kMfTileH;
+            hipLaunchKernelGGL(ym::map_forget_gather_kernel, dim3(tiles.x, std::min(65535u, tiles.y - ty)), dim3(256), halo_bytes, st, g);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        x0 = std::min(x0, rx0); y0 = std::min(y0, ry0); x1 = std::max(x1, rx1); y1 = std::max(y1, ry1);
+    }
+    if (x1 > x0 && y1 > y0) { s.x0 = x0; s.y0 = y0; s.x1 = x1; s.y1 = y1; }
+    if (stats) *stats = s;
+    return YM_OK;
+}
+
+int ym_map_update_scans(ym_matcher *m, ym_map *mp, const ym_scan *const *remove, const double *remove_poses, int n_remove,
+                        const ym_scan *const *add, int n_add, ym_map_update_stats *stats) {
+    if (!m || !mp || (n_remove != 0 && (!remove || !remove_poses)) || (n_add != 0 && !add)) return set_err(YM_ERR_INVALID, "null argument");
+    if (n_remove < 0 || n_add < 0) return set_err(YM_ERR_INVALID, "n_remove and n_add must not be negative");
+    if (m->cfg.semantics != YM_SEM_YAGPY) return set_err(YM_ERR_UNSUPPORTED, "ym_map_update_scans needs a YM_SEM_YAGPY matcher");
+    if (mp->device != m->device) return set_err(YM_ERR_INVALID, "map lives on another device");
+    if (!mp->counted) return set_err(YM_ERR_UNSUPPORTED, "this map keeps no counts and cannot forget: use ym_map_create_counted");
+    return map_update(m, mp, remove, remove_poses, n_remove, add, n_add, stats);
+}
+
 int ym_map_add_scans(ym_matcher *m, ym_map *mp, double ox, double oy, const ym_scan *const *scans, int n_scans, ym_map_add_stats *stats) {
     if (!m || !mp || (!scans && n_scans != 0)) return set_err(YM_ERR_INVALID, "null argument");
     if (m->cfg.semantics != YM_SEM_YAGPY) return set_err(YM_ERR_UNSUPPORTED, "ym_map_add_scans needs a YM_SEM_YAGPY matcher");
     if (n_scans < 0) return set_err(YM_ERR_INVALID, "n_scans must not be negative");
     if (mp->device != m->device) return set_err(YM_ERR_INVALID, "map lives on another device");
+    if (mp->counted) { // the counts go up with the stamps
+        if (!(ox == mp->ox && oy == mp->oy))
+            return set_err(YM_ERR_INVALID, "a counted map keeps the origin it was created with (%.17g, %.17g)", mp->ox, mp->oy);
+        ym_map_update_stats u;
+        int rc;
+        if ((rc = map_update(m, mp, nullptr, nullptr, 0, scans, n_scans, &u))) return rc;
+        if (stats) {
+            std::memset(stats, 0, sizeof *stats);
+            stats->points = u.added + u.dropped; stats->stamped = u.added; stats->dropped = u.dropped;
+            stats->x0 = u.x0; stats->y0 = u.y0; stats->x1 = u.x1; stats->y1 = u.y1;
+        }
+        return YM_OK;
+    }
     int max_n = 1;
     for (int i = 0; i < n_scans; i++) {
         if (!scans[i] || scans[i]->device != m->device) return set_err(YM_ERR_INVALID, "scan %d is null or lives on another device", i);

@@ -5,6 +5,11 @@ struct ym_map {
     int width, height;
     DevBuf<double> d_cgrid;  // the float correlation grid as the reference holds it
     DevBuf<uint8_t> d_g8;    // int(100 * cell): what scoring reads (+ 64 bytes)
+    // ym_map_create_counted only: the origin is fixed, and both forms above are a function of stamps > 0
+    bool counted = false;
+    double ox = 0, oy = 0;
+    DevBuf<uint32_t> d_stamps; // readings stamped per cell
+    DevBuf<uint8_t> d_dirty;   // all zero between calls: the cells a removal has to recompute
 };
 
 struct ym_occupancy {
@@ -64,6 +69,7 @@ struct ym_matcher {
     DevBuf<YmScanRef> grow_scans; // ym_map_add_scans: the scans of one chunk, ...
     DevBuf<int32_t> grow_cells;   // ... the cell of every beam (ym_k_mapgrow.hpp) ...
     DevBuf<unsigned long long> grow_stats; // ... and the counts and the box of the call
+    DevBuf<int32_t> grow_released; // ym_map_update_scans: the cells whose count fell to zero
     int z2max = 0;               // largest squared cell distance whose kernel value is 100
     DevBuf<uint8_t> ktab;
     DevBuf<uint8_t> rowtab;   // the raster's row-pass tables (upload_lut)

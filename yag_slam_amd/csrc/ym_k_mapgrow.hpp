@@ -1,5 +1,6 @@
-// ym_k_mapgrow.hpp -- a resident correlation map that takes scans: map_grow_cells_kernel, map_grow_smear_kernel, map_clear_kernel.
-// Part of ym_kernels.hpp (include that, not this file).  DESIGN.md section 15.
+// ym_k_mapgrow.hpp -- a resident correlation map that takes scans: map_grow_cells_kernel, map_grow_smear_kernel, map_clear_kernel;
+// and one that lets them go again: map_count_kernel, map_forget_mark_kernel, map_forget_gather_kernel.
+// Part of ym_kernels.hpp (include that, not this file).  DESIGN.md sections 15 and 16.
 #pragma once
 
 namespace ym {
@@ -126,6 +127,138 @@ __global__ __launch_bounds__(256) void map_clear_kernel(double *cgrid, uint8_t *
     } else {
         for (size_t i = i0; i < n; i++) { cgrid[i] = 0.0; g8[i] = 0; }
     }
+}
+
+// ---- counted maps: a map that can forget
+// A counted map keeps stamps[height][width], the number of readings stamped in each cell, and the invariant that cgrid and g8 are what
+// map_from_occupancy_kernel makes of the image stamps > 0.  Adding keeps it as above (the smear is that kernel's scatter form, section 15).
+// Removing takes the counts down and then recomputes, by that kernel's gather, exactly the cells within reach of a cell whose count fell
+// to zero:
+//   count   one lane per beam, on the cells map_grow_cells_kernel left.  REMOVE: an atomic subtraction; a reading that meets a
+//           count of zero puts its one back and is counted as unmatched (the caller named a pose the scan was not added at); the lane
+//           that takes a count to zero appends the cell to `released` and widens the released box.  Removes of a call run before its adds,
+//           so a count reaches zero at most once per call and `released` holds no cell twice.  Add: an atomic add; a cell whose count
+//           was already positive has its taps in the map (the invariant, or the lane of this launch that found zero), so its entry in
+//           `cells` is struck out and the smear skips it.
+//   mark    one lane per (released cell, tap): the byte dirty[target] = 1 (lanes that share a target store the same value)
+//   gather  64 x 4 tiles over the released box widened by the taps' reach.  A tile without a dirty cell leaves; the others stage
+//           stamps > 0 of the tile and its halo in LDS, and every dirty cell takes the maximum of kernel[sy][sx] over the stamped cells
+//           that reach it -- map_from_occupancy_kernel's loop on the same table --, writes both forms and clears its flag.
+//           It runs after the smear of the same call: the counts it reads hold what that call added.
+enum { kMuUnmatched = 0, kMuReleased, kMuGained, kMuX0, kMuY0, kMuX1, kMuY1, kMuStatSlots };
+enum { kMfTileW = 64, kMfTileH = 4 };
+
+struct MapForgetArgs {
+    int32_t *cells;             // [n_scans][max_n] what map_grow_cells_kernel wrote
+    int32_t max_n;
+    int32_t width, height;
+    uint32_t *stamps;           // [height][width] readings stamped per cell
+    int32_t *released;          // cells whose count fell to zero in this call; stats[kMuReleased] is its cursor
+    unsigned long long *stats;  // [kMuStatSlots]; X0, Y0 start at the largest value, the rest at 0
+    uint8_t *dirty;             // [height][width] 1: within reach of a released cell
+    const double *kernel;       // [ksize][ksize]
+    int32_t ksize;
+    int32_t first, count;       // mark: released[first .. first + count)
+    int32_t bx0, by0, bx1, by1; // gather: the cells [bx0, bx1) x [by0, by1); bx0, by0 multiples of the tile
+    double *cgrid;
+    uint8_t *g8;
+};
+
+// grid (ceil(max_n / 256), n_scans), 256 threads
+template <bool REMOVE>
+__global__ __launch_bounds__(256) void map_count_kernel(MapForgetArgs a) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    int32_t *slot = a.cells + (size_t)blockIdx.y * a.max_n + p;
+    const int cell = p < a.max_n ? *slot : -1;
+    const int lane = threadIdx.x & 63;
+    if (REMOVE) {
+        bool unmatched = false, released = false;
+        if (cell >= 0) {
+            // One hardware atomic per reading: a compare-and-swap loop took 110 ms to move 2000 scans of a hall at 0.05 m, where
+            // hundreds of readings share a cell, and this form 3.7 ms (profiles/map_forget_time.json).  Read as an int32, the count a decrement finds is positive
+            // exactly as often as the cell held readings: the decrements that find less put their one back, so the value never exceeds
+            // what is truly left, and the first of them comes only when nothing is left.  Exactly one decrement finds 1.
+            const int old = (int)atomicSub(&a.stamps[cell], 1u);
+            if (old <= 0) { atomicAdd(&a.stamps[cell], 1u); unmatched = true; }
+            released = old == 1;
+        }
+        const unsigned long long mu = __ballot(unmatched), mr = __ballot(released);
+        int x0 = INT32_MAX, y0 = INT32_MAX, x1 = -1, y1 = -1;
+        if (released) { y0 = y1 = cell / a.width; x0 = x1 = cell - y0 * a.width; }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            x0 = min(x0, __shfl_xor(x0, d)); y0 = min(y0, __shfl_xor(y0, d));
+            x1 = max(x1, __shfl_xor(x1, d)); y1 = max(y1, __shfl_xor(y1, d));
+        }
+        unsigned long long base = 0;
+        if (lane == 0) {
+            if (mu) atomicAdd(&a.stats[kMuUnmatched], (unsigned long long)__popcll(mu));
+            if (mr) {
+                base = atomicAdd(&a.stats[kMuReleased], (unsigned long long)__popcll(mr));
+                atomicMin(&a.stats[kMuX0], (unsigned long long)x0); atomicMin(&a.stats[kMuY0], (unsigned long long)y0);
+                atomicMax(&a.stats[kMuX1], (unsigned long long)x1); atomicMax(&a.stats[kMuY1], (unsigned long long)y1);
+            }
+        }
+        base = __shfl(base, 0);
+        // (the list has room for every cell of the map, and no cell is released twice in a call)
+        if (released) a.released[base + (unsigned long long)__popcll(mr & ((1ull << lane) - 1ull))] = cell;
+    } else {
+        bool gained = false;
+        if (cell >= 0) {
+            gained = atomicAdd(&a.stamps[cell], 1u) == 0u; // (2^32 readings in one cell are out of reach: a call holds fewer)
+            if (!gained) *slot = -1;
+        }
+        const unsigned long long mg = __ballot(gained);
+        if (lane == 0 && mg) atomicAdd(&a.stats[kMuGained], (unsigned long long)__popcll(mg));
+    }
+}
+
+// grid (ceil(count * ksize^2 / 256)), 256 threads (count * ksize^2 is below 2^31: the host cuts the list)
+__global__ __launch_bounds__(256) void map_forget_mark_kernel(MapForgetArgs a) {
+    const int kk = a.ksize * a.ksize, half = a.ksize / 2;
+    const unsigned idx = blockIdx.x * 256u + threadIdx.x;
+    const int r = (int)(idx / (unsigned)kk), t = (int)(idx - (unsigned)r * (unsigned)kk);
+    if (r >= a.count) return;
+    const int cell = a.released[(size_t)a.first + r];
+    const int sy = t / a.ksize, sx = t - sy * a.ksize;
+    const int gy = cell / a.width, gx = cell - gy * a.width;
+    const int x = gx + (sx - half), y = gy + (sy - half);
+    if (x < 0 || x >= a.width || y < 0 || y >= a.height) return;
+    a.dirty[(size_t)y * a.width + x] = 1;
+}
+
+// grid (ceil((bx1 - bx0) / 64), ceil((by1 - by0) / 4)), 256 threads, (64 + ksize - 1) * (4 + ksize - 1) bytes of dynamic LDS
+__global__ __launch_bounds__(256) void map_forget_gather_kernel(MapForgetArgs a) {
+    extern __shared__ uint8_t s_occ[]; // [4 + 2 half][64 + 2 half] stamps > 0, zero outside the map
+    const int half = a.ksize / 2, tw = kMfTileW + 2 * half, th = kMfTileH + 2 * half;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int x = a.bx0 + blockIdx.x * kMfTileW + tx, y = a.by0 + blockIdx.y * kMfTileH + ty;
+    const size_t c = (size_t)y * a.width + x;
+    const bool dirty = x < a.bx1 && y < a.by1 && a.dirty[c] != 0; // (bx1 <= width, by1 <= height)
+    if (!__syncthreads_or(dirty)) return;
+    const int hx0 = x - tx - half, hy0 = y - ty - half;
+    for (int i = threadIdx.x; i < tw * th; i += 256) {
+        const int ly = i / tw, lx = i - ly * tw;
+        const int gx = hx0 + lx, gy = hy0 + ly;
+        s_occ[i] = (gx >= 0 && gx < a.width && gy >= 0 && gy < a.height && a.stamps[(size_t)gy * a.width + gx] > 0u) ? 1 : 0;
+    }
+    __syncthreads();
+    if (!dirty) return;
+    const uint8_t *centre = s_occ + (ty + half) * tw + (tx + half);
+    double v = 0.0;
+    for (int sy = 0; sy < a.ksize; sy++) {
+        const uint8_t *row = centre - (sy - half) * tw; // the stamped points that reach (x, y) through the taps of row sy
+        for (int sx = 0; sx < a.ksize; sx++) {
+            if (row[-(sx - half)]) {
+                const double cand = a.kernel[sy * a.ksize + sx];
+                v = cand > v ? cand : v;
+            }
+        }
+    }
+    if (*centre) v = 1.0 > v ? 1.0 : v;
+    a.cgrid[c] = v;
+    a.g8[c] = (uint8_t)(int)(100 * v);
+    a.dirty[c] = 0;
 }
 
 }  // namespace ym

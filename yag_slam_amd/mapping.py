@@ -423,21 +423,46 @@ class MapBuilder(object):
     one of the two -- the ROS node's keyframe rule (slam_node_ros1:299-301) negated.  A step whose correction was not applied
     is never added: its pose is dead reckoning.
 
-    `last` is the last scan processed, `last_added` the last one added, `added` every scan in the map (in order), `lost` the
-    number of consecutive steps whose correction was not applied, `results` every step's result."""
+    window=N (None: no limit) keeps a rolling local map, the resident counterpart of the reference's `running_scans` buffer: at
+    most N keyframes stay in the map, and adding one more takes the oldest out in the same library call
+    (`CorrelationMap.update_scans`).  That needs a map that can forget, a counted one
+    (`matcher.empty_correlation_map(w, h, counted=True, ox=ox, oy=oy)`), which the builder then owns: it
+    holds the builder's keyframes and nothing else.
 
-    def __init__(self, matcher, cmap, ox, oy, coarse=None, min_response=0.0, min_distance=0.0, min_rotation=0.0):
+    `last` is the last scan processed, `last_added` the last one added, `added` every scan in the map (in order), `dropped`
+    the scans the window has taken out again (in order), `lost` the number of consecutive steps whose correction was not
+    applied, `results` every step's result."""
+
+    # rebuild() on a counted map: above this share of moved keyframes the map is cleared and filled again.  Measured with 2000
+    # scans of 1081 beams (DESIGN.md section 16, profiles/map_forget_time.json): with 5 x 5 taps moving costs as much as clearing
+    # and adding all at a share of 0.2, with 29 x 29 taps only at 1.0 (there a builder may set its REBUILD_SHARE to 1.0).
+    REBUILD_SHARE = 0.2
+
+    def __init__(self, matcher, cmap, ox, oy, coarse=None, min_response=0.0, min_distance=0.0, min_rotation=0.0, window=None):
+        if window is not None:
+            if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+                raise ValueError("MapBuilder: window %r: None or an integer of at least 1" % (window,))
+            if not getattr(cmap, "counted", False):
+                raise ValueError("MapBuilder: a window needs a map that can forget: "
+                                 "matcher.empty_correlation_map(w, h, counted=True, ox=ox, oy=oy)")
         self.matcher, self.cmap, self.ox, self.oy = matcher, cmap, ox, oy
         self.coarse, self.min_response = coarse, min_response
         self.min_distance, self.min_rotation = min_distance, min_rotation
+        self.window = window
         self.last = None
         self.last_added = None
         self.added = []
+        self.dropped = []
         self.lost = 0
         self.results = []
 
     def _add(self, scan):
-        stats = self.cmap.add_scans(self.ox, self.oy, [scan])
+        if self.window is not None and len(self.added) >= self.window:
+            oldest = self.added[0]
+            stats = self.cmap.update_scans([oldest], [scan])  # (MapUpdateStats)
+            self.dropped.append(self.added.pop(0))
+        else:
+            stats = self.cmap.add_scans(self.ox, self.oy, [scan])
         self.added.append(scan)
         self.last_added = scan
         return stats
@@ -488,7 +513,13 @@ class MapBuilder(object):
         return out
 
     def rebuild(self):
-        """Clear the map and add every scan of `added` at its current pose, in one library call: after an optimiser moved
-        them (a maximum cannot be undone scan by scan).  Returns the add's MapAddStats."""
+        """Bring the map to the current poses of `added`, after an optimiser moved them.  A map that keeps no counts is cleared
+        and every scan of `added` added again, in one library call (a maximum cannot be undone scan by scan); returns the
+        add's MapAddStats.  A counted map moves the scans whose pose changed (`CorrelationMap.sync`, MapUpdateStats), which
+        costs what moved; when more than REBUILD_SHARE of them moved it is cleared and filled like the other."""
+        if getattr(self.cmap, "counted", False):
+            moved = self.cmap.moved_scans(self.added)
+            if len(moved) <= self.REBUILD_SHARE * len(self.added):
+                return self.cmap.sync(moved)  # (the poses of the others have been compared once: 0.6 ms for 2000 scans)
         self.cmap.clear()
         return self.cmap.add_scans(self.ox, self.oy, list(self.added))

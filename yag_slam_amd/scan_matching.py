@@ -371,12 +371,21 @@ class ScanMatcher(object):
             raise _capi.YmError(-1, _capi.last_error())
         return CorrelationMap(self, h)
 
-    def empty_correlation_map(self, width, height):
-        """A resident CorrelationMap of `height` x `width` zeros, to be filled with `CorrelationMap.add_scans`."""
-        h = self._lib.ym_map_create_empty(self._m, int(width), int(height))
+    def empty_correlation_map(self, width, height, counted=False, ox=None, oy=None):
+        """A resident CorrelationMap of `height` x `width` zeros, to be filled with `CorrelationMap.add_scans`.
+        counted=True (`ym_map_create_counted`): the map also counts the readings stamped in each cell, so that scans can be
+        taken out again (`remove_scans`, `sync`); its cell (0, 0) lies at world (ox, oy) for good."""
+        if not counted:
+            if ox is not None or oy is not None:
+                raise ValueError("empty_correlation_map: only a counted map has an origin of its own")
+            h = self._lib.ym_map_create_empty(self._m, int(width), int(height))
+        else:
+            if ox is None or oy is None:
+                raise ValueError("empty_correlation_map: a counted map needs its origin (ox, oy)")
+            h = self._lib.ym_map_create_counted(self._m, int(width), int(height), float(ox), float(oy))
         if not h:
             raise _capi.YmError(-1, _capi.last_error())
-        return CorrelationMap(self, h)
+        return CorrelationMap(self, h, origin=(float(ox), float(oy)) if counted else None)
 
     def match_scan_sets_with_map(self, cgrid, ox, oy, query_scans, penalty=True, do_fine=True, coarse=None):
         """The reference's signature (scan_matching.py:124): the point readings of all `query_scans` are matched as one
@@ -680,38 +689,158 @@ class ScanMatcher(object):
 
 
 MapAddStats = namedtuple("MapAddStats", ["points", "stamped", "dropped", "x0", "y0", "x1", "y1"])
+MapUpdateStats = namedtuple("MapUpdateStats", ["removed", "added", "dropped", "unmatched", "released", "gained", "x0", "y0", "x1", "y1"])
 
 
 class CorrelationMap(object):
     """A correlation grid resident on the device (ym_map): built from an occupancy image, uploaded, or made empty and
-    filled with `add_scans`.  `revision` starts at 0 and goes up by one with every `add_scans` that stamped something and
-    with every `clear`: what was derived from the map (a MapLocator) compares it with the revision it was made at."""
+    filled with `add_scans`.  `revision` starts at 0 and goes up by one with every call that changed a cell -- an `add_scans`
+    that stamped something, a `remove_scans` or `sync` that took something out or put something in -- and with every `clear`:
+    what was derived from the map (a MapLocator) compares it with the revision it was made at.
 
-    def __init__(self, matcher, handle):
+    A counted map (`ScanMatcher.empty_correlation_map(w, h, counted=True, ox=..., oy=...)`) can also
+    forget: `counted` is True, `origin` its fixed (ox, oy), and it keeps every scan it holds with the pose it was added at, as
+    LiveOccupancyGrid does, so `remove_scans` and `sync` take out exactly what went in whatever happened to the scan's pose
+    since.  `scan in cmap` and `len(cmap)` speak of the held scans.  On any other map `counted` is False, `origin` None, and
+    the methods that forget raise ValueError."""
+
+    def __init__(self, matcher, handle, origin=None):
         self.m, self._h = matcher, handle
         w, h = C.c_int32(), C.c_int32()
         _capi.check(matcher._lib.ym_map_size(handle, C.byref(w), C.byref(h)))
         self.shape = (h.value, w.value)
         self.revision = 0
+        self.counted, self.origin = origin is not None, origin
+        self._held = {}  # counted maps: id(scan) -> (the scan, the pose it was added at); insertion-ordered
 
     def add_scans(self, ox, oy, scans):
         """The reference's `add_scan_to_grid` (helpers.py:105-131) on the device (`ym_map_add_scans`): every point reading
         `scan.points()` yields at the scan's current pose is stamped into the map whose cell (0, 0) lies at world (ox, oy)
         and max-smeared with the matcher's kernel; readings outside the map are dropped and counted.  The map does not
         depend on the order of scans or calls.  Returns MapAddStats(points, stamped, dropped, x0, y0, x1, y1): the changed
-        cells lie inside [x0, x1) x [y0, y1)."""
+        cells lie inside [x0, x1) x [y0, y1).
+        On a counted map (ox, oy) must be the map's origin and no scan may be held already (ValueError, before the library
+        is touched); the scans are then held at the poses they have now."""
         scans = list(scans)
+        counted = getattr(self, "counted", False)
+        if counted:
+            if (float(ox), float(oy)) != self.origin:
+                raise ValueError("add_scans: this counted map's origin is %r, not (%r, %r)" % (self.origin, ox, oy))
+            self._distinct(scans, "add_scans", held=False)
         hs = (C.c_void_p * max(1, len(scans)))(*[self.m._require_native(q) for q in scans])
+        poses = [_pose_of(q) for q in scans] if counted else None
         st = _capi.YmMapAddStats()
         _capi.check(self.m._lib.ym_map_add_scans(self.m._m, self._h, float(ox), float(oy), hs, len(scans), C.byref(st)))
+        if counted:
+            for q, pose in zip(scans, poses):
+                self._held[id(q)] = (q, pose)
         if st.stamped > 0:
             self.revision += 1
         return MapAddStats(st.points, st.stamped, st.dropped, st.x0, st.y0, st.x1, st.y1)
 
     def clear(self):
-        """every cell back to zero (`ym_map_clear`)"""
+        """every cell back to zero (`ym_map_clear`); a counted map forgets the scans it held"""
         _capi.check(self.m._lib.ym_map_clear(self.m._m, self._h))
+        if getattr(self, "counted", False):
+            self._held = {}
         self.revision += 1
+
+    # ---- counted maps: the scans held, and letting them go (ym_map_update_scans)
+    def _need_counted(self, what):
+        if not getattr(self, "counted", False):
+            raise ValueError("%s: this map keeps no counts; make it with empty_correlation_map(w, h, counted=True, ox=..., oy=...)" % what)
+
+    def _distinct(self, scans, what, held):
+        seen = set()
+        for i, q in enumerate(scans):
+            if id(q) in seen:
+                raise ValueError("%s: scan %d is in the list twice" % (what, i))
+            seen.add(id(q))
+            if (id(q) in self._held) != held:
+                raise ValueError("%s: scan %d is %s" % (what, i, "not held" if held else "already held"))
+
+    def __len__(self):
+        self._need_counted("len")
+        return len(self._held)
+
+    def __bool__(self):  # (a map is a map however many scans it holds)
+        return True
+
+    def __contains__(self, scan):
+        self._need_counted("in")
+        return id(scan) in self._held
+
+    def _update(self, remove, add):
+        """`remove` out at the poses they were added at and `add` in at their current ones, in one library call"""
+        if not remove and not add:
+            return MapUpdateStats(*([0] * 10))
+        lib = self.m._lib
+        rs = (C.c_void_p * max(1, len(remove)))(*[self.m._require_native(q) for q in remove])
+        ads = (C.c_void_p * max(1, len(add)))(*[self.m._require_native(q) for q in add])
+        old = np.array([self._held[id(q)][1] for q in remove], dtype=np.float64).reshape(len(remove), 3)
+        new = [_pose_of(q) for q in add]
+        st = _capi.YmMapUpdateStats()
+        _capi.check(lib.ym_map_update_scans(self.m._m, self._h, rs, old.ctypes.data_as(C.POINTER(C.c_double)), len(remove), ads,
+                                            len(add), C.byref(st)))
+        for q in remove:
+            del self._held[id(q)]
+        for q, pose in zip(add, new):
+            self._held[id(q)] = (q, pose)
+        if st.removed > 0 or st.added > 0:
+            self.revision += 1
+        out = MapUpdateStats(st.removed, st.added, st.dropped, st.unmatched, st.released, st.gained, st.x0, st.y0, st.x1, st.y1)
+        if st.unmatched > 0:
+            raise RuntimeError("CorrelationMap: %d removed readings met a count of zero: the map's counts and the scans it is "
+                               "said to hold disagree (%r)" % (st.unmatched, out))
+        return out
+
+    def remove_scans(self, scans):
+        """Take held scans out of a counted map, at the poses they were added at.  A scan that is not held raises ValueError
+        before the library is touched.  Returns MapUpdateStats(removed, added, dropped, unmatched, released, gained, x0, y0,
+        x1, y1): readings, then cells, then the rectangle that holds every changed cell."""
+        self._need_counted("remove_scans")
+        scans = list(scans)
+        self._distinct(scans, "remove_scans", held=True)
+        return self._update(scans, [])
+
+    def sync(self, scans=None):
+        """Move every held scan among `scans` (None: all held scans; scans that are not held are passed over) whose current
+        pose differs from the one it was added at: out at the old pose and in at the new one, in one library call.  The cost
+        is that of the moved scans.  Returns MapUpdateStats."""
+        self._need_counted("sync")
+        if scans is not None:
+            scans = list(scans)
+            if len({id(q) for q in scans}) != len(scans):
+                raise ValueError("sync: a scan is in the list twice")
+        moved = self.moved_scans(scans)
+        return self._update(moved, moved)
+
+    def moved_scans(self, scans=None):
+        """the held scans among `scans` (None: all held scans) whose current pose differs from the one they were added at"""
+        self._need_counted("moved_scans")
+        if scans is None:
+            scans = [e[0] for e in self._held.values()]
+        return [q for q in scans if id(q) in self._held and self._held[id(q)][1] != _pose_of(q)]
+
+    def update_scans(self, remove, add):
+        """`remove_scans(remove)` and `add_scans(ox, oy, add)` in ONE library call (`ym_map_update_scans`): the removed scans go
+        out first.  A scan may be in both lists (it is moved); otherwise the rules of the two methods hold.  Returns
+        MapUpdateStats."""
+        self._need_counted("update_scans")
+        remove, add = list(remove), list(add)
+        self._distinct(remove, "update_scans (remove)", held=True)
+        going = {id(q) for q in remove}
+        self._distinct([q for q in add if id(q) not in going], "update_scans (add)", held=False)
+        if len({id(q) for q in add}) != len(add):
+            raise ValueError("update_scans (add): a scan is in the list twice")
+        return self._update(remove, add)
+
+    def stamps(self):
+        """the number of readings stamped in each cell of a counted map (uint32, the map's shape)"""
+        self._need_counted("stamps")
+        out = np.empty(self.shape, dtype=np.uint32)
+        _capi.check(self.m._lib.ym_map_read_stamps(self._h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size))
+        return out
 
     def to_numpy(self):
         out = np.empty(self.shape, dtype=np.float64)
