@@ -66,7 +66,14 @@ int ym_debug_cells(ym_matcher *m, int item, int32_t *out, int64_t out_count, int
     if ((size_t)out_count < per * 2) return set_err(YM_ERR_INVALID, "buffer too small: need %zu ints", per * 2);
     DEV_GUARD(m->device);
     HIP_TRY(hipStreamSynchronize(m->stream));
-    HIP_TRY(hipMemcpy(out, m->cells.p + (size_t)item * per, sizeof(int2) * per, hipMemcpyDeviceToHost));
+    // (the caller's format is (x, y) int32 pairs, YM_CELL_NONE twice where there is no cell, whatever the device keeps)
+    std::vector<YmCell> dev(per);
+    HIP_TRY(hipMemcpy(dev.data(), m->cells.p + (size_t)item * per, sizeof(YmCell) * per, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < per; i++) {
+        const int2 c = ym_cell_unpack(dev[i]);
+        out[2 * i] = c.x;
+        out[2 * i + 1] = c.y;
+    }
     return YM_OK;
 }
 

@@ -80,7 +80,7 @@ struct ym_matcher {
     DevBuf<double2> qlocal;    // [query slots][max_n] sensor-frame query points
     DevBuf<int32_t> qnp;       // [query slots]
     DevBuf<unsigned char> tmp_cache; // batches: per-call cache slots of base scans the point cache cannot hold
-    DevBuf<int2> cells;
+    DevBuf<YmCell> cells;
     DevBuf<int4> bbox;
     DevBuf<uint8_t> grid;
     DevBuf<uint8_t> planes;    // even/odd column planes of every window

@@ -94,6 +94,10 @@ int plan_sizes(ym_matcher *m, Slot &slot, CallPlan &P) {
     g.pitch = P.tiles_x * YM_TILE_W + 64;
     P.grid_stride = align_up((size_t)g.pitch * g.win_w + 64, 256);
     if ((double)g.pitch * g.win_w > 2.0e9) return set_err(YM_ERR_UNSUPPORTED, "correlation window too large");
+    // a window cell is kept as two signed 16-bit halves (YmCell): x = gx + border - win_origin with 0 <= gx < roi_w and
+    // 0 <= win_origin <= border + roi_w / 2, so |x| < roi_w + border
+    if (g.roi_w + g.border >= YM_CELL_COORD_LIMIT)
+        return set_err(YM_ERR_UNSUPPORTED, "region of interest of %d + %d cells: a window coordinate must stay below %d", g.roi_w, g.border, YM_CELL_COORD_LIMIT);
     if (lf.nx > 64 || lf.ny > 64 || lf.nt > YM_MAX_FINE_NT || (int64_t)lf.nx * lf.ny * lf.nt > YM_MAX_FINE_HYP)
         return set_err(YM_ERR_UNSUPPORTED, "fine lattice %dx%dx%d exceeds the built-in limit", lf.nx, lf.ny, lf.nt);
     if (lc.nt > YM_MAX_COARSE_NT)

@@ -7,6 +7,9 @@ namespace ym {
 // ================================================================== K1 prepare
 #define YM_PREP_LDS_BYTES(max_n) ((size_t)(max_n) * 25 + ((size_t)(max_n) / 64 + 2) * 4 + 16)
 #define YM_INLINE_SCANS 16
+#ifndef YM_CELLS_Q
+#define YM_CELLS_Q 3         // chunks of 256 points cells_kernel keeps in flight (see cells_from_cache)
+#endif
 struct YmInlineDesc {        // call descriptor passed in the kernel arguments (single item, few scans)
     YmItem item;
     YmScanRef scans[YM_INLINE_SCANS];
@@ -22,7 +25,7 @@ struct PrepareArgs {
     YmItemState *states;
     double2 *qlocal;         // [query slots][max_n]
     int32_t *qnp;            // [query slots] number of point readings of the slot's query
-    int2 *cells;             // [B][max_base][max_n]  window cell of every base point, NONE when filtered
+    YmCell *cells;           // [B][max_base][max_n]  window cell of every base point (ym_types.h), "no cell" when filtered
     int4 *bbox;              // [B][max_base][YM_N_BOXES(max_n)] window bounding box of YM_BOX_CELLS consecutive cells
     double2 *ctrig;          // [B][nt_stride] (cos, sin) of every coarse angle
     int32_t *hypcell;        // [B][2][dim_stride]
@@ -204,11 +207,11 @@ __device__ __forceinline__ int2 gov_walk(const PrepLds &l, int i, int np, bool y
 template <int NT>
 __device__ __forceinline__ void store_cache(const YmScanRef &sr, const PrepLds &l, int np, bool yag) {
     double2 *cpts = reinterpret_cast<double2 *>(sr.cache + YM_CACHE_HEADER);
-    int2 *cgov = reinterpret_cast<int2 *>(sr.cache + YM_CACHE_HEADER + (size_t)sr.n * 16);
+    YmGov *cgov = reinterpret_cast<YmGov *>(sr.cache + YM_CACHE_HEADER + (size_t)sr.n * 16);
     const int2 *known = reinterpret_cast<const int2 *>(sr.gov);
     for (int i = threadIdx.x; i < np; i += NT) {
         cpts[i] = make_double2(l.sx[i], l.sy[i]);
-        cgov[i] = known ? known[i] : gov_walk(l, i, np, yag);
+        cgov[i] = ym_gov_pack(known ? known[i] : gov_walk(l, i, np, yag));
     }
     if (threadIdx.x == 0) *reinterpret_cast<int *>(sr.cache) = np;
 }
@@ -287,7 +290,7 @@ __device__ __forceinline__ void prepare_cells(const PrepareArgs &a, int b, int s
                                               double off_x, double off_y, PT pt_of, GOV gov_of) {
     const int tid = threadIdx.x;
     const int n_cchunks = YM_N_BOXES(a.max_n);
-    int2 *cells = a.cells + ((size_t)b * a.max_base + slot) * a.max_n;
+    YmCell *cells = a.cells + ((size_t)b * a.max_base + slot) * a.max_n;
     int4 *bbox = a.bbox + ((size_t)b * a.max_base + slot) * n_cchunks;
     for (int i0 = 0; i0 < n_cchunks * YM_BOX_CELLS; i0 += NT) {
         const int i = i0 + tid; // a row of 16 lanes covers one chunk of YM_BOX_CELLS cells
@@ -318,11 +321,11 @@ __device__ __forceinline__ void prepare_cells(const PrepareArgs &a, int b, int s
                     c = make_int2(gx + a.g.border - a.g.win_origin, gy + a.g.border - a.g.win_origin);
             }
         }
-        if (i < a.max_n) cells[i] = c;
+        const bool has = c.x != YM_CELL_NONE;
+        if (i < a.max_n) cells[i] = has ? ym_cell_pack(c.x, c.y) : ym_cell_none();
         chain_check_cell(a, c);
         // bounding box of the chunk's rasterised cells: the raster kernel reads a chunk only when
         // this box touches its tile
-        const bool has = c.x != YM_CELL_NONE;
         const int x0 = row16_reduce(has ? c.x : INT32_MAX, OpMinI()), y0 = row16_reduce(has ? c.y : INT32_MAX, OpMinI());
         const int x1 = row16_reduce(has ? c.x : INT32_MIN, OpMaxI()), y1 = row16_reduce(has ? c.y : INT32_MIN, OpMaxI());
         if ((tid & (YM_BOX_CELLS - 1)) == 0 && i / YM_BOX_CELLS < n_cchunks) bbox[i / YM_BOX_CELLS] = make_int4(x0, y0, x1, y1);
@@ -333,56 +336,48 @@ __device__ __forceinline__ void prepare_cells(const PrepareArgs &a, int b, int s
 template <int NT>
 __device__ __forceinline__ void clear_slot(const PrepareArgs &a, int b, int slot) {
     const int n_cchunks = YM_N_BOXES(a.max_n);
-    int2 *cells = a.cells + ((size_t)b * a.max_base + slot) * a.max_n;
+    YmCell *cells = a.cells + ((size_t)b * a.max_base + slot) * a.max_n;
     int4 *bbox = a.bbox + ((size_t)b * a.max_base + slot) * n_cchunks;
-    for (int i = threadIdx.x; i < a.max_n; i += NT) cells[i] = make_int2(YM_CELL_NONE, YM_CELL_NONE);
+    for (int i = threadIdx.x; i < a.max_n; i += NT) cells[i] = ym_cell_none();
     for (int i = threadIdx.x; i < n_cchunks; i += NT) bbox[i] = make_int4(INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN);
 }
 
-// one base scan of one item from the point cache: no LDS, no barrier.  The three dependent rounds of loads (who decides
-// point i -> the two deciding points -> the point itself) are issued for Q chunks of the scan at a time, so a block
-// waits three round trips per Q * NT points instead of three per NT.
+// one base scan of one item from the point cache: no LDS, no barrier.  Two dependent rounds of loads (who decides point i,
+// with the point itself -> the two deciding points) are issued for Q chunks of the scan at a time, so a block waits two
+// round trips per Q * NT points instead of two per NT.  The kernel is bound by those round trips times the blocks a CU
+// holds, not by its bytes: a point is turned into its cell (one register) before its deciding points (eight) are asked for,
+// which is what lets Q = 3 keep seven waves per SIMD.
 template <int NT>
 __device__ __forceinline__ void cells_from_cache(const PrepareArgs &a, int b, int slot, const YmScanRef &sr, const YmScanRef &qr, bool yag) {
-    constexpr int Q = NT == 256 ? 3 : 4; // (cells_kernel, measured: Q = 4 398 us per 4096 items at 86 VGPRs, Q = 3 326 at 72, Q = 2 360 at 58)
+    // (cells_kernel on 4096 items of 10 scans of 1081 readings, per launch: Q = 3 265 us at 72 VGPRs, Q = 4 309 at 86, Q = 5 -- one
+    //  trip through the loop -- 282 at 100; with the point held until the store Q = 3 took 82 VGPRs and 312 us.  profiles/cells_packed_study.md)
+    constexpr int Q = NT == 256 ? YM_CELLS_Q : 4;
     const double2 *__restrict__ cpts = reinterpret_cast<const double2 *>(sr.cache + YM_CACHE_HEADER);
-    const int2 *__restrict__ cgov = reinterpret_cast<const int2 *>(sr.cache + YM_CACHE_HEADER + (size_t)sr.n * 16);
+    const YmGov *__restrict__ cgov = reinterpret_cast<const YmGov *>(sr.cache + YM_CACHE_HEADER + (size_t)sr.n * 16);
     const int np = *reinterpret_cast<const int *>(sr.cache);
     const double off_x = qr.pose[0] - (0.5 * (a.g.roi_w - 1) * a.g.res);
     const double off_y = qr.pose[1] - (0.5 * (a.g.roi_w - 1) * a.g.res);
     const double vpx = qr.pose[0], vpy = qr.pose[1];
     const int tid = threadIdx.x;
     const int n_cchunks = YM_N_BOXES(a.max_n);
-    int2 *cells = a.cells + ((size_t)b * a.max_base + slot) * a.max_n;
+    YmCell *cells = a.cells + ((size_t)b * a.max_base + slot) * a.max_n;
     int4 *bbox = a.bbox + ((size_t)b * a.max_base + slot) * n_cchunks;
     for (int i0 = 0; i0 < n_cchunks * YM_BOX_CELLS; i0 += Q * NT) {
-        int2 g[Q];
-        double2 f[Q], t[Q], p[Q];
+        YmGov g[Q]; // (kept as loaded -- one register a chunk with the packed records -- and taken apart where it is used)
+        YmCell cw[Q];
+        double2 f[Q], t[Q];
+        {
+            double2 p[Q];
 #pragma unroll
-        for (int q = 0; q < Q; q++) {
-            const int i = i0 + q * NT + tid;
-            g[q] = i < np ? cgov[i] : make_int2(-1, np);
-        }
+            for (int q = 0; q < Q; q++) {
+                const int i = i0 + q * NT + tid;
+                g[q] = i < np ? cgov[i] : ym_gov_pack(make_int2(-1, np));
+                p[q] = cpts[i < np ? i : 0];
+            }
+            // where the point lies, before the deciding points are asked for: a cell is one register (two in the wide build), the
+            // point was four, and the registers a chunk holds at its widest decide how many chunks a SIMD keeps in flight
 #pragma unroll
-        for (int q = 0; q < Q; q++) {
-            const int i = i0 + q * NT + tid;
-            const bool decided = g[q].x >= 0 && g[q].y < np;
-            f[q] = cpts[decided ? g[q].x : 0];
-            t[q] = cpts[decided ? g[q].y : 0];
-            p[q] = cpts[i < np ? i : 0];
-        }
-#pragma unroll
-        for (int q = 0; q < Q; q++) {
-            const int i = i0 + q * NT + tid; // a wave covers one 64-cell chunk
-            if (i0 + q * NT >= n_cchunks * YM_BOX_CELLS) break; // block-uniform
-            int2 c = make_int2(YM_CELL_NONE, YM_CELL_NONE);
-            if (i < np && g[q].x >= 0 && g[q].y < np) {
-                const double fx = f[q].x, fy = f[q].y, cx = t[q].x, cy = t[q].y;
-                const double aa = vpy - fy;
-                const double bb = fx - vpx;
-                const double cc = fy * vpx - fx * vpy;
-                const double ss = cx * aa + cy * bb + cc;
-                const bool keep = yag ? (ss > 0.0) : !(ss < 0.0);
+            for (int q = 0; q < Q; q++) {
                 int gx, gy;
                 if (yag) {
                     gx = (int)rint((p[q].x - off_x) / a.g.res);
@@ -391,12 +386,37 @@ __device__ __forceinline__ void cells_from_cache(const PrepareArgs &a, int b, in
                     gx = world_to_grid(p[q].x, off_x, a.g.scale);
                     gy = world_to_grid(p[q].y, off_y, a.g.scale);
                 }
-                if (keep && gx >= 0 && gx < a.g.roi_w && gy >= 0 && gy < a.g.roi_w)
-                    c = make_int2(gx + a.g.border - a.g.win_origin, gy + a.g.border - a.g.win_origin);
+                cw[q] = (gx >= 0 && gx < a.g.roi_w && gy >= 0 && gy < a.g.roi_w) ? ym_cell_pack(gx + a.g.border - a.g.win_origin, gy + a.g.border - a.g.win_origin)
+                                                                                 : ym_cell_none();
             }
-            if (i < a.max_n) cells[i] = c;
-            chain_check_cell(a, c);
+        }
+        __builtin_amdgcn_sched_barrier(0); // (the deciding points' loads are not to be issued while the points are still held)
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            const int2 st = ym_gov_unpack(g[q]);
+            const bool decided = st.x >= 0 && st.y < np;
+            f[q] = cpts[decided ? st.x : 0];
+            t[q] = cpts[decided ? st.y : 0];
+        }
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            const int i = i0 + q * NT + tid; // a row of 16 lanes covers one chunk of YM_BOX_CELLS cells
+            if (i0 + q * NT >= n_cchunks * YM_BOX_CELLS) break; // block-uniform
+            const int2 st = ym_gov_unpack(g[q]);
+            bool keep = false;
+            if (i < np && st.x >= 0 && st.y < np) {
+                const double fx = f[q].x, fy = f[q].y, cx = t[q].x, cy = t[q].y;
+                const double aa = vpy - fy;
+                const double bb = fx - vpx;
+                const double cc = fy * vpx - fx * vpy;
+                const double ss = cx * aa + cy * bb + cc;
+                keep = yag ? (ss > 0.0) : !(ss < 0.0);
+            }
+            const YmCell w = keep ? cw[q] : ym_cell_none();
+            const int2 c = ym_cell_unpack(w);
             const bool has = c.x != YM_CELL_NONE;
+            if (i < a.max_n) cells[i] = w;
+            chain_check_cell(a, c);
             const int x0 = row16_reduce(has ? c.x : INT32_MAX, OpMinI()), y0 = row16_reduce(has ? c.y : INT32_MAX, OpMinI());
             const int x1 = row16_reduce(has ? c.x : INT32_MIN, OpMaxI()), y1 = row16_reduce(has ? c.y : INT32_MIN, OpMaxI());
             if ((tid & (YM_BOX_CELLS - 1)) == 0 && i / YM_BOX_CELLS < n_cchunks) bbox[i / YM_BOX_CELLS] = make_int4(x0, y0, x1, y1);
@@ -700,7 +720,7 @@ __global__ __launch_bounds__(YM_TILES_THREADS) void tiles_kernel(TilesArgs a) {
 // earliest undecided cell always resolves, so the loop ends; (3) erase every point
 // that is not the earliest of an effective cell from `cells`.  One block per item.
 struct SelectArgs {
-    int2 *cells;          // [B][max_base][max_n]
+    YmCell *cells;        // [B][max_base][max_n]
     int32_t max_n, max_base;
     int32_t z2max;        // largest squared distance whose kernel value is 100
     int32_t log2cap;      // hash capacity = 1 << log2cap entries (dynamic LDS: 9 bytes per entry)
@@ -770,7 +790,7 @@ __global__ __launch_bounds__(1024) void select_kernel(SelectArgs a) {
     // The thread's points: all loaded at once and kept for step (3), with the slots step (1) finds for them.  (The one block
     // of an item is a latency chain: a load per loop trip -- which the stores of step (3) into the same array keep the
     // compiler from moving -- cost steps (1) and (3) a memory round trip per point, 14 + 58 of the kernel's 118 us.)
-    int2 *cells = a.cells + (size_t)b * a.max_base * a.max_n;
+    YmCell *cells = a.cells + (size_t)b * a.max_base * a.max_n;
     const int total = a.max_base * a.max_n;
     int2 mine[PMAX];
     unsigned short slot_of[PMAX];
@@ -782,7 +802,7 @@ __global__ __launch_bounds__(1024) void select_kernel(SelectArgs a) {
 #pragma unroll
     for (int q = 0; q < PMAX; q++) {
         const int e = e0 + q;
-        mine[q] = (q < per && e < total) ? cells[e] : make_int2(YM_CELL_NONE, YM_CELL_NONE);
+        mine[q] = (q < per && e < total) ? ym_cell_unpack(cells[e]) : make_int2(YM_CELL_NONE, YM_CELL_NONE);
     }
     for (unsigned i = tid; i < cap; i += NT) { keys[i] = 0u; minidx[i] = 0xffffffffu; status[i] = 0; }
     __syncthreads();
@@ -880,7 +900,7 @@ __global__ __launch_bounds__(1024) void select_kernel(SelectArgs a) {
     for (int q = 0; q < PMAX; q++) {
         if (mine[q].x == YM_CELL_NONE) continue;
         const int e = e0 + q, t = slot_of[q];
-        if (!(status[t] == 1 && minidx[t] == (unsigned)e)) cells[e] = make_int2(YM_CELL_NONE, YM_CELL_NONE);
+        if (!(status[t] == 1 && minidx[t] == (unsigned)e)) cells[e] = ym_cell_none();
     }
     YM_STAMP(a, 31);
 }
@@ -892,7 +912,7 @@ __global__ __launch_bounds__(1024) void select_kernel(SelectArgs a) {
 // a 16-byte record per point (SelectSplitArgs::rec): rec.x = slot | owned << 16 | effective << 17 (0xffffffff: no point), rec.y / rec.z = the slots of
 // the neighbour cells with an earlier point, 16 bits each (0xffff: none).
 struct SelectSplitArgs {
-    int2 *cells;          // [B][max_base][max_n]
+    YmCell *cells;        // [B][max_base][max_n]
     int32_t max_n, max_base;
     int32_t log2cap, pad;
     unsigned *keys;       // [B][cap]  zero between calls
@@ -910,7 +930,7 @@ __global__ __launch_bounds__(YM_SELECT_SPLIT_THREADS) void select_hash_kernel(Se
     if (e >= total) return;
     const unsigned cap = 1u << a.log2cap, bmask = (cap >> 2) - 1u;
     const int shift = 32 - (a.log2cap - 2);
-    const int2 c = a.cells[(size_t)b * total + e];
+    const int2 c = ym_cell_unpack(a.cells[(size_t)b * total + e]);
     unsigned slot = 0xffffffffu;
     if (c.x != YM_CELL_NONE) {
         slot = (unsigned)select_insert(a.keys + (size_t)b * cap, bmask, shift, select_key(c.x, c.y));
@@ -931,7 +951,7 @@ __global__ __launch_bounds__(YM_SELECT_SPLIT_THREADS) void select_neighbours_ker
     const int per = (total + 1023) / 1024;
     uint4 *rec = a.rec + (size_t)b * 12 * 1024 + (size_t)(e % per) * 1024 + e / per;
     const unsigned s = a.slot_of[(size_t)b * total + e];
-    const int2 c = a.cells[(size_t)b * total + e]; // (a point without a cell: YM_CELL_NONE, any bucket)
+    const int2 c = ym_cell_unpack(a.cells[(size_t)b * total + e]); // (a point without a cell: YM_CELL_NONE, any bucket)
     // the first probe of every neighbour leaves before the point's own entry is looked at: one round trip, not two
     unsigned nkey[5], nbk[5];
     uint4 nq[5];
@@ -981,7 +1001,7 @@ __global__ __launch_bounds__(1024) void select_relax_kernel(SelectSplitArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x;
     const unsigned cap = 1u << a.log2cap;
     const int total = a.max_base * a.max_n;
-    int2 *cells = a.cells + (size_t)b * total;
+    YmCell *cells = a.cells + (size_t)b * total;
     const uint4 *rec = a.rec + (size_t)b * 12 * 1024;
     // a thread takes `per` CONSECUTIVE points (see select_kernel: a wall's chain of decisions resolves inside one thread)
     const int per = (total + NT - 1) / NT, e0 = tid * per;
@@ -1039,7 +1059,7 @@ __global__ __launch_bounds__(1024) void select_relax_kernel(SelectSplitArgs a) {
 #pragma unroll
     for (int q = 0; q < PMAX; q++) {
         if (r[q].x == 0xffffffffu) continue;
-        if (!((r[q].x & (1u << 16)) && status[r[q].x & 0xffffu] == 1)) cells[e0 + q] = make_int2(YM_CELL_NONE, YM_CELL_NONE);
+        if (!((r[q].x & (1u << 16)) && status[r[q].x & 0xffffu] == 1)) cells[e0 + q] = ym_cell_none();
     }
     // the tables as the next call expects them
     uint4 *k4 = reinterpret_cast<uint4 *>(a.keys + (size_t)b * cap), *m4 = reinterpret_cast<uint4 *>(a.mx + (size_t)b * cap);
@@ -1052,7 +1072,7 @@ __global__ __launch_bounds__(1024) void select_relax_kernel(SelectSplitArgs a) {
 // dependent decisions, not a parallel job -- but its reads now cost an L2 round trip instead of an LDS one).  LDS only
 // holds each thread's shrinking list of undecided slots.  Capacity 2^17 slots = 98 304 readings at load factor 0.75.
 struct SelectGlobalArgs {
-    int2 *cells;          // [B][max_base][max_n]
+    YmCell *cells;        // [B][max_base][max_n]
     int32_t max_n, max_base;
     int32_t z2max, log2cap;
     unsigned *keys;       // [B][cap]           zeroed by the host
@@ -1072,11 +1092,11 @@ __global__ __launch_bounds__(1024) void select_global_kernel(SelectGlobalArgs a)
     const int shift = 32 - (a.log2cap - 2);
     unsigned *keys = a.keys + (size_t)b * cap, *minidx = a.minidx + (size_t)b * cap, *status = a.status + (size_t)b * cap;
     unsigned *nbr = a.nbr + (size_t)b * (NB - 1) * cap;
-    int2 *cells = a.cells + (size_t)b * a.max_base * a.max_n;
+    YmCell *cells = a.cells + (size_t)b * a.max_base * a.max_n;
     const int total = a.max_base * a.max_n;
     // (1) cell -> earliest point index
     for (int e = tid; e < total; e += NT) {
-        const int2 c = cells[e];
+        const int2 c = ym_cell_unpack(cells[e]);
         if (c.x == YM_CELL_NONE) continue;
         const int slot = select_insert(keys, bmask, shift, select_key(c.x, c.y));
         atomicMin(&minidx[slot], (unsigned)e);
@@ -1131,11 +1151,11 @@ __global__ __launch_bounds__(1024) void select_global_kernel(SelectGlobalArgs a)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     // (3) keep only the earliest point of every effective cell
     for (int e = tid; e < total; e += NT) {
-        const int2 c = cells[e];
+        const int2 c = ym_cell_unpack(cells[e]);
         if (c.x == YM_CELL_NONE) continue;
         const int t = select_find(keys, bmask, shift, select_key(c.x, c.y));
         if (!(t >= 0 && __hip_atomic_load(&status[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1u && minidx[t] == (unsigned)e))
-            cells[e] = make_int2(YM_CELL_NONE, YM_CELL_NONE);
+            cells[e] = ym_cell_none();
     }
 }
 

@@ -6,7 +6,7 @@ namespace ym {
 
 // ================================================================== K2 raster
 struct RasterArgs {
-    const int2 *cells;
+    const YmCell *cells; // (ym_types.h)
     const int4 *bbox;     // [B][max_base][YM_N_BOXES(max_n)]
     const YmItemState *states;
     YmGeom g;
@@ -194,9 +194,9 @@ __global__ __launch_bounds__(NT) void raster_kernel(RasterArgs a) {
         }
     }
     // LISTED: the cells of the first NT * 4 work items (hit slot, cell of the chunk) leave now, before the LDS tables are cleared
-    const int2 *cells = a.cells + (size_t)bi * a.max_base * a.max_n;
+    const YmCell *cells = a.cells + (size_t)bi * a.max_base * a.max_n;
     const int n_cells = a.max_base * a.max_n;
-    int2 cc0[4];
+    YmCell cc0[4];
     if constexpr (LISTED) {
 #pragma unroll
         for (int u = 0; u < 4; u++) {
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(NT) void raster_kernel(RasterArgs a) {
             // (a chunk's 16 cells may run past its scan's last reading into the next scan's first ones: the same item's occupied
             //  cells, stamped again -- harmless; past the item's last cell they would be another item's)
             const int ci = (int)hq[u] + (tid % YM_BOX_CELLS);
-            cc0[u] = make_int2(YM_CELL_NONE, YM_CELL_NONE);
+            cc0[u] = ym_cell_none();
             if (hi < hn && ci < n_cells) cc0[u] = cells[ci];
         }
     }
@@ -220,9 +220,10 @@ __global__ __launch_bounds__(NT) void raster_kernel(RasterArgs a) {
     static_assert(RW == 3, "row_words");
     // (ly * RW * 2 + word as ONE 24-bit multiply-add: hipcc folds "* 6" and the byte scaling into a quarter-rate v_mul_lo_u32 by 24)
     auto row_words = [](int ly, int word) { int r; asm("v_mad_u32_u24 %0, %1, 6, %2" : "=v"(r) : "v"(ly), "v"(word)); return r; };
-    auto stamp = [&](const int2 c2) {
+    auto stamp = [&](const YmCell cw) {
+        const int2 c2 = ym_cell_halves(cw); // ("no cell": an x no tile's halo reaches -- lo_x >= -YM_MAX_KERNEL_HALF)
         const int lx = c2.x - lo_x, ly = c2.y - lo_y;
-        if (c2.x != YM_CELL_NONE && lx >= 0 && lx < OW && ly >= 0 && ly < OH) {
+        if ((YM_WIDE_CELLS ? c2.x != YM_CELL_NONE : true) && lx >= 0 && lx < OW && ly >= 0 && ly < OH) {
             atomicOr(&occ32[row_words(ly, lx >> 5)], 1u << (lx & 31));
             any = 1;
         }
@@ -254,11 +255,11 @@ __global__ __launch_bounds__(NT) void raster_kernel(RasterArgs a) {
             for (int u = 0; u < 4; u++) stamp(cc0[u]);
             // (a tile more than NT / 4 chunks reach: the remaining hit slots, then their cells -- two more round trips)
             for (int h0 = NT / 4; h0 < hn; h0 += NT / 4) {
-                int2 cc[4];
+                YmCell cc[4];
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     const int hi = h0 + tid / YM_BOX_CELLS + u * (NT / YM_BOX_CELLS);
-                    cc[u] = make_int2(YM_CELL_NONE, YM_CELL_NONE);
+                    cc[u] = ym_cell_none();
                     if (hi < hn) {
                         const int ci = (int)hl[hi] + (tid % YM_BOX_CELLS);
                         if (ci < n_cells) cc[u] = cells[ci];
@@ -276,11 +277,11 @@ __global__ __launch_bounds__(NT) void raster_kernel(RasterArgs a) {
         // work item = (hit chunk, cell of the chunk); 4 items per thread in flight
         const int nwork = nhits * YM_BOX_CELLS;
         for (int w0 = 0; w0 < nwork; w0 += 4 * NT) {
-            int2 cc[4];
+            YmCell cc[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int w = w0 + u * NT + tid;
-                cc[u] = make_int2(YM_CELL_NONE, YM_CELL_NONE);
+                cc[u] = ym_cell_none();
                 if (w < nwork && (w % YM_BOX_CELLS) < s_left[w / YM_BOX_CELLS]) cc[u] = cells[s_hits[w / YM_BOX_CELLS] + (w % YM_BOX_CELLS)];
             }
 #pragma unroll
