@@ -674,9 +674,8 @@ int ym_debug_query_local(ym_matcher *m, int item, double *out_xy, int32_t cap, i
 int ym_debug_cells(ym_matcher *m, int item, int32_t *out, int64_t out_count, int32_t *max_n);
 /* the region correlate's pair lists of query slot `slot` of the last call, as bin_kernel left them ("The pair-list
  * contract"), with the geometry they were built for and what the builder read of the slot's representative item `qrep`.
- * YM_ERR_INVALID: the last call built no such lists (its correlate was not correlate_region_kernel), or no such slot;
- * YM_ERR_UNSUPPORTED: the lists have the one-part layout of the experimental forms.  Lists reused from an earlier call (option 45)
- * are read like freshly built ones.  With all five arrays NULL only *info is filled (the sizes to allocate); otherwise all five
+ * YM_ERR_INVALID: the last call built no such lists (its correlate was not correlate_region_kernel), or no such slot.
+ * Lists reused from an earlier call (option 45) are read like freshly built ones.  With all five arrays NULL only *info is filled (the sizes to allocate); otherwise all five
  * are written, and nothing is written when the call fails:
  *   ctrig   [nt][2]                 cos, sin of qrep's coarse angles
  *   starts  [lparts][nbins + 1]     first entry of bin region * lnw + (angle - part * lnw), positions in `entries`
@@ -699,7 +698,7 @@ int ym_debug_pair_lists(ym_matcher *m, int slot, ym_pair_list_info *info, double
 
 /* Switches of the parity tests: every row names a path the tests force so that each kernel and each host decision is compared with
  * the oracle (or with the default path) bit for bit.  None changes a result.  Development and timing switches that no test uses
- * (2 - 5, 9, 23, 26, 29, 33 - 36, 38, 40, 42, 44) are described where they are implemented, yag_slam_amd/csrc/ym_abi_debug.hpp.
+ * (2 - 5, 9, 23, 26, 29, 34, 36, 38, 40, 42) are described where they are implemented, yag_slam_amd/csrc/ym_abi_debug.hpp.
  *
  *   option  value                          effect
  *   ------  -----------------------------  ------------------------------------------------------------------------------------------
@@ -728,12 +727,9 @@ int ym_debug_pair_lists(ym_matcher *m, int slot, ym_pair_list_info *info, double
  *                                          (gather correlate 64, region correlate 48)
  *   30      32 / 64 / 0                    rows per raster tile whatever the call / the host's choice
  *   31      0                              a synchronous match waits for the creation launch of a just-created query scan
- *   32      0 / 1, 2 .. 6                  form of the region correlate: correlate_region_kernel / the forms that lost (scripts/exp/forms),
- *                                          only in builds made with `make experimental`: the product library answers YM_ERR_UNSUPPORTED
  *   37      1                              the raster's row pass by bit scans instead of its tables
  *   39      1                              every call writes the column planes and the region correlate stages from them
  *   41      n                              items up to which the order-dependent smear rule runs in its split form (8; 0 = never)
- *   43      80 / 100 / 128                 region height of experimental form 5
  *   45      0                              the pair lists of a single-query batch are built at every call (default: a call whose query,
  *                                          pose, window and lattice equal those of the last list build finds them in place)
  *   46      0 / 2                          YM_SEM_YAGPY, 0: both passes scored pair by pair, the Python rule as written (default: the coarse
@@ -742,6 +738,8 @@ int ym_debug_pair_lists(ym_matcher *m, int slot, ym_pair_list_info *info, double
  *                                          2: the default, with the fine pass reading its rows byte by byte (the path of a row whose
  *                                          columns do not fit one 8-byte read)
  *   47      n / 0                          items per chunk of ym_match_map_many whatever its scratch budget says / by the budget
+ *
+ * Options 0, 32, 33, 35, 43 and 44 chose between correlate forms that no longer exist: YM_ERR_INVALID, like any unknown option.
  */
 int ym_debug_option(ym_matcher *m, int option, int value);
 

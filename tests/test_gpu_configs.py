@@ -365,7 +365,7 @@ def test_cfg2_batch_512_distinct_chains_region_correlate_against_direct_and_orac
     (option 14 = 1), bit for bit, a seeded sample of 24 chains the oracle's, and the same call in two enqueues of 256 the
     same again (workspace items reused by other chains)."""
     from oracle import oracle as orc
-    from yag_slam_amd import _capi, synth
+    from yag_slam_amd import synth
     from yag_slam_amd.scan_matching import ScanMatcher
     n_chains = 512
     scene = synth.Scene()
@@ -379,17 +379,10 @@ def test_cfg2_batch_512_distinct_chains_region_correlate_against_direct_and_orac
     m = ScanMatcher()
     per, best = m.match_scan_batch(q, chains, True, True)
     assert len(per) == n_chains and all(tuple(p.meta["coarse_dims"]) == (26, 26, 21) for p in per)
-    # the direct kernel; the general gather correlate; the region correlate's wave-specialised and one-block-per-item forms; sixteen
-    # waves per block with regions of 80 / 100 / 128 rows (option 43)
-    for opt, mode in ((14, 1), (14, 4), (32, 2), (32, 3), (43, 80), (43, 100), (43, 128)):
+    # the direct kernel; the general gather correlate
+    for opt, mode in ((14, 1), (14, 4)):
         md = ScanMatcher()
-        try:
-            if opt == 43:
-                md.debug_option(32, 5)
-            md.debug_option(opt, mode)
-        except _capi.YmError as e:  # (option 32 = 2, 3: forms compiled only with -DYM_EXPERIMENTAL)
-            assert e.code == -4 and opt in (32, 43)
-            continue
+        md.debug_option(opt, mode)
         perd, bestd = md.match_scan_batch(q, chains, True, True)
         assert best == bestd == int(np.argmax([p.response for p in per]))
         for a, b in zip(per, perd):
@@ -408,6 +401,30 @@ def test_cfg2_batch_512_distinct_chains_region_correlate_against_direct_and_orac
     for lo in (256, 0):
         half, _ = m.match_scan_batch(q, chains[lo:lo + 256], True, True)
         assert all(a.response == b.response and a.covariance == b.covariance for a, b in zip(per[lo:lo + 256], half))
+
+
+def test_options_of_the_retired_correlate_forms_are_refused_and_change_nothing():
+    """Debug options 32, 33, 35, 43 and 44 chose between correlate forms the library no longer has: every one of them is
+    refused with YM_ERR_INVALID whatever its value, like option 0, and a matcher that was asked matches the eight-chain batch
+    of test_gpu_parity.py exactly as a fresh one does."""
+    from tests.test_gpu_parity import _mk_native
+    from tests.util import cfg2_scans
+    from yag_slam_amd import _capi
+    from yag_slam_amd.scan_matching import ScanMatcher
+    q, base = cfg2_scans()
+    nq, nb = _mk_native(q), [_mk_native(b) for b in base]
+    chains = [nb, nb[:3], nb[2:9], nb[::-1], nb[4:5], nb[1:], nb[:7], nb[3:]]
+    m = ScanMatcher()
+    for option, value in ((32, 0), (32, 2), (33, 1), (35, 64), (43, 100), (44, 64)):
+        with pytest.raises(_capi.YmError) as refused:
+            m.debug_option(option, value)
+        assert refused.value.code == -1, (option, value, refused.value.code)  # YM_ERR_INVALID
+    per, best = m.match_scan_batch(nq, chains, True, True)
+    per0, best0 = ScanMatcher().match_scan_batch(nq, chains, True, True)
+    assert best == best0 and len(per) == len(per0) == len(chains)
+    for a, b in zip(per, per0):
+        assert a.response == b.response and a.covariance == b.covariance and a.meta == b.meta
+        assert (a.best_pose.x, a.best_pose.y, a.best_pose.euler[-1]) == (b.best_pose.x, b.best_pose.y, b.best_pose.euler[-1])
 
 
 def _pairs_workload(n, scene=None):

@@ -15,22 +15,6 @@ def _mk_native(plain):
                               plain.min_range, plain.max_range, plain.range_threshold, p.x, p.y, p.euler[-1])
 
 
-def _has_experimental_forms():
-    """The correlate forms that lost to correlate_region_kernel (debug option 32 = 2, 3, 4) are compiled only into builds made
-    with -DYM_EXPERIMENTAL; a default build refuses the option with YM_ERR_UNSUPPORTED and the tests leave those forms out."""
-    from yag_slam_amd import _capi
-    from yag_slam_amd.scan_matching import ScanMatcher
-    m = ScanMatcher()
-    try:
-        m.debug_option(32, 2)
-        return True
-    except _capi.YmError as e:
-        assert e.code == -4
-        return False
-    finally:
-        m.close()
-
-
 def compare(cfg, query, base, penalty, fine, loop=False, resident=True, check_grid=True):
     from oracle import oracle as orc
     from yag_slam_amd.scan_matching import ScanMatcher
@@ -1148,7 +1132,6 @@ def test_region_correlate_equals_the_direct_kernel_and_the_oracle():
         m_ = _ScanMatcher(*args, **kw)
         m_.debug_option(28, 8)
         return m_
-    experimental = _has_experimental_forms()
     q, base = cfg2_scans()
     nq, nb = _mk_native(q), [_mk_native(b) for b in base]
     cut = lambda s, n: PlainScan(s.ranges[:n], s.min_angle, s.angle_increment, s.min_range, 20.0, (3.0, 3.0, 0.0))
@@ -1179,34 +1162,9 @@ def test_region_correlate_equals_the_direct_kernel_and_the_oracle():
                     assert np.array_equal(vols[mode][0][i], vols[1][0][i]), (mode, i)
                 same(vols[mode], vols[1])
             assert vols[0][0][0].any()
-            # the region correlate's other forms: wave-specialised (option 32 = 2: gather waves + loader waves, persistent blocks) and
-            # one block per item with the item's sums in LDS (= 3: what large batches take), with the lists that fit and without
-            # and the pooled form at two blocks per item (= 4: a region's patches dealt evenly over twelve waves, 16-bit sums in LDS)
-            # round 5: sixteen waves per block, two or three per angle (option 32 = 5; 43 = region height: form 80 / 100 / 128)
-            for form, irregular in ((2, 0), (3, 0), (3, 2), (3, 3), (4, 0), (4, 2), (4, 3), (80, 0), (100, 0), (128, 0), (128, 2), (100, 3)) if experimental else ():
-                m = ScanMatcher(cfg)
-                m.debug_option(12, 1)
-                if form >= 80:
-                    m.debug_option(43, form)
-                m.debug_option(32, 5 if form >= 80 else form)
-                if irregular:
-                    m.debug_option(14, irregular)
-                per, best = m.match_scan_batch(nquery, chains, True, True)
-                other = ([m.debug_sums(0, item=i, dims=per[0].meta["coarse_dims"]) for i in range(len(chains))], per, best)
-                for i in range(len(chains)):
-                    assert np.array_equal(other[0][i], vols[1][0][i]), (form, irregular, i)
-                same(other, vols[1])
             # without the kept sums (the production form: the region correlate scores its sums itself; option 21 = 2 leaves
             # that to the score kernel), through either kernel
-            for opts in ({}, {21: 2}, {14: 4}, {32: 2}, {32: 2, 21: 2}, {32: 3}, {32: 3, 21: 2}, {32: 3, 14: 2}, {32: 4}, {32: 4, 21: 2}, {32: 4, 14: 2}, {32: 4, 39: 1}):
-                if 32 in opts and not experimental:
-                    continue
-                if opts.get(32) == 4 and len(opts) == 1:  # (rides along: the sixteen-wave form with its three region heights)
-                    for h in (80, 100, 128):
-                        m = ScanMatcher(cfg)
-                        m.debug_option(43, h)
-                        m.debug_option(32, 5)
-                        same((None,) + tuple(m.match_scan_batch(nquery, chains, True, True)), vols[1])
+            for opts in ({}, {21: 2}, {14: 4}):
                 m = ScanMatcher(cfg)
                 for k, v in opts.items():
                     m.debug_option(k, v)

@@ -83,7 +83,6 @@ int ym_debug_pair_lists(ym_matcher *m, int slot, ym_pair_list_info *info, double
     if (!m || !info) return set_err(YM_ERR_INVALID, "null argument");
     const ym_matcher::ListsLast &ll = m->lists_last;
     if (!m->last_valid || !ll.valid) return set_err(YM_ERR_INVALID, "the last call built no region pair lists");
-    if (ll.whole) return set_err(YM_ERR_UNSUPPORTED, "the one-part lists of the experimental forms are not read back");
     if (slot < 0 || slot >= (int)ll.qrep.size()) return set_err(YM_ERR_INVALID, "no such query slot in the last call");
     const int n_out = (ctrig != nullptr) + (starts != nullptr) + (flags != nullptr) + (entries != nullptr) + (rbox != nullptr);
     if (n_out != 0 && n_out != 5) return set_err(YM_ERR_INVALID, "all five arrays or none");
@@ -128,14 +127,16 @@ int ym_debug_pair_lists(ym_matcher *m, int slot, ym_pair_list_info *info, double
 //    4  extra dynamic LDS bytes per direct-correlate block        5  beam chunks per angle of the direct correlate
 //    9  chunk-waves per direct-correlate block (1, 2, 4)        23  0 = single matches wait for a stream event instead of polling
 //   26  512 = the single-item prepare kernel with 512 threads   29  0 = the region path's pair lists on the call's own stream
-//   33  experimental forms: loader / gather waves idle (timing) 34  blocks that share an (item, angle block)'s regions (0 = by batch size)
-//   35  batch size from which experimental form 3 is default    36  the raster does not write the row-major window (timing only)
+//   34  blocks that share an (item, angle block)'s regions (0 = by batch size)
+//   36  the raster does not write the row-major window (timing only)
 //   38  unused dynamic LDS bytes per region-correlate block     40  batch size from which batches get raster work lists (48)
-//   42  the region correlate's threshold alone (0 = 48)         44  batch size from which experimental form 5 is default
+//   42  the region correlate's threshold alone (0 = 48)
+// (0, 32, 33, 35, 43 and 44 chose between correlate forms that are gone: YM_ERR_INVALID)
 int ym_debug_option(ym_matcher *m, int option, int value) {
     if (m) { m->cache_gen++; m->list_key_valid = false; } // (whatever the option changes, no earlier plan or pair list is reused)
     if (!m) return set_err(YM_ERR_INVALID, "null matcher");
-    if (option == 0) return set_err(YM_ERR_INVALID, "debug option 0 (an experimental correlate form) no longer exists");
+    if (option == 0 || option == 32 || option == 33 || option == 35 || option == 43 || option == 44)
+        return set_err(YM_ERR_INVALID, "debug option %d (an experimental correlate form) no longer exists", option);
     else if (option == 2) m->full_raster = value;
     else if (option == 3) m->corr_u = value;
     else if (option == 4) m->corr_pad_lds = value;
@@ -166,28 +167,8 @@ int ym_debug_option(ym_matcher *m, int option, int value) {
     else if (option == 21) m->corr_fuse_score = value;
     else if (option == 45) { m->list_cache_on = value != 0; m->list_key_valid = false; }
     else if (option == 46) m->yag_fast = value < 0 ? 0 : value > 2 ? 1 : value;
-    else if (option == 43) m->rg2_h = value;
     else if (option == 47) m->map_chunk_forced = value > 0 ? value : 0;
-    else if (option == 44) {
-#ifndef YM_EXPERIMENTAL
-        return set_err(YM_ERR_UNSUPPORTED, "correlate_region2_kernel is compiled only into builds made with -DYM_EXPERIMENTAL");
-#endif
-        m->rg2_min_batch = value > 0 ? value : 1 << 30;
-    }
-    else if (option == 32) {
-#ifndef YM_EXPERIMENTAL
-        if (value >= 2) return set_err(YM_ERR_UNSUPPORTED, "correlate form %d is compiled only into builds made with -DYM_EXPERIMENTAL", value);
-#endif
-        m->corr_region_form = value;
-    }
-    else if (option == 33) m->corr_region_dbg = value;
     else if (option == 34) m->corr_region_rsplit = value;
-    else if (option == 35) {
-#ifndef YM_EXPERIMENTAL
-        return set_err(YM_ERR_UNSUPPORTED, "correlate_item_kernel is compiled only into builds made with -DYM_EXPERIMENTAL");
-#endif
-        m->item_min_batch = value;
-    }
     else if (option == 36) m->raster_planes_only = value;
     else if (option == 37) m->raster_no_rowtab = value;
     else if (option == 38) m->corr_region_pad_lds = value;

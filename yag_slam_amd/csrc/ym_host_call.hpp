@@ -48,11 +48,11 @@ int launch_call_body(ym_matcher *m, Slot &slot) {
         ym_matcher::ListKey key;
         std::memset(&key, 0, sizeof key);
         const CallScan *q0 = P.n_qslots == 1 ? &slot.call.scans[slot.call.items[0].query] : nullptr;
-        bool keyed = q0 && q0->id != 0 && m->list_cache_on && !P.stamps && !P.rg_ws;
+        bool keyed = q0 && q0->id != 0 && m->list_cache_on && !P.stamps;
         if (keyed) {
             key.qid = q0->id; key.pose[0] = q0->pose[0]; key.pose[1] = q0->pose[1]; key.pose[2] = q0->pose[2];
             key.g = P.g; key.lc = P.lc; key.nw = P.rg_nw; key.parts = P.rg_parts; key.nrx = P.rg_nrx; key.nry = P.rg_nry;
-            key.rg_h = P.rg2 ? P.rg2_h : YM_RG_H; key.force = m->corr_region; key.nregions = P.rg_nregions; key.ng = P.rg_ng;
+            key.rg_h = YM_RG_H; key.force = m->corr_region; key.nregions = P.rg_nregions; key.ng = P.rg_ng;
             key.es = P.rg_entries_stride; key.ss = P.rg_starts_stride;
             key.pe = m->rg_entries.p; key.ps = m->rg_starts.p; key.pb = m->rg_rbox.p;
             P.lists_cached = m->list_key_valid && std::memcmp(&key, &m->list_key, sizeof key) == 0;
@@ -109,8 +109,7 @@ int launch_call_body(ym_matcher *m, Slot &slot) {
     if (P.region26 && P.k_end > P.k_begin) { // (ym_debug_pair_lists: the lists' geometry, a handful of integers per enqueue)
         const ym::RegionArgs r = region_args(m, P);
         ym_matcher::ListsLast &ll = m->lists_last;
-        ll.whole = P.rg_ws || P.rg2 || P.rg_item || P.rg_pool;
-        ll.nt = P.lc.nt; ll.lnw = r.lnw; ll.lparts = r.lparts; ll.nbins = r.nbins; ll.nrx = r.nrx; ll.nry = r.nry; ll.nregions = r.nregions;
+        ll.nt = P.lc.nt; ll.lnw = r.nw; ll.lparts = r.parts; ll.nbins = r.nbins; ll.nrx = r.nrx; ll.nry = r.nry; ll.nregions = r.nregions;
         ll.rg_h = r.rg_h; ll.rg_cls = r.rg_cls; ll.rg_zero = r.rg_zero; ll.ng = r.ng;
         ll.entries_pstride = r.entries_pstride; ll.entries_stride = r.entries_stride; ll.starts_stride = r.starts_stride; ll.rbox_stride = r.rbox_stride;
         ll.qrep.swap(P.qrep); // (the plan ends here: no copy)

@@ -194,39 +194,18 @@ ym::RegionArgs region_args(ym_matcher *m, const CallPlan &P) {
     r.starts = m->rg_starts.p; r.starts_stride = P.rg_starts_stride; r.partial = m->partial.p; r.partial_stride = P.partial_stride;
     r.rbox = m->rg_rbox.p; r.rbox_stride = (size_t)P.rg_nregions * P.rg_parts; r.nw = P.rg_nw; r.parts = P.rg_parts;
     r.nt_stride = P.nt_stride; r.dim_stride = P.dim_stride; r.nrx = P.rg_nrx; r.nry = P.rg_nry; r.ng = P.rg_ng; r.nbins = P.rg_nbins;
-    r.force_irregular = (m->corr_region == 2 || m->corr_region == 3) ? m->corr_region - 1 : 0; r.pad = m->corr_region_dbg; r.stamps = P.stamps;
+    r.force_irregular = (m->corr_region == 2 || m->corr_region == 3) ? m->corr_region - 1 : 0; r.stamps = P.stamps;
     r.fuse_score = P.fuse_score ? 1 : 0; r.resp = P.resp; r.sums_stride = P.sums_c; r.blockmax = m->blockmax.p;
     r.probs = P.probs; r.probs_stride = (size_t)P.lc.nx * P.lc.ny; r.n_blocks = P.score_blocks;
-    r.rg_h = YM_RG_H; r.rg_cls = YM_RG_CLS; r.rg_zero = YM_RG_ZERO; r.pad2 = 0;
-#ifdef YM_EXPERIMENTAL
-    r.rg_h = P.rg_ws ? YM_WS_H : YM_RG_H; r.rg_cls = P.rg_ws ? YM_WS_CLS : P.rg_item ? YM_IT_CLS : YM_RG_CLS;
-    r.rg_zero = P.rg_ws ? YM_WS_ZERO : P.rg_item ? YM_IT_ZERO : YM_RG_ZERO;
-#endif
-    if (P.rg2) { r.rg_h = P.rg2_h; r.rg_cls = YM_RG_PITCH * (P.rg2_h + 26); r.rg_zero = 4 * r.rg_cls; }
-    r.pad2 = ((1 << 21) + r.rg_h - 1) / r.rg_h; // bin_kernel: class row / region height as a multiplication (region_entry)
-    r.rg_w = 0; r.rg_pitch = YM_RG_PITCH; r.nregions = P.rg_nregions; r.pad3 = 0;
-    r.walk = m->rg_walk.p; r.nitems = P.B; r.rsplit = P.rg_rsplit; r.pad4 = 0;
-    r.lnw = P.rg_lnw; r.lparts = P.rg_lparts; r.entries_pstride = P.rg_entries_pstride;
-    // teams of `parts` blocks per XCD: two blocks per CU, no more teams than the XCD gets items
-    r.gpx = std::max(1, std::min((2 * std::max(m->n_cus, 8) / 8) / std::max(1, P.rg_parts), (P.B + 7) / 8));
+    r.rg_h = YM_RG_H; r.rg_cls = YM_RG_CLS; r.rg_zero = YM_RG_ZERO;
+    r.rg_h_recip = ((1 << 21) + r.rg_h - 1) / r.rg_h; // bin_kernel: class row / region height as a multiplication (region_entry)
+    r.nregions = P.rg_nregions; r.rsplit = P.rg_rsplit; r.entries_pstride = P.rg_entries_pstride;
     return r;
 }
 
 // bin_kernel, once per query slot of the call: after the prepare stage (item states, hypothesis cells, angle tables)
 int enqueue_region_lists(ym_matcher *m, const CallPlan &P, hipStream_t st) {
     const ym::RegionArgs r = region_args(m, P);
-#ifdef YM_EXPERIMENTAL
-    if (P.rg_lparts == 1 && P.rg_lnw == P.lc.nt && (P.rg_ws || P.rg2 || P.rg_item || P.rg_pool)) { // the round-5 layout: one list of all angles
-        const size_t bin_lds = YM_BIN_LDS_BYTES(P.rg_nbins, P.rg_entries_stride, P.rg_nregions * P.rg_parts);
-        if (bin_lds > m->bin_lds_limit) { // (more than the default 64 KB of dynamic LDS has to be asked for)
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ym::bin_whole_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds));
-            m->bin_lds_limit = bin_lds;
-        }
-        hipLaunchKernelGGL(ym::bin_whole_kernel<false>, dim3(P.n_qslots), dim3(YM_BIN_THREADS), bin_lds, st, r);
-        if (P.rg_ws) hipLaunchKernelGGL(ym::region_walk_kernel, dim3(P.rg_parts, P.n_qslots), dim3(64), 0, st, r);
-        return YM_OK;
-    }
-#endif
     const size_t bin_lds = YM_BINP_LDS_BYTES(P.rg_nbins, P.rg_entries_pstride, P.rg_nregions);
     if (bin_lds > m->binp_lds_limit) { // (more than the default 64 KB of dynamic LDS has to be asked for)
 #define YM_BINP_ATTR(Y, M) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ym::bin_kernel<Y, M>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bin_lds))
@@ -235,8 +214,8 @@ int enqueue_region_lists(ym_matcher *m, const CallPlan &P, hipStream_t st) {
         m->binp_lds_limit = bin_lds;
     }
     // pairs per thread: the instantiation with registers for them (18: scans of up to 1152 readings at eight angles per part)
-    const int per_thread = (P.rg_lnw * P.max_n + YM_BINP_THREADS - 1) / YM_BINP_THREADS;
-    const dim3 bgrid(P.rg_lparts, P.n_qslots);
+    const int per_thread = (P.rg_nw * P.max_n + YM_BINP_THREADS - 1) / YM_BINP_THREADS;
+    const dim3 bgrid(P.rg_parts, P.n_qslots);
 #define YM_BINP_LAUNCH(Y, M) hipLaunchKernelGGL((ym::bin_kernel<Y, M>), bgrid, dim3(YM_BINP_THREADS), bin_lds, st, r)
     if (P.yag) { if (per_thread <= 18) YM_BINP_LAUNCH(true, 18); else if (per_thread <= 32) YM_BINP_LAUNCH(true, 32); else YM_BINP_LAUNCH(true, 64); }
     else { if (per_thread <= 18) YM_BINP_LAUNCH(false, 18); else if (per_thread <= 32) YM_BINP_LAUNCH(false, 32); else YM_BINP_LAUNCH(false, 64); }
@@ -283,43 +262,6 @@ int enqueue_correlate(ym_matcher *m, const CallPlan &P) {
         else if (!P.lists_cached && (rc = enqueue_region_lists(m, P, st))) return rc;
         if ((rc = prof_begin(m, 0, &ev_k))) return rc;
         const dim3 rgrid(P.rg_parts * P.rg_rsplit, P.B);
-#ifdef YM_EXPERIMENTAL
-        if (P.rg2) {
-            const size_t lds = (size_t)r.rg_zero + 26 * YM_RG_PITCH + 32 + (size_t)m->corr_region_pad_lds;
-            if (lds > m->rg2_lds_limit) { // (more than the default 64 KB of dynamic LDS has to be asked for)
-                const int want = 144 * 1024; // (the 160 KB of a CU less the kernel's static 15 KB)
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ym::correlate_region2_kernel<80>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ym::correlate_region2_kernel<100>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ym::correlate_region2_kernel<128>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-                m->rg2_lds_limit = (size_t)want;
-            }
-            if (P.rg2_h == 80) hipLaunchKernelGGL(ym::correlate_region2_kernel<80>, rgrid, dim3(64 * YM_R2_NW), lds, st, r);
-            else if (P.rg2_h == 100) hipLaunchKernelGGL(ym::correlate_region2_kernel<100>, rgrid, dim3(64 * YM_R2_NW), lds, st, r);
-            else hipLaunchKernelGGL(ym::correlate_region2_kernel<128>, rgrid, dim3(64 * YM_R2_NW), lds, st, r);
-            return prof_end(m, ev_k);
-        }
-#endif
-#ifdef YM_EXPERIMENTAL // (the three forms that lost to correlate_region_kernel: profiles/r04_region_study.md; option 32 refuses them otherwise)
-        if (P.rg_item) {
-            const size_t lds = YM_IT_ACC_BYTES(P.lc.nt);
-            if (!m->item_lds_set) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(ym::correlate_item_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)YM_IT_ACC_BYTES(YM_IT_MAX_NT)));
-                m->item_lds_set = true;
-            }
-            hipLaunchKernelGGL(ym::correlate_item_kernel, dim3(P.B), dim3(64 * YM_IT_NW), lds, st, r);
-            return prof_end(m, ev_k);
-        }
-        if (P.rg_pool) {
-            if (P.win_only) hipLaunchKernelGGL(ym::correlate_pool_kernel<true>, rgrid, dim3(64 * YM_PL_NW), 0, st, r);
-            else hipLaunchKernelGGL(ym::correlate_pool_kernel<false>, rgrid, dim3(64 * YM_PL_NW), 0, st, r);
-            return prof_end(m, ev_k);
-        }
-        if (P.rg_ws) {
-            hipLaunchKernelGGL(ym::correlate_region_ws_kernel, dim3(8 * r.gpx * P.rg_parts), dim3(64 * (YM_WS_NG + YM_WS_NL)), 0, st, r);
-            hipLaunchKernelGGL(ym::region_percell_kernel, rgrid, dim3(64 * YM_WS_NG), 0, st, r);
-            return prof_end(m, ev_k);
-        }
-#endif
         switch (P.rg_nw) {
         case 4: hipLaunchKernelGGL(ym::correlate_region_kernel<4>, rgrid, dim3(256), 0, st, r); break;
         case 5: hipLaunchKernelGGL(ym::correlate_region_kernel<5>, rgrid, dim3(320), 0, st, r); break;
@@ -356,18 +298,10 @@ int enqueue_correlate(ym_matcher *m, const CallPlan &P) {
         hipLaunchKernelGGL(ym::gbin_pieces_kernel<true>, pgrid, dim3(YM_GBIN_THREADS), 0, st, r);
         if (P.ga_lds > m->ga_lds_limit) { // (more than the default 64 KB of dynamic LDS has to be asked for)
             const int want = (int)std::min<size_t>(160 * 1024, P.ga_lds);
-            // (the instantiations for three blocks of eight waves per CU -- 80 VGPRs -- park the staging registers in scratch: 11 GB of
-            //  scratch traffic per launch of 4096 loop-lattice items for 4 % of the kernel's time; only in builds with -DYM_EXPERIMENTAL)
-#ifdef YM_EXPERIMENTAL
-#define YM_GA_512(NA, NP) reinterpret_cast<const void *>(ym::gather_kernel<NA, NP, YM_GA_PER, 512>)
-#else
-#define YM_GA_512(NA, NP) reinterpret_cast<const void *>(ym::gather_kernel<NA, NP, YM_GA_PER>)
-#endif
-            const void *kernels[21] = {
-#define YM_GA_BOTH(NA, NP) reinterpret_cast<const void *>(ym::gather_kernel<NA, NP, YM_GA_PER>), YM_GA_512(NA, NP), reinterpret_cast<const void *>(ym::gather_percell_kernel<NA, NP>)
+            const void *kernels[14] = {
+#define YM_GA_BOTH(NA, NP) reinterpret_cast<const void *>(ym::gather_kernel<NA, NP, YM_GA_PER>), reinterpret_cast<const void *>(ym::gather_percell_kernel<NA, NP>)
                 YM_GA_BOTH(1, 1), YM_GA_BOTH(2, 1), YM_GA_BOTH(3, 1), YM_GA_BOTH(4, 1), YM_GA_BOTH(1, 2), YM_GA_BOTH(2, 2), YM_GA_BOTH(1, 3)};
 #undef YM_GA_BOTH
-#undef YM_GA_512
             for (const void *k : kernels) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, want));
             m->ga_lds_limit = P.ga_lds;
         }
@@ -376,14 +310,8 @@ int enqueue_correlate(ym_matcher *m, const CallPlan &P) {
         // gather_kernel takes the items whose lists exist and whose hypothesis cells form a lattice (all of them, but for fp
         // rounding accidents and oversized lists), gather_percell_kernel the others: each returns at once from the other's
         // items
-#ifdef YM_EXPERIMENTAL
-#define YM_GA_LAUNCH_512(NA, NP) if (P.ga_nwv <= 8 && m->corr_region_form == 6) hipLaunchKernelGGL((ym::gather_kernel<NA, NP, YM_GA_PER, 512>), rgrid, rblock, P.ga_lds, st, r); else
-#else
-#define YM_GA_LAUNCH_512(NA, NP)
-#endif
 #define YM_GA_LAUNCH(NA, NP)                                                                                               \
     do {                                                                                                                   \
-        YM_GA_LAUNCH_512(NA, NP)                                                                                           \
         hipLaunchKernelGGL((ym::gather_kernel<NA, NP, YM_GA_PER>), rgrid, rblock, P.ga_lds, st, r);                        \
         hipLaunchKernelGGL((ym::gather_percell_kernel<NA, NP>), rgrid, rblock, P.ga_lds, st, r);                           \
     } while (0)
@@ -397,7 +325,6 @@ int enqueue_correlate(ym_matcher *m, const CallPlan &P) {
             else YM_GA_LAUNCH(2, 2);
         } else YM_GA_LAUNCH(1, 3);
 #undef YM_GA_LAUNCH
-#undef YM_GA_LAUNCH_512
         return prof_end(m, ev_k);
     }
     if ((rc = prof_begin(m, 0, &ev_k))) return rc;

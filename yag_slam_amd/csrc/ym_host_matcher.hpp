@@ -104,10 +104,8 @@ struct ym_matcher {
     DevBuf<uint16_t> rg_entries; // region correlate: per query slot of a call the (beam, angle) pairs sorted by region
     DevBuf<int32_t> rg_starts;
     DevBuf<uint32_t> rg_rbox;    // per query slot, region and angle block: the box its patches read of the region
-    DevBuf<uint32_t> rg_walk;    // per query slot and angle block: the walk of the wave-specialised region correlate (region_walk_kernel)
     int n_cus = 0;               // compute units of the device
-    size_t bin_lds_limit = 64 * 1024; // dynamic LDS bin_whole_kernel may use so far (experimental builds)
-    size_t binp_lds_limit = 64 * 1024; // ... and bin_kernel
+    size_t binp_lds_limit = 64 * 1024; // dynamic LDS bin_kernel may use so far
     int chain_margin = 1;        // tiles (64 cells) added around the predicted raster rectangle of a chained step
     uint64_t cache_gen = 1;      // bumped whenever the point cache changes (entries created, re-posed, dropped) or an option is set
     int64_t seq_segments = 0, seq_faults = 0, seq_sync_steps = 0; // ym_map_sequence: chained segments, those cut short, synchronous steps
@@ -121,16 +119,12 @@ struct ym_matcher {
     bool use_scan_structure = true; // base scans' trigger chains come from ym_scan_create's structure_kernel where that is exact
     bool poll_completion = true; // single matches: the host polls a pinned word instead of waiting for the stream event
     int corr_region_nw = 0;  // development: waves (= angles) per region-correlate block
-    int item_min_batch = 1 << 30; // batches from this many items on take correlate_item_kernel
-    bool item_lds_set = false;
     int raster_planes_only = 0; // timing experiment (option 36): the raster does not write the row-major window
     int raster_no_rowtab = 0;   // tests (option 37): the raster's row pass by bit scans instead of its tables
     int corr_region_rsplit = 0; // 0 = by batch size, 1 = never split an item's regions over blocks, n = always n blocks
     int tile_list_min_batch = 48; // option 40: batches from this size on get raster work lists (tiles_kernel)
     int keep_planes = 0;         // option 39: 1 = every call writes the column planes and the region correlate stages from them
     int corr_region_pad_lds = 0; // development (option 38): dynamic LDS bytes the region correlate is launched with and does not use (fewer blocks per CU)
-    int corr_region_dbg = 0;  // development (timing only): 1 = the loader waves move nothing, 2 = the gather waves gather nothing
-    int corr_region_form = 0; // 2 = the wave-specialised region correlate (gather waves + loader waves) instead of correlate_region_kernel
     // the pair lists of the last single-query call that built them: what they were built from.  A call with the same key finds them
     // in the list buffers and builds nothing (no bin_kernel, no second stream, no join) -- they depend on the query's readings and
     // pose, the window and the lattice alone, like the projected points the point cache keeps (round 5; option 45 = 0: off)
@@ -141,9 +135,6 @@ struct ym_matcher {
     ListKey list_key;
     bool list_key_valid = false, list_cache_on = true;
     int64_t list_cache_hits = 0;
-    int rg2_min_batch = 1 << 30; // batches from this many items on take correlate_region2_kernel (option 32 = 5: always where it can)
-    int rg2_h = 128;          // option 43: class rows a region of correlate_region2_kernel owns (80, 100 or 128)
-    size_t rg2_lds_limit = 0;
     int corr_fuse_score = 0; // tests: 2 = the region correlate never scores itself (score_kernel does)
     // gather correlate: per query slot of a call the (beam, angle) units sorted by region, the bin table, the work
     // lists and the counters they are built with; the lane -> (row, segment) table of the lattice
@@ -229,7 +220,7 @@ struct ym_matcher {
     // what ym_debug_pair_lists needs of the last call whose correlate was correlate_region_kernel: the geometry its pair lists were built
     // for (the plan does not outlive the enqueue) and the item that stands for each query slot
     struct ListsLast {
-        bool valid = false, whole = false; // whole: the one-part layout of the experimental forms
+        bool valid = false;
         int32_t nt = 0, lnw = 0, lparts = 0, nbins = 0, nrx = 0, nry = 0, nregions = 0, rg_h = 0, rg_cls = 0, rg_zero = 0, ng = 0;
         size_t entries_pstride = 0, entries_stride = 0, starts_stride = 0, rbox_stride = 0;
         std::vector<int32_t> qrep;

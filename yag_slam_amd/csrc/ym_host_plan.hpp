@@ -161,24 +161,8 @@ int plan_sizes(ym_matcher *m, Slot &slot, CallPlan &P) {
         P.rg_nw = m->corr_region_nw > 0 ? std::min(m->corr_region_nw, 16) : lc.nt <= 8 ? lc.nt : 8;
         if (P.rg_nw < 4 || P.rg_nw == 9 || (P.rg_nw > 11 && P.rg_nw != 16)) P.rg_nw = lc.nt <= 4 ? 4 : 8;
         P.rg_parts = (lc.nt + P.rg_nw - 1) / P.rg_nw;
-        int rg_h = YM_RG_H;
-#ifdef YM_EXPERIMENTAL // (the forms that lost to correlate_region_kernel: scripts/exp/forms, `make experimental`)
-        // the wave-specialised form: blocks of 8, 11 or 12 gather waves (21 angles = 11 + 10) + 4 loader waves, regions of one class image
-        P.rg_ws = m->corr_region_nw == 0 && m->corr_region_form == 2; // (measured slower than the first form: opt-in, option 32 = 2)
-        if (P.rg_ws) { // (8 gather waves + 8 loader waves per block, two blocks per CU)
-            P.rg_nw = YM_WS_NG;
-            P.rg_parts = (lc.nt + YM_WS_NG - 1) / YM_WS_NG;
-        }
-        // round 5: large batches on up to 24 angles -- sixteen waves per block, two or three per angle (ym_k_region2.hpp)
-        // (below two blocks per CU the regions of the first form are dealt out to more blocks instead: rsplit)
-        P.rg2 = !P.rg_ws && m->corr_region_nw == 0 && !m->keep_planes && lc.nt > 0 &&
-                (m->corr_region_form == 5 || (m->corr_region_form == 0 && B >= m->rg2_min_batch && 3 * B >= 2 * m->n_cus));
-        P.rg2_h = m->rg2_h == 80 ? 80 : m->rg2_h == 100 ? 100 : 128;
-        if (P.rg2) { P.rg_nw = lc.nt <= 8 ? lc.nt : 8; P.rg_parts = (lc.nt + P.rg_nw - 1) / P.rg_nw; }
-        rg_h = P.rg_ws ? YM_WS_H : P.rg2 ? P.rg2_h : YM_RG_H;
-#endif
         P.rg_nrx = (half_w + YM_RG_W - 1) / YM_RG_W;
-        P.rg_nry = (half_w + rg_h - 1) / rg_h;
+        P.rg_nry = (half_w + YM_RG_H - 1) / YM_RG_H;
         P.rg_nregions = P.rg_nrx * P.rg_nry;
         // sets of 16-bit sums per (item, angle): room for the padding of the entry lists (an item that needs more is scored
         // by the per-cell path)
@@ -190,37 +174,17 @@ int plan_sizes(ym_matcher *m, Slot &slot, CallPlan &P) {
         if (P.region26) {
             // fewer blocks than three per CU: deal every (item, angle block)'s regions out to several blocks (64 chains: the
             // kernel 121 -> 65 us with four, the enqueue 236 -> 205 us; 128 chains 317 -> 295 with two; scripts/dev/rsplit_time.py)
-            P.rg_rsplit = 1;
-            if (!P.rg_ws && !P.rg2 && m->corr_region_rsplit != 1 && m->corr_region_form != 3 && m->corr_region_form != 4) {
-                const int blocks = B * P.rg_parts;
-                P.rg_rsplit = m->corr_region_rsplit > 1 ? m->corr_region_rsplit : std::max(1, std::min(8, (3 * m->n_cus) / std::max(1, blocks)));
-            }
+            const int blocks = B * P.rg_parts;
+            P.rg_rsplit = m->corr_region_rsplit == 1 ? 1 : m->corr_region_rsplit > 1 ? m->corr_region_rsplit : std::max(1, std::min(8, (3 * m->n_cus) / std::max(1, blocks)));
             P.n_groups = P.rg_ng * P.rg_rsplit;
-#ifdef YM_EXPERIMENTAL
-            // batches that fill the chip with one block per item: correlate_item_kernel (option 32: 1 = never, 3 = always)
-            P.rg_item = !P.rg_ws && !P.rg2 && P.rg_rsplit == 1 && lc.nt <= YM_IT_MAX_NT && m->corr_region_form != 1 &&
-                        (m->corr_region_form == 3 || B >= m->item_min_batch);
-            P.n_groups = P.rg_ng * P.rg_rsplit * (P.rg2 ? YM_R2_MAX_WPA : 1); // (rg2: every slice of an angle writes its own sets)
-            // the pooled form (option 32 = 4): large batches of at most 22 angles
-            P.rg_pool = !P.rg_ws && !P.rg2 && !P.rg_item && P.rg_rsplit == 1 && m->corr_region_form == 4 && lc.nt <= 2 * YM_PL_MAX_NK && m->corr_region_nw == 0;
-            if (P.rg_pool) {
-                P.rg_nw = lc.nt <= YM_PL_MAX_NK ? lc.nt : (lc.nt + 1) / 2;
-                P.rg_parts = (lc.nt + P.rg_nw - 1) / P.rg_nw;
-            }
-#endif
-            // the default form at eight waves stages from the window: the raster of such a call writes no planes (option 39 = 1: keeps them)
-            P.win_only = !P.rg_ws && !P.rg_item && (P.rg_nw == 8 || P.rg_pool || P.rg2) && !m->keep_planes;
-            // (+ the padding of the bins that hold work; a query whose list still does not fit takes the per-cell path)
-            // 10 % over the pairs themselves (measured on the bench scans: 5 %)
-            // (the wave-specialised form's bins are a third more and hold less each: 20 %)
-            // the lists: one part per angle block of the correlate (the experimental forms read one list of all angles)
-            const bool whole = P.rg_ws || P.rg2 || P.rg_item || P.rg_pool;
-            P.rg_lnw = whole ? lc.nt : P.rg_nw;
-            P.rg_lparts = whole ? 1 : P.rg_parts;
-            P.rg_nbins = P.rg_nregions * P.rg_lnw;
-            P.rg_entries_pstride = std::min((size_t)YM_RG_MAX_ENTRIES, ((size_t)P.rg_lnw * max_n * 11 / 10 + 63) / 64 * 64);
-            P.rg_entries_stride = P.rg_entries_pstride * P.rg_lparts; // (positions are 16-bit in the correlate: checked on the device per part)
-            P.rg_starts_stride = ((size_t)P.rg_lparts * (P.rg_nbins + 1) + P.rg_lparts + 15) / 16 * 16;
+            // at eight waves the correlate stages from the window: the raster of such a call writes no planes (option 39 = 1: keeps them)
+            P.win_only = P.rg_nw == 8 && !m->keep_planes;
+            // the lists: one part per angle block of the correlate, 10 % over the pairs themselves for the padding of the bins that
+            // hold work (measured on the bench scans: 5 %); a query whose list still does not fit takes the per-cell path
+            P.rg_nbins = P.rg_nregions * P.rg_nw;
+            P.rg_entries_pstride = std::min((size_t)YM_RG_MAX_ENTRIES, ((size_t)P.rg_nw * max_n * 11 / 10 + 63) / 64 * 64);
+            P.rg_entries_stride = P.rg_entries_pstride * P.rg_parts; // (positions are 16-bit in the correlate: checked on the device per part)
+            P.rg_starts_stride = ((size_t)P.rg_parts * (P.rg_nbins + 1) + P.rg_parts + 15) / 16 * 16;
         }
     }
     // Other batches on lattices of at most 48 x 64: the general form (ym_k_gather.hpp).
@@ -335,11 +299,7 @@ int plan_sizes(ym_matcher *m, Slot &slot, CallPlan &P) {
     if ((rc = m->qnp.ensure(B))) return rc;
     if ((rc = m->cells.ensure((size_t)B * max_base * max_n))) return rc;
     if ((rc = m->bbox.ensure((size_t)B * max_base * YM_N_BOXES(max_n)))) return rc;
-    size_t window_slack = YM_RG_WINDOW_SLACK(g.pitch), planes_slack = YM_RG_PLANES_SLACK(g.pitch / 2);
-#ifdef YM_EXPERIMENTAL
-    window_slack = std::max(window_slack, YM_R2_WINDOW_SLACK(g.pitch, 128));
-    planes_slack = std::max(planes_slack, YM_WS_PLANES_SLACK(g.pitch / 2));
-#endif
+    const size_t window_slack = YM_RG_WINDOW_SLACK(g.pitch), planes_slack = YM_RG_PLANES_SLACK(g.pitch / 2);
     if ((rc = m->grid.ensure((size_t)B * P.grid_stride + window_slack))) return rc;
     if ((rc = m->planes.ensure((size_t)B * P.grid_stride + std::max(planes_slack, YM_GA_PLANES_SLACK(g.pitch / 2, std::max(P.ga_rows, P.ga_nry + P.ga_H), lc.ny, P.ga_P))))) return rc;
     if ((rc = m->ctrig.ensure((size_t)B * P.nt_stride))) return rc;
@@ -359,7 +319,7 @@ int plan_sizes(ym_matcher *m, Slot &slot, CallPlan &P) {
     if ((rc = m->probs.ensure((size_t)B * lc.nx * lc.ny))) return rc;
     P.resp = call.ext_resp ? call.ext_resp : m->resp.p;
     P.probs = call.ext_probs ? call.ext_probs : m->probs.p;
-    P.fuse_score = P.region26 && !P.rg_ws && P.rg_rsplit == 1 && !m->keep_sums && m->corr_fuse_score != 2 && !yag; // (yagpy scores the integer sums its own way)
+    P.fuse_score = P.region26 && P.rg_rsplit == 1 && !m->keep_sums && m->corr_fuse_score != 2 && !yag; // (yagpy scores the integer sums its own way)
     P.k_begin = call.slice ? std::max(0, call.k_begin) : 0;
     P.k_end = call.slice ? std::min(lc.nt, call.k_end) : lc.nt;
     if (call.slice && (yag || B != 1)) return set_err(YM_ERR_UNSUPPORTED, "angle-sliced matches are single Karto matches");
@@ -495,9 +455,6 @@ int plan_jobs(ym_matcher *m, Slot &slot, CallPlan &P, bool replay = false) {
             if ((rc = m->rg_entries.ensure((size_t)n_q * P.rg_entries_stride))) return rc;
             if ((rc = m->rg_starts.ensure((size_t)n_q * P.rg_starts_stride))) return rc;
             if ((rc = m->rg_rbox.ensure((size_t)n_q * P.rg_nregions * P.rg_parts))) return rc;
-#ifdef YM_EXPERIMENTAL
-            if (P.rg_ws && (rc = m->rg_walk.ensure((size_t)n_q * P.rg_parts * YM_WS_WALK_WORDS))) return rc;
-#endif
         }
         if (P.region) { // the gather correlate's lists: one set per query slot
             if ((rc = m->ga_units.ensure((size_t)n_q * P.ga_units_stride))) return rc;

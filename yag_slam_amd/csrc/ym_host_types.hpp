@@ -216,14 +216,8 @@ struct CallPlan {
     bool fuse_score = false;  // ... also scores (no score_kernel launch)
     int rg_nrx = 0, rg_nry = 0, rg_ng = 1, rg_nbins = 0, rg_nw = 7, rg_parts = 1, rg_nregions = 0;
     int rg_rsplit = 1;  // blocks that share the regions of an (item, angle block) on small batches
-    bool rg_item = false; // correlate_item_kernel: one block of 16 waves per item, the item's sums in LDS
-    bool rg_pool = false; // correlate_pool_kernel: two blocks of 12 waves per item, a region's patches dealt evenly, 16-bit sums in LDS
     bool win_only = false; // the region correlate stages from the row-major window and the raster does not write the planes
-    bool rg_ws = false; // the wave-specialised region correlate (gather waves + loader waves, regions of YM_WS_H rows)
-    bool rg2 = false;   // correlate_region2_kernel (round 5): sixteen waves per block, several waves per angle, regions rg2_h rows high
-    int rg2_h = 0;
-    size_t rg_entries_stride = 0, rg_starts_stride = 0, rg_entries_pstride = 0;
-    int rg_lnw = 0, rg_lparts = 1; // the pair lists are built per block of rg_lnw angles (ym_k_region.hpp, bin_kernel); the experimental forms: one part of all
+    size_t rg_entries_stride = 0, rg_starts_stride = 0, rg_entries_pstride = 0; // the pair lists: one part per block of rg_nw angles (ym_k_region.hpp, bin_kernel)
     // batches on other lattices up to 48 x 64, or with merged offsets: the LDS gather correlate (ym_k_gather.hpp), which
     // always scores its sums
     bool region = false;

@@ -35,9 +35,6 @@ namespace ym {
 #define YM_GA_FLUSH 652     // weight (patches x multiplicity) a set of 16-bit sums holds: 652 x 100 < 65536
 #define YM_GA_MULT 0x40000000 // flag on a run's first-unit entry: some unit of the run has a multiplicity above 1
 #define YM_GBIN_THREADS 256
-#ifndef YM_GA_OCC512
-#define YM_GA_OCC512 6 // waves per SIMD blocks of up to 512 threads are compiled for (6: three blocks of eight waves per CU)
-#endif
 #ifndef YM_GA_PER
 #define YM_GA_PER 4          // 16-byte chunks of a class image a thread copies per work item
 #endif
@@ -467,10 +464,8 @@ __device__ __forceinline__ void ga_score(const GatherArgs &a, int b, int NT, int
 // class image as PER 16-byte chunks per thread, one unit and one bin-row entry per thread) are in flight in registers;
 // they go to LDS between the two barriers that end the gather.  (LDS-DMA was measured for this copy and lost: a wave
 // that issues global_load_lds is held for hundreds of cycles per instruction, profiles/r03_lds_dma_experiment.md.)
-// MAXT: the largest block the instantiation is launched with: blocks of up to eight waves (the usual case: one angle per wave,
-// about eight angles per block) are compiled for three blocks per CU (80 VGPRs; round 5 -- until then 104 VGPRs left two).
-template <int NA, int NP, int PER, int MAXT = 1024>
-__global__ __launch_bounds__(MAXT, MAXT <= 512 ? YM_GA_OCC512 : 4) void gather_kernel(GatherArgs a) {
+template <int NA, int NP, int PER>
+__global__ __launch_bounds__(1024, 4) void gather_kernel(GatherArgs a) {
     YM_GA_SETUP((int)(blockDim.x >> 6));
     if (!(st.regular[0] && a.force_irregular != 1 && starts[2 * nbins2] >= 0)) return; // gather_percell_kernel's item
     const int NT = 64 * NWV;

@@ -223,7 +223,7 @@ __global__ __launch_bounds__(NT) void raster_kernel(RasterArgs a) {
     auto stamp = [&](const YmCell cw) {
         const int2 c2 = ym_cell_halves(cw); // ("no cell": an x no tile's halo reaches -- lo_x >= -YM_MAX_KERNEL_HALF)
         const int lx = c2.x - lo_x, ly = c2.y - lo_y;
-        if ((YM_WIDE_CELLS ? c2.x != YM_CELL_NONE : true) && lx >= 0 && lx < OW && ly >= 0 && ly < OH) {
+        if (lx >= 0 && lx < OW && ly >= 0 && ly < OH) {
             atomicOr(&occ32[row_words(ly, lx >> 5)], 1u << (lx & 31));
             any = 1;
         }

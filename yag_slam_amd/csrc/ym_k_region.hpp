@@ -74,11 +74,6 @@ static_assert(16 * YM_RG_SEGS >= YM_RG_W + 2 * YM_RG_G + 3 && YM_RG_PITCH >= 16 
 #define YM_RG_MAX_REGIONS 96                   // regions with work a block of correlate_region_kernel can list
 #define YM_RG_MAX_ENTRIES 28672
 #define YM_RG_FLUSH 652                       // patches per set of 16-bit sums: 652 x 100 < 65536 (a multiple of four)
-#define YM_BIN_THREADS 1024
-#ifndef YM_BIN_MIN_WAVES
-#define YM_BIN_MIN_WAVES 8 // waves per SIMD the compiler must leave room for: 8 = two blocks per CU (64 VGPRs)
-#endif
-#define YM_BIN_LDS_BYTES(nbins, entries, nboxes) ((size_t)(YM_BIN_THREADS / 64 + YM_MAX_COARSE_NT + YM_RG_MAX_BINS / 32 + 1) * 4 + (size_t)(nbins) * 8 + ((size_t)(entries) * 2 + 15) / 16 * 16 + (size_t)(nboxes) * 16)
 
 struct RegionArgs {
     YmGeom g;
@@ -92,7 +87,7 @@ struct RegionArgs {
     const int32_t *qrep;    // [n_qslots] an item that uses the query slot
     uint16_t *entries;      // [Q][entries_stride]: LDS offset of the patch's first byte in the staged region, sorted by bin; one
     size_t entries_stride;  // list per QUERY SLOT of the call (the pairs depend on the query alone, not on the chain)
-    int32_t *starts;        // [Q][starts_stride]: first entry of bin (region * nt + angle); [nbins] = total, or -1: no list
+    int32_t *starts;        // [Q][starts_stride]: per list part the first entry of every bin, then the parts' flags (entries_pstride below)
     size_t starts_stride;
     // [Q][rbox_stride]: per (region, block of nw angles) the box of its patches' origins inside the region, rmin | rmax << 8 |
     // xmin << 16 | xmax << 24 (class rows and bytes): a correlate block stages only the rows and 16-byte segments its own
@@ -111,25 +106,17 @@ struct RegionArgs {
     double *blockmax;        // [B][n_blocks], block = (angle, YM_SCORE_THREADS cells)
     double *probs;           // [B][ny*nx] max over theta per (x, y); zeroed by the prepare stage
     size_t probs_stride;
-    int32_t n_blocks, pad;
-    // the region geometry the lists are built for (the two correlate kernels stage regions of different heights): class rows a
-    // region owns, LDS bytes from one class image to the next, LDS offset of the all-zero patch the padding entries point at
-    int32_t rg_h, rg_cls, rg_zero, pad2;
-    // wave-specialised form (rg_w != 0): a region is ONE class image, rg_w class bytes x rg_h class rows, staged at a row
-    // pitch of rg_pitch bytes; region index = (ry * nrx + rx) * 4 + class; nregions = 4 * nrx * nry (else nrx * nry)
-    int32_t rg_w, rg_pitch, nregions, pad3;
-    // wave-specialised form: the walks (region_walk_kernel: [Q][parts][YM_WS_WALK_WORDS]), items of the call, block teams per XCD
-    uint32_t *walk;
-    int32_t nitems, gpx;
-    int32_t rsplit, pad4;    // correlate_region_kernel: blocks that share the regions of an (item, angle block); <= 1: one
+    int32_t n_blocks, nregions; // nregions = nrx * nry
+    // the region geometry the lists are built for: class rows a region owns, LDS bytes from one class image to the next, LDS offset
+    // of the all-zero patch the padding entries point at, and ceil(2^21 / rg_h) (region_entry divides by the height with it)
+    int32_t rg_h, rg_cls, rg_zero, rg_h_recip;
+    int32_t rsplit;          // correlate_region_kernel: blocks that share the regions of an (item, angle block); <= 1: one
     unsigned long long *stamps;
-    // Round 6: the lists of a query are built PER ANGLE BLOCK (lparts blocks of lnw angles, by one bin_kernel block each: a third of the
-    // pairs, 25 KB of LDS, eight waves -- such a block sits beside two region-correlate blocks of another lane, where the round-5 block
-    // (all 21 angles: 65 KB, sixteen waves) pushed two of three off its CU).  starts: [Q][lparts][nbins + 1] first entry of bin
-    // (region * lnw + angle - part * lnw), positions in the query's entry array (part p's entries start at p * entries_pstride);
-    // then [lparts] flags: total of the part, or -1 = no list (that block's angles take the per-cell path).  nbins = regions * lnw.
-    // (lparts = 1, lnw = nt is the round-5 layout: what the experimental forms read, built by bin_whole_kernel.)
-    int32_t lnw, lparts;
+    // The lists of a query are built PER ANGLE BLOCK (parts blocks of nw angles, by one bin_kernel block each: a third of the pairs,
+    // 25 KB of LDS, eight waves -- such a block sits beside two region-correlate blocks of another lane).  starts: [Q][parts][nbins + 1]
+    // first entry of bin (region * nw + angle - part * nw), positions in the query's entry array (part p's entries start at
+    // p * entries_pstride); then [parts] flags: total of the part, or -1 = no list (that block's angles take the per-cell path).
+    // nbins = regions * nw.
     size_t entries_pstride;
 };
 // the starts row of list part p, and whether the part has a list
@@ -137,7 +124,7 @@ __device__ __forceinline__ const int32_t *rg_part_starts(const RegionArgs &a, in
     return a.starts + (size_t)qslot * a.starts_stride + (size_t)p * (a.nbins + 1);
 }
 __device__ __forceinline__ bool rg_part_listed(const RegionArgs &a, int qslot, int p) {
-    return a.starts[(size_t)qslot * a.starts_stride + (size_t)a.lparts * (a.nbins + 1) + p] >= 0;
+    return a.starts[(size_t)qslot * a.starts_stride + (size_t)a.parts * (a.nbins + 1) + p] >= 0;
 }
 
 // the bin of one (beam, angle) pair and its entry = the LDS offset of the patch's first byte once the region is staged;
@@ -151,24 +138,12 @@ __device__ __forceinline__ bool region_entry(const RegionArgs &a, int2 cell, int
     if (X < 0 || Y < 0) return false;
     const unsigned xc = (unsigned)X >> 1, yc = (unsigned)Y >> 1;
     const unsigned cls = (unsigned)((X & 1) | ((Y & 1) << 1));
-#ifdef YM_EXPERIMENTAL
-    if (a.rg_w) { // one class image per region (the wave-specialised form)
-        const unsigned rx = xc / (unsigned)a.rg_w, ry = yc / (unsigned)a.rg_h;
-        if ((int)rx >= a.nrx || (int)ry >= a.nry) return false;
-        region = (int)((ry * (unsigned)a.nrx + rx) * 4u + cls);
-        bin = region * a.lat.nt + k;
-        er = yc - ry * (unsigned)a.rg_h;
-        ex = xc - rx * (unsigned)a.rg_w;
-        entry = er * (unsigned)a.rg_pitch + ex;
-        return true;
-    }
-#endif
-    // (round 5: every product below is of numbers below 2^24 -- v_mul_u32_u24 at the full rate instead of v_mul_lo_u32 at a quarter --
-    //  and the division by the region height is a multiplication by pad2 = ceil(2^21 / rg_h), exact for class rows below 4096:
-    //  the error yc (pad2 rg_h - 2^21) / (2^21 rg_h) stays below 4096 / 2^21 < 1 / rg_h for rg_h <= 255; this kernel is a whole launch of
+    // (every product below is of numbers below 2^24 -- v_mul_u32_u24 at the full rate instead of v_mul_lo_u32 at a quarter --
+    //  and the division by the region height is a multiplication by rg_h_recip = ceil(2^21 / rg_h), exact for class rows below 4096:
+    //  the error yc (rg_h_recip rg_h - 2^21) / (2^21 rg_h) stays below 4096 / 2^21 < 1 / rg_h for rg_h <= 255; this kernel is a whole launch of
     //  4096 blocks when every item of a batch has its own query)
     if (yc >= 4096u) return false; // (never: a window is at most 4073 cells wide)
-    const unsigned rx = xc / (unsigned)YM_RG_W, ry = __umul24(yc, (unsigned)a.pad2) >> 21;
+    const unsigned rx = xc / (unsigned)YM_RG_W, ry = __umul24(yc, (unsigned)a.rg_h_recip) >> 21;
     if ((int)rx >= a.nrx || (int)ry >= a.nry) return false;
     region = (int)(__umul24(ry, (unsigned)a.nrx) + rx);
     bin = (int)__umul24((unsigned)region, (unsigned)(bin_nw < 0 ? a.lat.nt : bin_nw)) + k;
@@ -178,8 +153,8 @@ __device__ __forceinline__ bool region_entry(const RegionArgs &a, int2 cell, int
     return true;
 }
 
-// ---- the pair lists, per angle block (round 6).  grid (lparts, Q): block (p, q) sorts the (beam, angle) pairs of query slot q
-// whose angle lies in [p * lnw, (p + 1) * lnw) by (region, angle); YM_BINP_THREADS threads.  Counting sort in LDS: count, scan, place (the order
+// ---- the pair lists, per angle block.  grid (parts, Q): block (p, q) sorts the (beam, angle) pairs of query slot q
+// whose angle lies in [p * nw, (p + 1) * nw) by (region, angle); YM_BINP_THREADS threads.  Counting sort in LDS: count, scan, place (the order
 // inside a bin is arbitrary: the sums are integers).  GridIndexLookup::ComputeOffsets for the part's coarse angles happens here.
 // Inside a bin the entries are sorted by their byte misalignment (entry & 3; class images and rows are multiples of 4
 // bytes), every run of equal misalignment is padded to an even length and the bin to a multiple of four with entries
@@ -207,7 +182,7 @@ __global__ __launch_bounds__(YM_BINP_THREADS, MAXP <= 18 ? 4 : 2) void bin_kerne
     unsigned (*box)[4] = reinterpret_cast<unsigned (*)[4]>(bin_smem + ((reinterpret_cast<unsigned char *>(ent + a.entries_pstride) - bin_smem) + 15) / 16 * 16); // [nregions] rmin, rmax, xmin, xmax
     const int part = blockIdx.x, qs = blockIdx.y, b = a.qrep[qs], tid = threadIdx.x, lane = tid & 63;
     const YmItemState &st = a.states[b];
-    const int nw = a.lnw, k_lo = part * nw, nk = min(a.lat.nt, k_lo + nw) - k_lo;
+    const int nw = a.nw, k_lo = part * nw, nk = min(a.lat.nt, k_lo + nw) - k_lo;
     const int nq = st.nq;
     const int total = nq * nk;
     const int32_t *cx = a.hypcell + (size_t)b * 2 * a.dim_stride;
@@ -216,7 +191,7 @@ __global__ __launch_bounds__(YM_BINP_THREADS, MAXP <= 18 ? 4 : 2) void bin_kerne
     const double2 *ql = reinterpret_cast<const double2 *>(st.ql);
     const double2 *trig = a.ctrig + (size_t)b * a.nt_stride + k_lo;
     int32_t *starts = a.starts + (size_t)qs * a.starts_stride + (size_t)part * (a.nbins + 1);
-    int32_t *flag = a.starts + (size_t)qs * a.starts_stride + (size_t)a.lparts * (a.nbins + 1) + part;
+    int32_t *flag = a.starts + (size_t)qs * a.starts_stride + (size_t)a.parts * (a.nbins + 1) + part;
     const int pos0 = part * (int)a.entries_pstride; // the part's first position in the query's entry array
     // the query's sensor-frame points and the part's angle table go through LDS (they borrow the entry list's room, which nothing
     // writes before pass 1 is over): pass 1 reads point i of angle k for `per` consecutive pairs per thread
@@ -281,7 +256,7 @@ __global__ __launch_bounds__(YM_BINP_THREADS, MAXP <= 18 ? 4 : 2) void bin_kerne
     __syncthreads();
     {
         uint32_t *rb = a.rbox + (size_t)qs * a.rbox_stride;
-        for (int r = tid; r < nboxes; r += NT) rb[(size_t)r * a.lparts + part] = box[r][0] | box[r][1] << 8 | box[r][2] << 16 | box[r][3] << 24;
+        for (int r = tid; r < nboxes; r += NT) rb[(size_t)r * a.parts + part] = box[r][0] | box[r][1] << 8 | box[r][2] << 16 | box[r][3] << 24;
     }
     // exclusive scan of the padded bin sizes: thread t owns the bins [t * per, (t + 1) * per)
     const int per = (a.nbins + NT - 1) / NT;
@@ -522,7 +497,7 @@ __global__ __launch_bounds__(64 * NW, NW <= 8 ? (3 * NW + 3) / 4 : 1 /* three bl
     const int half_pitch = a.g.pitch / 2;
     const int plane_bytes = half_pitch * a.g.win_w;
     const uint8_t *__restrict__ planes = a.planes + (size_t)b * a.grid_stride;
-    // (the lists of this block's angles: list part p -- the host builds them with lnw = NW, lparts = parts)
+    // (the lists of this block's angles: list part p -- the host launches with nw = NW)
     const int32_t *__restrict__ starts = rg_part_starts(a, st.qslot, p);
     const uint16_t *__restrict__ entries = a.entries + (size_t)st.qslot * a.entries_stride;
     const uint32_t lds0 = (uint32_t)(size_t)region;
@@ -854,8 +829,5 @@ __global__ __launch_bounds__(64 * NW, NW <= 8 ? (3 * NW + 3) / 4 : 1 /* three bl
     prof_out();
 #endif
 }
-
-// (the forms that lost to correlate_region_kernel -- wave-specialised, one block per item, pooled, sixteen waves per block -- and the
-//  round-5 list builder they read live in scripts/exp/forms/: profiles/r04_region_study.md, r05_region_study.md; `make experimental`)
 
 } // namespace ym

@@ -26,9 +26,6 @@
 #include "ym_k_correlate.hpp"
 #include "ym_k_finish.hpp"
 #include "ym_k_region.hpp"
-#ifdef YM_EXPERIMENTAL // the correlate forms that lost (scripts/exp/forms; `make experimental` puts that directory on the include path)
-#include "ym_exp_forms.hpp"
-#endif
 #include "ym_k_gather.hpp"
 #include "ym_k_yagpy.hpp"
 #include "ym_k_yagmap.hpp"

@@ -20,22 +20,8 @@
 // two signed 16-bit halves.  A cell keeps x in the low half and y in the high half; a window coordinate lies within
 // roi_w + border of zero either way (the planner refuses a geometry beyond YM_CELL_COORD_LIMIT), so x = -32768 is never a
 // cell's and marks "no cell".  It is left of every tile's halo: a range test on the halves rejects it like any cell out of reach.
-// -DYM_WIDE_CELLS=1 builds the former int2 records instead (a second library for timing one format against the other, never a
-// run-time choice); everything that reads or writes either array goes through the helpers below.
-#ifndef YM_WIDE_CELLS
-#define YM_WIDE_CELLS 0
-#endif
+// Everything that reads or writes either array goes through the helpers below.
 #define YM_CELL_COORD_LIMIT 32768  // roi_w + border must stay below it
-#if YM_WIDE_CELLS
-typedef int2 YmCell;
-typedef int2 YmGov;
-__host__ __device__ __forceinline__ YmCell ym_cell_none() { return make_int2(YM_CELL_NONE, YM_CELL_NONE); }
-__host__ __device__ __forceinline__ YmCell ym_cell_pack(int x, int y) { return make_int2(x, y); }
-__host__ __device__ __forceinline__ int2 ym_cell_unpack(YmCell c) { return c; }  // (x, y), or (YM_CELL_NONE, YM_CELL_NONE)
-__host__ __device__ __forceinline__ int2 ym_cell_halves(YmCell c) { return c; }  // (x, y); "no cell" has an x left of every window
-__host__ __device__ __forceinline__ YmGov ym_gov_pack(int2 g) { return g; }
-__host__ __device__ __forceinline__ int2 ym_gov_unpack(YmGov g) { return g; }
-#else
 typedef uint32_t YmCell;
 typedef uint32_t YmGov;
 __host__ __device__ __forceinline__ YmCell ym_cell_none() { return 0x8000u; }
@@ -46,7 +32,6 @@ __host__ __device__ __forceinline__ int2 ym_cell_unpack(YmCell c) {
 }
 __host__ __device__ __forceinline__ YmGov ym_gov_pack(int2 g) { return ((uint32_t)g.x & 0xffffu) | (uint32_t)g.y << 16; }
 __host__ __device__ __forceinline__ int2 ym_gov_unpack(YmGov g) { return make_int2((int)(int16_t)(g & 0xffffu), (int)g >> 16); }
-#endif
 
 // Grid geometry of one matcher configuration + the device window chosen for one call.
 // Karto: ScanMatcher::Create / CorrelationGrid::CreateGrid.  The device never allocates Karto's

@@ -133,7 +133,7 @@ class ScanMatcher(object):
         self._m = self._lib.ym_create(C.byref(self._cfg), self.device)
         if not self._m:
             raise _capi.YmError(-1, _capi.last_error())
-        # development only, and only on request: YM_DEVELOPMENT=1 YM_DEBUG_OPTIONS="32=1,33=2" -> ym_debug_option on every
+        # development only, and only on request: YM_DEVELOPMENT=1 YM_DEBUG_OPTIONS="14=1,21=2" -> ym_debug_option on every
         # matcher of the process.  Without YM_DEVELOPMENT an inherited YM_DEBUG_OPTIONS changes nothing in a library user.
         if os.environ.get("YM_DEVELOPMENT") == "1":
             for kv in filter(None, (t.strip() for t in os.environ.get("YM_DEBUG_OPTIONS", "").split(","))):
