@@ -315,6 +315,47 @@ int ym_map_update_scans(ym_matcher *m, ym_map *map, const ym_scan *const *remove
                         int n_remove, const ym_scan *const *add, int n_add, ym_map_update_stats *stats /* or null */);
 int ym_map_counted(const ym_map *map);
 int ym_map_read_stamps(const ym_map *map, uint32_t *out, int64_t out_count);
+/* ---- maps whose window moves.  A map has a window in cells of an anchor lattice: an integer offset (x0, y0)
+ * and a size.  The maps of the creators above have offset (0, 0); the anchor (ax, ay) of a counted map is the origin it was created
+ * with and never changes.  On a counted map the cell of a reading is (rint((x - ax) / res) - x0, rint((y - ay) / res) - y0): the quotient
+ * and the rounding of ym_map_add_scans, the offset subtracted afterwards, exactly -- a reading keeps its lattice cell wherever the
+ * window lies.  The world origin of the window is ax + x0 * res, ay + y0 * res, computed as written from the anchor and the whole offset
+ * (the library is built with -ffp-contract=off), never step by step: ym_map_add_scans accepts exactly that value on a counted map.
+ *   ym_map_create_counted_window  ym_map_create_counted with a window offset: the yardstick of a reframe, and how a saved map is
+ *                        restored.  ym_map_create_counted is its (0, 0) case.
+ *   ym_map_window        the window of any map.
+ *   ym_map_reframe       makes new cell (i, j) the old cell (i + dx, j + dy) in a window of width x height cells.  Counted maps:
+ *                        held[i] at held_poses[i] are ALL the scans the map holds, at the poses they were added at (the convention of
+ *                        ym_map_update_scans' remove_poses).  Afterwards grid, bytes and counts are bit for bit those of a fresh
+ *                        ym_map_create_counted_window map with the same anchor, the new window and the same scans: a reading the
+ *                        old window dropped and the new one contains is stamped now, a reading that left the window takes its count
+ *                        with it, and a cell near a side that moved gains or loses the taps of stamped cells beyond that side.  The
+ *                        kept cells are copied, the held scans' readings outside the old window are stamped, and only the cells
+ *                        whose tap neighbourhood meets the two windows differently are recomputed from the counts.  Uncounted maps
+ *                        (n_held must be 0) keep no scans and no origin: the overlap keeps its values, every other cell is zero, the
+ *                        caller moves its origin, and what border cells would have received from readings dropped earlier is lost.
+ *                        Transactional: the new window is built in memory of its own and traded in when it is complete; a call
+ *                        that is refused or fails, allocation included, leaves the map as it was.  The check on the held list: the
+ *                        counts of the kept cells must sum to the held readings that fall there; if not, stats->mismatch is their
+ *                        difference, the call returns YM_ERR_INVALID and nothing is changed.  (The check counts; it does not compare
+ *                        cell by cell.)  The identity (dx = dy = 0, the same size) does nothing and reports kept = width * height.
+ *                        Runs on the matcher's stream, synchronous, never throws.  A ym_locator made before does not see it.
+ * YM_ERR_INVALID: a null argument, a negative n_held, a size <= 0 or above 10^9 cells, an accumulated offset beyond +-2^30, a held
+ * list on an uncounted map, a null scan, a scan or a map on another device, a mismatch.  YM_ERR_UNSUPPORTED: a matcher that is not
+ * YM_SEM_YAGPY, on a counted map taps too wide for the recompute's LDS tile (ym_map_update_scans' limit). */
+typedef struct ym_map_reframe_stats {
+    int64_t kept;        /* cells copied from the old window */
+    int64_t restamped;   /* readings of held scans the old window dropped and the new one holds */
+    int64_t dropped;     /* readings of held scans outside the new window */
+    int64_t recomputed;  /* cells recomputed from the counts */
+    int64_t mismatch;    /* |sum of kept counts - held readings inside the overlap|; non-zero: nothing was changed */
+    int32_t x0, y0, width, height; /* the window after the call */
+} ym_map_reframe_stats;
+int ym_map_reframe(ym_matcher *m, ym_map *map, int dx, int dy, int width, int height,
+                   const ym_scan *const *held, const double *held_poses /* [n_held][3], the poses they were added at */,
+                   int n_held, ym_map_reframe_stats *stats /* or null */);
+int ym_map_window(const ym_map *map, int *x0, int *y0, int *width, int *height);
+ym_map *ym_map_create_counted_window(ym_matcher *m, int width, int height, double ax, double ay, int x0, int y0);
 /* one find_best_pose_non_symmetric pass (/root/reference/yag_slam/helpers.py:434-573) */
 typedef struct ym_map_search {
     double xy_search, xy_step;       /* +- metres around the centre, lattice step */

@@ -102,12 +102,22 @@ ym_map *ym_map_create_empty(ym_matcher *m, int width, int height) {
     return mp;
 }
 
+static const int kMapMaxOffset = 1 << 30; // a window's offset in lattice cells: exact in fp64 and in the int32 of the kernels
+
 ym_map *ym_map_create_counted(ym_matcher *m, int width, int height, double ox, double oy) {
+    return ym_map_create_counted_window(m, width, height, ox, oy, 0, 0);
+}
+
+ym_map *ym_map_create_counted_window(ym_matcher *m, int width, int height, double ax, double ay, int x0, int y0) {
+    if (x0 < -kMapMaxOffset || x0 > kMapMaxOffset || y0 < -kMapMaxOffset || y0 > kMapMaxOffset) {
+        set_err(YM_ERR_INVALID, "window offset (%d, %d): at most 2^30 cells either way", x0, y0);
+        return nullptr;
+    }
     DevGuard guard(m ? m->device : 0);
     ym_map *mp = map_alloc(m, width, height);
     if (!mp) return nullptr;
     const size_t n = (size_t)width * height;
-    mp->counted = true; mp->ox = ox; mp->oy = oy;
+    mp->counted = true; mp->ox = ax; mp->oy = ay; mp->x0 = x0; mp->y0 = y0;
     if (mp->d_stamps.alloc(n) != YM_OK || mp->d_dirty.alloc(n) != YM_OK || map_clear(m, mp) != YM_OK) { // (the error text is set)
         delete mp;
         return nullptr;
@@ -185,7 +195,7 @@ static int map_update(ym_matcher *m, ym_map *mp, const ym_scan *const *remove, c
     ym::MapGrowArgs a;
     std::memset(&a, 0, sizeof a);
     a.scans = m->grow_scans.p; a.max_n = max_n; a.width = mp->width; a.height = mp->height;
-    a.ox = mp->ox; a.oy = mp->oy; a.res = m->cfg.resolution;
+    a.ox = mp->ox; a.oy = mp->oy; a.res = m->cfg.resolution; a.wx0 = mp->x0; a.wy0 = mp->y0;
     a.cells = m->grow_cells.p; a.kernel = m->kernel_f_dev.p; a.ksize = ks;
     a.cgrid = mp->d_cgrid.p; a.g8 = mp->d_g8.p;
     ym::MapForgetArgs f;
@@ -271,8 +281,10 @@ int ym_map_add_scans(ym_matcher *m, ym_map *mp, double ox, double oy, const ym_s
     if (n_scans < 0) return set_err(YM_ERR_INVALID, "n_scans must not be negative");
     if (mp->device != m->device) return set_err(YM_ERR_INVALID, "map lives on another device");
     if (mp->counted) { // the counts go up with the stamps
-        if (!(ox == mp->ox && oy == mp->oy))
-            return set_err(YM_ERR_INVALID, "a counted map keeps the origin it was created with (%.17g, %.17g)", mp->ox, mp->oy);
+        // the window's origin, from the anchor and the whole offset (never step by step: section 17); the anchor itself at offset 0
+        const double wox = mp->ox + mp->x0 * m->cfg.resolution, woy = mp->oy + mp->y0 * m->cfg.resolution;
+        if (!(ox == wox && oy == woy))
+            return set_err(YM_ERR_INVALID, "a counted map keeps its origin: that of its window is (%.17g, %.17g)", wox, woy);
         ym_map_update_stats u;
         int rc;
         if ((rc = map_update(m, mp, nullptr, nullptr, 0, scans, n_scans, &u))) return rc;
@@ -334,6 +346,172 @@ int ym_map_add_scans(ym_matcher *m, ym_map *mp, double ox, double oy, const ym_s
         s.x0 = std::max(0, (int)got[ym::kMgX0] - half); s.y0 = std::max(0, (int)got[ym::kMgY0] - half);
         s.x1 = std::min(mp->width, (int)got[ym::kMgX1] + half + 1); s.y1 = std::min(mp->height, (int)got[ym::kMgY1] + half + 1);
     }
+    if (stats) *stats = s;
+    return YM_OK;
+}
+
+// ---- maps whose window moves (ym_k_mapgrow.hpp)
+int ym_map_window(const ym_map *mp, int *x0, int *y0, int *width, int *height) {
+    if (!mp) return set_err(YM_ERR_INVALID, "null map");
+    if (x0) *x0 = mp->x0;
+    if (y0) *y0 = mp->y0;
+    if (width) *width = mp->width;
+    if (height) *height = mp->height;
+    return YM_OK;
+}
+
+int ym_map_reframe(ym_matcher *m, ym_map *mp, int dx, int dy, int width, int height, const ym_scan *const *held,
+                   const double *held_poses, int n_held, ym_map_reframe_stats *stats) {
+    if (!m || !mp || (n_held != 0 && (!held || !held_poses))) return set_err(YM_ERR_INVALID, "null argument");
+    if (n_held < 0) return set_err(YM_ERR_INVALID, "n_held must not be negative");
+    if (width <= 0 || height <= 0 || (double)width * height > 1.0e9) return set_err(YM_ERR_INVALID, "bad map size %d x %d", width, height);
+    if (m->cfg.semantics != YM_SEM_YAGPY) return set_err(YM_ERR_UNSUPPORTED, "ym_map_reframe needs a YM_SEM_YAGPY matcher");
+    if (mp->device != m->device) return set_err(YM_ERR_INVALID, "map lives on another device");
+    const int64_t nx0 = (int64_t)mp->x0 + dx, ny0 = (int64_t)mp->y0 + dy;
+    if (nx0 < -kMapMaxOffset || nx0 > kMapMaxOffset || ny0 < -kMapMaxOffset || ny0 > kMapMaxOffset)
+        return set_err(YM_ERR_INVALID, "window offset (%lld, %lld): at most 2^30 cells either way", (long long)nx0, (long long)ny0);
+    if (!mp->counted && n_held != 0) return set_err(YM_ERR_INVALID, "this map keeps no counts and holds no scans: n_held must be 0");
+    int max_n = 1;
+    for (int i = 0; i < n_held; i++) {
+        if (!held[i] || held[i]->device != m->device) return set_err(YM_ERR_INVALID, "held scan %d is null or lives on another device", i);
+        max_n = std::max(max_n, held[i]->n);
+    }
+    const int ks = 2 * m->geom.half_kernel + 1, half = m->geom.half_kernel;
+    const size_t halo_bytes = (size_t)(ym::kMfTileW + ks - 1) * (size_t)(ym::kMfTileH + ks - 1);
+    if (mp->counted) {
+        if ((double)max_n * ks * ks > 2.0e9) return set_err(YM_ERR_UNSUPPORTED, "%d beams x %d x %d taps: more than one launch holds", max_n, ks, ks);
+        if (halo_bytes > 65536)
+            return set_err(YM_ERR_UNSUPPORTED, "%d x %d taps: the recompute's tile and halo (%zu bytes) do not fit 64 KiB of LDS", ks, ks, halo_bytes);
+    }
+    ym_map_reframe_stats s;
+    std::memset(&s, 0, sizeof s);
+    s.x0 = mp->x0; s.y0 = mp->y0; s.width = mp->width; s.height = mp->height;
+    if (dx == 0 && dy == 0 && width == mp->width && height == mp->height) { // the identity: nothing to do
+        s.kept = (int64_t)width * height;
+        if (stats) *stats = s;
+        return YM_OK;
+    }
+    // the overlap of the two windows, in cells of the new one (int64: dx, dy are any int)
+    const int64_t o0x = std::max<int64_t>(0, -(int64_t)dx), o1x = std::min<int64_t>(width, (int64_t)mp->width - dx);
+    const int64_t o0y = std::max<int64_t>(0, -(int64_t)dy), o1y = std::min<int64_t>(height, (int64_t)mp->height - dy);
+    const bool overlap = o1x > o0x && o1y > o0y;
+    const int ex0 = overlap ? (int)o0x : 0, ex1 = overlap ? (int)o1x : 0, ey0 = overlap ? (int)o0y : 0, ey1 = overlap ? (int)o1y : 0;
+    // (without an overlap every source test of the copy must fail: a shift no window reaches, which cannot overflow the kernel's sums)
+    const int kdx = overlap ? dx : -kMapMaxOffset * 2 + 1, kdy = overlap ? dy : 0;
+    DEV_GUARD(m->device);
+    hipStream_t st = m->stream;
+    const size_t n = (size_t)width * height;
+    // everything is built in arrays of its own and traded in when all of it is complete: whatever fails, the map is as it was
+    DevBuf<double> n_cgrid;
+    DevBuf<uint8_t> n_g8, n_dirty;
+    DevBuf<uint32_t> n_stamps;
+    DevBuf<unsigned long long> d_stats;
+    int rc;
+    if ((rc = n_cgrid.alloc(n)) || (rc = n_g8.alloc(n + 64)) || (rc = d_stats.alloc(2))) return rc;
+    if (mp->counted && ((rc = n_stamps.alloc(n)) || (rc = n_dirty.alloc(n)))) return rc;
+    HIP_TRY(hipMemsetAsync(d_stats.p, 0, 2 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(n_g8.p + n, 0, 64, st));
+    ym::MapReframeArgs r;
+    std::memset(&r, 0, sizeof r);
+    r.src_cgrid = mp->d_cgrid.p; r.src_g8 = mp->d_g8.p; r.src_stamps = mp->d_stamps.p; r.src_w = mp->width; r.src_h = mp->height;
+    r.dx = kdx; r.dy = kdy; r.width = width; r.height = height;
+    r.cgrid = n_cgrid.p; r.g8 = n_g8.p; r.stamps = n_stamps.p; r.dirty = n_dirty.p; r.stats = d_stats.p; r.half = half;
+    const dim3 groups((unsigned)((n + 1023) / 1024));
+    if (mp->counted) hipLaunchKernelGGL(ym::map_reframe_copy_kernel<true>, groups, dim3(256), 0, st, r);
+    else hipLaunchKernelGGL(ym::map_reframe_copy_kernel<false>, groups, dim3(256), 0, st, r);
+    HIP_TRY(hipGetLastError());
+    if (overlap) s.kept = (int64_t)(ex1 - ex0) * (ey1 - ey0);
+    unsigned long long got_r[2] = {0, 0};
+    if (mp->counted) {
+        enum { kAdd = 0, kUpd = ym::kMgStatSlots, kSlots = ym::kMgStatSlots + ym::kMuStatSlots };
+        // (what the copies of this call read on the host -- `init`, `all` -- stays as it is until the wait below)
+        unsigned long long init[kSlots], got[kSlots];
+        std::vector<YmScanRef> all((size_t)n_held);
+        if ((rc = m->kernel_f_dev.ensure(m->kernel_f.size()))) return rc;
+        HIP_TRY(hipMemcpyAsync(m->kernel_f_dev.p, m->kernel_f.data(), m->kernel_f.size() * sizeof(double), hipMemcpyHostToDevice, st));
+        if (n_held > 0) { // the restamp: what the old window dropped and the new one holds
+            const int chunk = std::min(n_held, kMapGrowChunk);
+            if ((rc = m->grow_scans.ensure((size_t)chunk)) || (rc = m->grow_cells.ensure((size_t)chunk * max_n)) ||
+                (rc = m->grow_stats.ensure(kSlots)))
+                return rc;
+            for (int i = 0; i < kSlots; i++) init[i] = 0;
+            init[kAdd + ym::kMgX0] = init[kAdd + ym::kMgY0] = init[kUpd + ym::kMuX0] = init[kUpd + ym::kMuY0] = ~0ull;
+            HIP_TRY(hipMemcpyAsync(m->grow_stats.p, init, sizeof init, hipMemcpyHostToDevice, st));
+            ym::MapGrowArgs a;
+            std::memset(&a, 0, sizeof a);
+            a.scans = m->grow_scans.p; a.max_n = max_n; a.width = width; a.height = height;
+            a.ox = mp->ox; a.oy = mp->oy; a.res = m->cfg.resolution; a.wx0 = (int)nx0; a.wy0 = (int)ny0;
+            a.ex0 = ex0; a.ey0 = ey0; a.ex1 = ex1; a.ey1 = ey1;
+            a.cells = m->grow_cells.p; a.stats = m->grow_stats.p + kAdd; a.kernel = m->kernel_f_dev.p; a.ksize = ks;
+            a.cgrid = n_cgrid.p; a.g8 = n_g8.p;
+            ym::MapForgetArgs f;
+            std::memset(&f, 0, sizeof f);
+            f.cells = m->grow_cells.p; f.max_n = max_n; f.width = width; f.height = height;
+            f.stamps = n_stamps.p; f.stats = m->grow_stats.p + kUpd; f.dirty = n_dirty.p;
+            f.kernel = m->kernel_f_dev.p; f.ksize = ks; f.cgrid = n_cgrid.p; f.g8 = n_g8.p;
+            const dim3 beams((unsigned)((max_n + 255) / 256)), taps((unsigned)(((size_t)max_n * ks * ks + 255) / 256));
+            for (int c0 = 0; c0 < n_held; c0 += chunk) {
+                const int B = std::min(chunk, n_held - c0);
+                YmScanRef *hs = all.data() + c0;
+                for (int i = 0; i < B; i++) hs[i] = scan_ref(held[c0 + i], held_poses + 3 * (size_t)(c0 + i));
+                HIP_TRY(hipMemcpyAsync(m->grow_scans.p, hs, sizeof(YmScanRef) * (size_t)B, hipMemcpyHostToDevice, st));
+                a.n_scans = B;
+                hipLaunchKernelGGL(ym::map_grow_cells_kernel, dim3(B), dim3(1024), 0, st, a);
+                hipLaunchKernelGGL(ym::map_count_kernel<false>, dim3(beams.x, B), dim3(256), 0, st, f);
+                hipLaunchKernelGGL(ym::map_grow_smear_kernel<false>, dim3(taps.x, B), dim3(256), 0, st, a);
+                hipLaunchKernelGGL(ym::map_grow_smear_kernel<true>, dim3(taps.x, B), dim3(256), 0, st, a);
+                HIP_TRY(hipGetLastError());
+            }
+            HIP_TRY(hipMemcpyAsync(got, m->grow_stats.p, sizeof got, hipMemcpyDeviceToHost, st));
+        }
+        if (overlap) {
+            // the recompute, after the restamp's atomics: the cells within the taps' reach of the overlap whose neighbourhood meets
+            // the two windows differently are flagged and take their value from the new window's counts
+            r.mx0 = std::max(0, ex0 - half); r.mx1 = std::min(width, ex1 + half);
+            const int my0 = std::max(0, ey0 - half), my1 = std::min(height, ey1 + half);
+            r.my1 = my1;
+            for (int y = my0; y < my1; y += 65535) { // (a launch has at most 65535 rows of blocks)
+                r.my0 = y;
+                hipLaunchKernelGGL(ym::map_reframe_mark_kernel, dim3((unsigned)((r.mx1 - r.mx0 + 255) / 256), (unsigned)std::min(65535, my1 - y)),
+                                   dim3(256), 0, st, r);
+            }
+            ym::MapForgetArgs g;
+            std::memset(&g, 0, sizeof g);
+            g.width = width; g.height = height; g.stamps = n_stamps.p; g.dirty = n_dirty.p;
+            g.kernel = m->kernel_f_dev.p; g.ksize = ks; g.cgrid = n_cgrid.p; g.g8 = n_g8.p;
+            g.bx0 = r.mx0 / ym::kMfTileW * ym::kMfTileW; g.by0 = my0 / ym::kMfTileH * ym::kMfTileH; g.bx1 = r.mx1; g.by1 = my1;
+            const dim3 tiles((unsigned)((g.bx1 - g.bx0 + ym::kMfTileW - 1) / ym::kMfTileW), (unsigned)((g.by1 - g.by0 + ym::kMfTileH - 1) / ym::kMfTileH));
+            for (unsigned ty = 0; ty < tiles.y; ty += 65535u) {
+                ym::MapForgetArgs p = g;
+                p.by0 = g.by0 + (int)ty * ym::kMfTileH;
+                hipLaunchKernelGGL(ym::map_forget_gather_kernel, dim3(tiles.x, std::min(65535u, tiles.y - ty)), dim3(256), halo_bytes, st, p);
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(got_r, d_stats.p, sizeof got_r, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        int64_t in_overlap = 0;
+        if (n_held > 0) {
+            s.restamped = (int64_t)got[ym::kMgStamped]; s.dropped = (int64_t)got[ym::kMgDropped];
+            in_overlap = (int64_t)got[ym::kMgOverlap];
+        }
+        s.recomputed = (int64_t)got_r[1];
+        const int64_t copied = (int64_t)got_r[0];
+        s.mismatch = copied > in_overlap ? copied - in_overlap : in_overlap - copied;
+        if (s.mismatch != 0) { // the counts and the scans said to be held disagree: the new arrays go, the map stays
+            s.kept = s.restamped = s.dropped = s.recomputed = 0;
+            if (stats) *stats = s;
+            return set_err(YM_ERR_INVALID, "the kept cells count %lld readings and the held scans put %lld there: nothing was changed",
+                           (long long)copied, (long long)in_overlap);
+        }
+    } else {
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    // the stream is idle: trade the arrays in (the old ones are freed with the locals)
+    mp->d_cgrid.swap(n_cgrid); mp->d_g8.swap(n_g8);
+    if (mp->counted) { mp->d_stamps.swap(n_stamps); mp->d_dirty.swap(n_dirty); }
+    mp->width = width; mp->height = height; mp->x0 = (int)nx0; mp->y0 = (int)ny0;
+    s.x0 = mp->x0; s.y0 = mp->y0; s.width = width; s.height = height;
     if (stats) *stats = s;
     return YM_OK;
 }

@@ -5,7 +5,10 @@ struct ym_map {
     int width, height;
     DevBuf<double> d_cgrid;  // the float correlation grid as the reference holds it
     DevBuf<uint8_t> d_g8;    // int(100 * cell): what scoring reads (+ 64 bytes)
-    // ym_map_create_counted only: the origin is fixed, and both forms above are a function of stamps > 0
+    // the window: cell (0, 0) is cell (x0, y0) of the lattice the map started in; ym_map_reframe moves it
+    int x0 = 0, y0 = 0;
+    // counted maps only: the anchor -- the world position of lattice cell (0, 0) -- is fixed, and both forms
+    // above are a function of stamps > 0
     bool counted = false;
     double ox = 0, oy = 0;
     DevBuf<uint32_t> d_stamps; // readings stamped per cell

@@ -94,6 +94,11 @@ struct DevBuf {
         p = nullptr;
         cap = 0;
     }
+    // trade memory with another buffer (ym_map_reframe: the arrays of the new window come in when all of them are complete)
+    void swap(DevBuf &o) {
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+    }
 };
 
 struct PinnedBuf {

@@ -1,6 +1,7 @@
 // ym_k_mapgrow.hpp -- a resident correlation map that takes scans: map_grow_cells_kernel, map_grow_smear_kernel, map_clear_kernel;
-// and one that lets them go again: map_count_kernel, map_forget_mark_kernel, map_forget_gather_kernel.
-// Part of ym_kernels.hpp (include that, not this file).  DESIGN.md sections 15 and 16.
+// one that lets them go again: map_count_kernel, map_forget_mark_kernel, map_forget_gather_kernel;
+// and one whose window moves: map_reframe_copy_kernel, map_reframe_mark_kernel.
+// Part of ym_kernels.hpp (include that, not this file).  DESIGN.md sections 15, 16 and 17.
 #pragma once
 
 namespace ym {
@@ -20,13 +21,16 @@ namespace ym {
 //           issued where it was not needed.
 //   bytes   the same lanes again, in a launch of its own (the maxima are complete): g8 = (uint8_t)(int)(100 * cell), the form the
 //           scoring kernels read.  Lanes that share a cell write the same byte.  Only touched cells are rewritten.
-enum { kMgPoints = 0, kMgStamped, kMgDropped, kMgX0, kMgY0, kMgX1, kMgY1, kMgStatSlots };
+enum { kMgPoints = 0, kMgStamped, kMgDropped, kMgX0, kMgY0, kMgX1, kMgY1, kMgOverlap, kMgStatSlots };
 
 struct MapGrowArgs {
     const YmScanRef *scans;     // the scans of this launch
     int32_t n_scans, max_n;     // max_n: the longest scan, the stride of `cells`
     int32_t width, height;
-    double ox, oy, res;         // world position of cell (0, 0), cell size
+    double ox, oy, res;         // world position of lattice cell (0, 0) -- the map's anchor --, cell size
+    int32_t wx0, wy0;           // the map's cell (0, 0) is lattice cell (wx0, wy0): 0, 0 unless the map was reframed (section 17)
+    int32_t ex0, ey0, ex1, ey1; // ym_map_reframe: readings in the cells [ex0, ex1) x [ey0, ey1) are counted in kMgOverlap and yield -1
+                                // (their counts were copied); empty -- ex1 <= ex0 -- for every other caller
     int32_t *cells;             // [n_scans][max_n] gy * width + gx of a stamped reading, -1: no reading or outside the map
     unsigned long long *stats;  // [kMgStatSlots]; X0, Y0 start at the largest value, X1, Y1 (inclusive) and the counts at 0
     const double *kernel;       // [ksize][ksize] the float taps (helpers.py:86-97)
@@ -44,7 +48,7 @@ __global__ __launch_bounds__(1024) void map_grow_cells_kernel(MapGrowArgs a) {
     if (tid < kMgStatSlots) s_stat[tid] = (tid == kMgX0 || tid == kMgY0) ? ~0ull : 0ull;
     __syncthreads();
     const double px = sr.pose[0], py = sr.pose[1], pt = sr.pose[2];
-    unsigned points = 0, stamped = 0;
+    unsigned points = 0, stamped = 0, overlap = 0;
     int x0 = INT32_MAX, y0 = INT32_MAX, x1 = -1, y1 = -1;
     for (int i = tid; i < a.max_n; i += 1024) {
         int cell = -1;
@@ -54,13 +58,19 @@ __global__ __launch_bounds__(1024) void map_grow_cells_kernel(MapGrowArgs a) {
                 const double angle = pt + sr.min_angle + i * sr.angle_inc;
                 const double x = px + r * cos(angle), y = py + r * sin(angle);
                 // a NaN or an infinity fails the comparisons; so does what does not fit an int32 (the map has fewer cells per side)
-                const double gx = rint((x - a.ox) / a.res), gy = rint((y - a.oy) / a.res);
+                // the cell in the anchor's lattice, then the window's integer offset: exact in fp64 (|offset| <= 2^30), so a reading
+                // has the same lattice cell wherever the window lies
+                const double gx = rint((x - a.ox) / a.res) - (double)a.wx0, gy = rint((y - a.oy) / a.res) - (double)a.wy0;
                 points++;
                 if (gx >= 0.0 && gx < (double)a.width && gy >= 0.0 && gy < (double)a.height) {
                     const int cx = (int)gx, cy = (int)gy;
-                    cell = cy * a.width + cx; // (below 2^31: a map holds at most 10^9 cells)
-                    stamped++;
-                    x0 = min(x0, cx); y0 = min(y0, cy); x1 = max(x1, cx); y1 = max(y1, cy);
+                    if (cx >= a.ex0 && cx < a.ex1 && cy >= a.ey0 && cy < a.ey1) {
+                        overlap++;
+                    } else {
+                        cell = cy * a.width + cx; // (below 2^31: a map holds at most 10^9 cells)
+                        stamped++;
+                        x0 = min(x0, cx); y0 = min(y0, cy); x1 = max(x1, cx); y1 = max(y1, cy);
+                    }
                 }
             }
         }
@@ -68,12 +78,13 @@ __global__ __launch_bounds__(1024) void map_grow_cells_kernel(MapGrowArgs a) {
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
-        points += __shfl_xor(points, d); stamped += __shfl_xor(stamped, d);
+        points += __shfl_xor(points, d); stamped += __shfl_xor(stamped, d); overlap += __shfl_xor(overlap, d);
         x0 = min(x0, __shfl_xor(x0, d)); y0 = min(y0, __shfl_xor(y0, d));
         x1 = max(x1, __shfl_xor(x1, d)); y1 = max(y1, __shfl_xor(y1, d));
     }
     if ((tid & 63) == 0 && points) {
         atomicAdd(&s_stat[kMgPoints], (unsigned long long)points);
+        if (overlap) atomicAdd(&s_stat[kMgOverlap], (unsigned long long)overlap);
         if (stamped) {
             atomicAdd(&s_stat[kMgStamped], (unsigned long long)stamped);
             atomicMin(&s_stat[kMgX0], (unsigned long long)x0); atomicMin(&s_stat[kMgY0], (unsigned long long)y0);
@@ -83,7 +94,8 @@ __global__ __launch_bounds__(1024) void map_grow_cells_kernel(MapGrowArgs a) {
     __syncthreads();
     if (tid == 0 && s_stat[kMgPoints]) {
         atomicAdd(&a.stats[kMgPoints], s_stat[kMgPoints]);
-        atomicAdd(&a.stats[kMgDropped], s_stat[kMgPoints] - s_stat[kMgStamped]);
+        atomicAdd(&a.stats[kMgDropped], s_stat[kMgPoints] - s_stat[kMgStamped] - s_stat[kMgOverlap]);
+        if (s_stat[kMgOverlap]) atomicAdd(&a.stats[kMgOverlap], s_stat[kMgOverlap]);
         if (s_stat[kMgStamped]) {
             atomicAdd(&a.stats[kMgStamped], s_stat[kMgStamped]);
             atomicMin(&a.stats[kMgX0], s_stat[kMgX0]); atomicMin(&a.stats[kMgY0], s_stat[kMgY0]);
@@ -259,6 +271,101 @@ __global__ __launch_bounds__(256) void map_forget_gather_kernel(MapForgetArgs a)
     a.cgrid[c] = v;
     a.g8[c] = (uint8_t)(int)(100 * v);
     a.dirty[c] = 0;
+}
+
+// ---- maps whose window moves
+// ym_map_reframe builds the map of a new window in new arrays: new cell (i, j) is old cell (i + dx, j + dy).
+//   copy    one pass over the new window, four consecutive cells per thread: grid, bytes and counts come from the old arrays inside
+//           the overlap and are zero elsewhere, the dirty flags are zero.  The destination is written in aligned pieces (two double2,
+//           one uint4, two 32-bit words: the group starts at a multiple of four cells); the source row is shifted by dx and is read cell
+//           by cell -- consecutive lanes read consecutive groups, so a wave still reads contiguous memory.  The copied counts are
+//           summed: per wave by shuffles, per block in LDS, one 64-bit atomic per block.
+//   restamp map_grow_cells_kernel with the old window as its exclusion rectangle, map_count_kernel<false> and the two smear launches
+//           on the held scans: what the old window dropped and the new one holds is stamped now.
+//   mark    a cell's copied value stands only if its tap neighbourhood meets both windows in the same cells.  Of the others, a new
+//           cell out of reach of the overlap is completed by the restamp's scatter (every stamped cell that reaches it is new); the
+//           rest -- all of them within the taps' reach of the overlap -- are flagged here and recomputed by map_forget_gather_kernel
+//           from the new window's counts.
+struct MapReframeArgs {
+    const double *src_cgrid; const uint8_t *src_g8; const uint32_t *src_stamps; // the old window (src_stamps: counted maps)
+    int32_t src_w, src_h;
+    int32_t dx, dy;             // new cell (i, j) = old cell (i + dx, j + dy)
+    int32_t width, height;      // the new window
+    double *cgrid; uint8_t *g8; uint32_t *stamps; uint8_t *dirty; // the new arrays (stamps, dirty: counted maps)
+    unsigned long long *stats;  // [0] the sum of the copied counts, [1] the cells marked dirty
+    int32_t mx0, my0, mx1, my1; // mark: the cells [mx0, mx1) x [my0, my1) of the new window, the overlap widened by the taps' reach
+    int32_t half;
+};
+
+// grid (ceil(width * height / 1024)), 256 threads
+template <bool COUNTED>
+__global__ __launch_bounds__(256) void map_reframe_copy_kernel(MapReframeArgs a) {
+    __shared__ unsigned long long s_sum;
+    if (threadIdx.x == 0) s_sum = 0ull;
+    __syncthreads();
+    const size_t n = (size_t)a.width * a.height;
+    const size_t i0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    unsigned long long sum = 0ull;
+    if (i0 < n) {
+        int y = (int)(i0 / (size_t)a.width), x = (int)(i0 - (size_t)y * a.width);
+        double v[4];
+        uint32_t b[4], s[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int sx = x + a.dx, sy = y + a.dy;
+            v[k] = 0.0; b[k] = 0u; s[k] = 0u;
+            // (y may pass the last row in the last group: those entries are not stored)
+            if (sx >= 0 && sx < a.src_w && sy >= 0 && sy < a.src_h && y < a.height) {
+                const size_t c = (size_t)sy * a.src_w + sx;
+                v[k] = a.src_cgrid[c]; b[k] = a.src_g8[c];
+                if (COUNTED) { s[k] = a.src_stamps[c]; sum += s[k]; }
+            }
+            if (++x == a.width) { x = 0; y++; }
+        }
+        if (i0 + 4 <= n) { // (cgrid + i0: 32-byte aligned, stamps + i0: 16, g8 + i0 and dirty + i0: 4)
+            double2 *d = reinterpret_cast<double2 *>(a.cgrid + i0);
+            d[0] = make_double2(v[0], v[1]); d[1] = make_double2(v[2], v[3]);
+            *reinterpret_cast<uint32_t *>(a.g8 + i0) = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+            if (COUNTED) {
+                *reinterpret_cast<uint4 *>(a.stamps + i0) = make_uint4(s[0], s[1], s[2], s[3]);
+                *reinterpret_cast<uint32_t *>(a.dirty + i0) = 0u;
+            }
+        } else {
+            for (int k = 0; i0 + k < n; k++) {
+                a.cgrid[i0 + k] = v[k]; a.g8[i0 + k] = (uint8_t)b[k];
+                if (COUNTED) { a.stamps[i0 + k] = s[k]; a.dirty[i0 + k] = 0; }
+            }
+        }
+    }
+    if (COUNTED) {
+        unsigned lo = (unsigned)sum, hi = (unsigned)(sum >> 32);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { // (the 64-bit sum travels as its two halves)
+            const unsigned long long o = ((unsigned long long)__shfl_xor(hi, d) << 32) | __shfl_xor(lo, d);
+            sum += o;
+            lo = (unsigned)sum; hi = (unsigned)(sum >> 32);
+        }
+        if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&s_sum, sum);
+        __syncthreads();
+        if (threadIdx.x == 0 && s_sum) atomicAdd(&a.stats[0], s_sum);
+    }
+}
+
+// grid (ceil((mx1 - mx0) / 256), my1 - my0 in pieces of 65535), 256 threads; a.my0 is the first row of the piece
+__global__ __launch_bounds__(256) void map_reframe_mark_kernel(MapReframeArgs a) {
+    const int x = a.mx0 + blockIdx.x * 256 + threadIdx.x, y = a.my0 + blockIdx.y;
+    bool mark = false;
+    if (x < a.mx1 && y < a.my1) {
+        // the neighbourhood [x - half, x + half] x [y - half, y + half] cut to the new window and to the old one (in new cells)
+        const int nx0 = x - a.half, nx1 = x + a.half + 1, ny0 = y - a.half, ny1 = y + a.half + 1;
+        const int ax0 = max(nx0, 0), ax1 = min(nx1, a.width), ay0 = max(ny0, 0), ay1 = min(ny1, a.height);
+        const int bx0 = max(nx0, -a.dx), bx1 = min(nx1, a.src_w - a.dx), by0 = max(ny0, -a.dy), by1 = min(ny1, a.src_h - a.dy);
+        const bool old_empty = bx1 <= bx0 || by1 <= by0; // (the new cut holds (x, y) itself)
+        mark = old_empty || ax0 != bx0 || ax1 != bx1 || ay0 != by0 || ay1 != by1;
+        if (mark) a.dirty[(size_t)y * a.width + x] = 1;
+    }
+    const int cnt = __syncthreads_count(mark);
+    if (threadIdx.x == 0 && cnt) atomicAdd(&a.stats[1], (unsigned long long)cnt);
 }
 
 }  // namespace ym

@@ -7,6 +7,8 @@ chain of the last `scan_buffer_len` scans (default 10, graph_slam.py:47,336-337)
 optimiser, no loop closure here -- this only drives the matcher the way yag-slam does, with every
 scan resident on the device (one upload per new scan, poses written through).
 """
+import math
+
 from .models import LocalizedRangeScan, set_corrected_poses
 from .transform import Transform
 
@@ -429,16 +431,34 @@ class MapBuilder(object):
     (`matcher.empty_correlation_map(w, h, counted=True, ox=ox, oy=oy)`), which the builder then owns: it
     holds the builder's keyframes and nothing else.
 
+    extent="fixed" (the default) leaves the map's extent as the caller sized it.  "scroll" and "grow" let the map follow the robot
+    (`CorrelationMap.reframe`): after a step's pose is known and before the scan is added, a pose nearer
+    than `margin` metres to a side of the map moves the window -- "scroll" keeps the size and recentres it on the robot, "grow"
+    enlarges it to the union of the old extent and the robot's pose +- margin -- by a whole number of `step` cells.  margin=None:
+    the matcher's range threshold plus the coarse search's half-width plus the taps' reach, what a step reads or stamps around
+    the pose.  With a window and "scroll" the map need only be twice that across, not as large as the site.  The builder's `ox`,
+    `oy` follow the window: the first origin plus the whole offset times the resolution, never step by step (on a counted map
+    that is the map's own `origin`).  On a map that keeps no counts a reframe keeps the overlap and nothing else: readings that
+    were dropped beyond a side do not come back when the window moves over them.
+
     `last` is the last scan processed, `last_added` the last one added, `added` every scan in the map (in order), `dropped`
     the scans the window has taken out again (in order), `lost` the number of consecutive steps whose correction was not
-    applied, `results` every step's result."""
+    applied, `results` every step's result, `reframes` the MapReframeStats of every move of the window."""
 
     # rebuild() on a counted map: above this share of moved keyframes the map is cleared and filled again.  Measured with 2000
     # scans of 1081 beams (DESIGN.md section 16, profiles/map_forget_time.json): with 5 x 5 taps moving costs as much as clearing
     # and adding all at a share of 0.2, with 29 x 29 taps only at 1.0 (there a builder may set its REBUILD_SHARE to 1.0).
     REBUILD_SHARE = 0.2
 
-    def __init__(self, matcher, cmap, ox, oy, coarse=None, min_response=0.0, min_distance=0.0, min_rotation=0.0, window=None):
+    def __init__(self, matcher, cmap, ox, oy, coarse=None, min_response=0.0, min_distance=0.0, min_rotation=0.0, window=None,
+                 extent="fixed", margin=None, step=32):
+        if extent not in ("fixed", "scroll", "grow"):
+            raise ValueError("MapBuilder: extent %r: \"fixed\", \"scroll\" or \"grow\"" % (extent,))
+        if extent != "fixed":
+            if isinstance(step, bool) or not isinstance(step, int) or step < 1:
+                raise ValueError("MapBuilder: step %r: an integer of at least 1 (cells)" % (step,))
+            if margin is not None and not margin > 0:
+                raise ValueError("MapBuilder: margin %r: None or metres above 0" % (margin,))
         if window is not None:
             if isinstance(window, bool) or not isinstance(window, int) or window < 1:
                 raise ValueError("MapBuilder: window %r: None or an integer of at least 1" % (window,))
@@ -449,6 +469,18 @@ class MapBuilder(object):
         self.coarse, self.min_response = coarse, min_response
         self.min_distance, self.min_rotation = min_distance, min_rotation
         self.window = window
+        self.extent, self.margin, self.step = extent, margin, step
+        self.reframes = []
+        if extent != "fixed":
+            cfg = matcher.config
+            self._res = float(cfg.resolution)
+            if margin is None:
+                reach = 2 * int(round(float(cfg.smear_deviation) / self._res)) * self._res  # half the taps' width, in metres
+                self.margin = float(cfg.range_threshold) + float((coarse or {}).get("xy_search", 0.25)) + reach
+            # the lattice the window moves in: a counted map's own anchor and offset, else the origin the caller gave
+            anchor = getattr(cmap, "anchor", None) if getattr(cmap, "counted", False) else None
+            self._base = (ox, oy) if anchor is None else anchor
+            self._offset = (0, 0) if anchor is None else tuple(cmap.window[:2])
         self.last = None
         self.last_added = None
         self.added = []
@@ -467,9 +499,35 @@ class MapBuilder(object):
         self.last_added = scan
         return stats
 
+    def _follow(self, scan):
+        """extent "scroll" / "grow": move the window if the scan's pose is nearer than `margin` to a side; the reframe's stats or None"""
+        if self.extent == "fixed":
+            return None
+        res, (h, w) = self._res, self.cmap.shape
+        p = scan.corrected_pose
+        px, py, m = (p.x - self.ox) / res, (p.y - self.oy) / res, self.margin / res  # in cells of the window
+        if px - m >= 0 and px + m <= w and py - m >= 0 and py + m <= h:
+            return None
+        k = self.step
+        if self.extent == "scroll":
+            dx, dy, nw, nh = k * int(round((px - 0.5 * w) / k)), k * int(round((py - 0.5 * h) / k)), w, h
+        else:
+            x0, y0 = min(0, k * int(math.floor((px - m) / k))), min(0, k * int(math.floor((py - m) / k)))
+            x1, y1 = max(w, k * int(math.ceil((px + m) / k))), max(h, k * int(math.ceil((py + m) / k)))
+            dx, dy, nw, nh = x0, y0, x1 - x0, y1 - y0
+        if (dx, dy, nw, nh) == (0, 0, w, h):
+            return None  # (a window narrower than two margins: recentred as well as the step allows)
+        stats = self.cmap.reframe(dx, dy, nw, nh)
+        self._offset = (self._offset[0] + dx, self._offset[1] + dy)
+        # from the first origin and the whole offset, as the library computes a counted map's origin: repeated moves do not drift
+        self.ox, self.oy = self._base[0] + self._offset[0] * res, self._base[1] + self._offset[1] * res
+        self.reframes.append(stats)
+        return stats
+
     def start(self, scan):
         """The first scan: its pose is known (`corrected_pose` and `odom_pose` set by the caller).  It is added to the map and
         becomes `last` and `last_added`.  Returns the add's MapAddStats."""
+        self._follow(scan)
         stats = self._add(scan)
         self.last, self.lost = scan, 0
         return stats
@@ -498,6 +556,7 @@ class MapBuilder(object):
         r = res[1]
         self.lost = 0 if r.meta["accepted"] else self.lost + 1
         r.meta["added"] = bool(r.meta["accepted"] and self._is_keyframe(scan))
+        self._follow(scan)
         if r.meta["added"]:
             self._add(scan)
         self.results.append(r)

@@ -371,21 +371,28 @@ class ScanMatcher(object):
             raise _capi.YmError(-1, _capi.last_error())
         return CorrelationMap(self, h)
 
-    def empty_correlation_map(self, width, height, counted=False, ox=None, oy=None):
+    def empty_correlation_map(self, width, height, counted=False, ox=None, oy=None, window=None):
         """A resident CorrelationMap of `height` x `width` zeros, to be filled with `CorrelationMap.add_scans`.
         counted=True (`ym_map_create_counted`): the map also counts the readings stamped in each cell, so that scans can be
-        taken out again (`remove_scans`, `sync`); its cell (0, 0) lies at world (ox, oy) for good."""
+        taken out again (`remove_scans`, `sync`); (ox, oy) is its anchor, the world position of cell (0, 0) of the lattice its
+        window lies in, for good.  window=(x0, y0) (`ym_map_create_counted_window`): the map's cell (0, 0)
+        is cell (x0, y0) of that lattice and its `origin` is anchor + offset * resolution; without it the window starts at the
+        anchor.  `CorrelationMap.reframe` moves the window of either kind of map."""
         if not counted:
-            if ox is not None or oy is not None:
-                raise ValueError("empty_correlation_map: only a counted map has an origin of its own")
+            if ox is not None or oy is not None or window is not None:
+                raise ValueError("empty_correlation_map: only a counted map has an origin and a window offset of its own")
             h = self._lib.ym_map_create_empty(self._m, int(width), int(height))
         else:
             if ox is None or oy is None:
                 raise ValueError("empty_correlation_map: a counted map needs its origin (ox, oy)")
-            h = self._lib.ym_map_create_counted(self._m, int(width), int(height), float(ox), float(oy))
+            if window is None:
+                h = self._lib.ym_map_create_counted(self._m, int(width), int(height), float(ox), float(oy))
+            else:
+                x0, y0 = (int(v) for v in window)
+                h = self._lib.ym_map_create_counted_window(self._m, int(width), int(height), float(ox), float(oy), x0, y0)
         if not h:
             raise _capi.YmError(-1, _capi.last_error())
-        return CorrelationMap(self, h, origin=(float(ox), float(oy)) if counted else None)
+        return CorrelationMap(self, h, origin=(float(ox), float(oy)) if counted else None, offset=window or (0, 0))
 
     def match_scan_sets_with_map(self, cgrid, ox, oy, query_scans, penalty=True, do_fine=True, coarse=None):
         """The reference's signature (scan_matching.py:124): the point readings of all `query_scans` are matched as one
@@ -690,6 +697,7 @@ class ScanMatcher(object):
 
 MapAddStats = namedtuple("MapAddStats", ["points", "stamped", "dropped", "x0", "y0", "x1", "y1"])
 MapUpdateStats = namedtuple("MapUpdateStats", ["removed", "added", "dropped", "unmatched", "released", "gained", "x0", "y0", "x1", "y1"])
+MapReframeStats = namedtuple("MapReframeStats", ["kept", "restamped", "dropped", "recomputed", "mismatch", "x0", "y0", "width", "height"])
 
 
 class CorrelationMap(object):
@@ -702,15 +710,23 @@ class CorrelationMap(object):
     forget: `counted` is True, `origin` its fixed (ox, oy), and it keeps every scan it holds with the pose it was added at, as
     LiveOccupancyGrid does, so `remove_scans` and `sync` take out exactly what went in whatever happened to the scan's pose
     since.  `scan in cmap` and `len(cmap)` speak of the held scans.  On any other map `counted` is False, `origin` None, and
-    the methods that forget raise ValueError."""
+    the methods that forget raise ValueError.
 
-    def __init__(self, matcher, handle, origin=None):
+    Every map has a `window` (x0, y0, width, height) in cells of the lattice it started in, which `reframe` moves or resizes
+    (DESIGN.md section 17); a counted map's `anchor` is its first origin and stays, its `origin` follows the window."""
+
+    def __init__(self, matcher, handle, origin=None, offset=(0, 0)):
         self.m, self._h = matcher, handle
         w, h = C.c_int32(), C.c_int32()
         _capi.check(matcher._lib.ym_map_size(handle, C.byref(w), C.byref(h)))
         self.shape = (h.value, w.value)
         self.revision = 0
-        self.counted, self.origin = origin is not None, origin
+        # `origin` is the anchor; a window that does not start at the anchor's cell (0, 0) has its own origin (section 17)
+        self.counted, self._anchor, self._offset = origin is not None, origin, (int(offset[0]), int(offset[1]))
+        self.origin = origin
+        if origin is not None and self._offset != (0, 0):
+            res = float(matcher._cfg.resolution)
+            self.origin = (origin[0] + self._offset[0] * res, origin[1] + self._offset[1] * res)
         self._held = {}  # counted maps: id(scan) -> (the scan, the pose it was added at); insertion-ordered
 
     def add_scans(self, ox, oy, scans):
@@ -834,6 +850,56 @@ class CorrelationMap(object):
         if len({id(q) for q in add}) != len(add):
             raise ValueError("update_scans (add): a scan is in the list twice")
         return self._update(remove, add)
+
+    # ---- the window (ym_map_reframe)
+    @property
+    def anchor(self):
+        """a counted map's first origin: world position of cell (0, 0) of the lattice its window moves in (None on other maps)"""
+        a = getattr(self, "_anchor", None)
+        return a if a is not None else getattr(self, "origin", None)
+
+    @property
+    def window(self):
+        """(x0, y0, width, height): the map's cell (0, 0) is cell (x0, y0) of the anchor's lattice"""
+        x0, y0 = getattr(self, "_offset", (0, 0))
+        return (x0, y0, self.shape[1], self.shape[0])
+
+    def reframe(self, dx, dy, width=None, height=None):
+        """Move or resize the window (`ym_map_reframe`): new cell (i, j) is the old cell (i + dx, j + dy), in a window of `width` x
+        `height` cells (None: as now).  A counted map is afterwards, bit for bit, the map a fresh counted map with the same
+        anchor, the new window and the same held scans would be -- readings the old window dropped are stamped, readings that
+        left it take their counts along, cells near a side that moved are recomputed -- and `origin` becomes
+        anchor + offset * resolution, computed from the first origin, never step by step; the scans stay held.  Any other map
+        keeps no scans and no origin: the overlap keeps its values, every other cell is zero, the caller moves its own origin by
+        (dx, dy) cells, and what the border cells would have received from readings dropped earlier is lost.
+        `revision` goes up unless the call was the identity.  Returns MapReframeStats(kept, restamped, dropped, recomputed,
+        mismatch, x0, y0, width, height); RuntimeError if the counts and the held scans disagree (nothing was changed)."""
+        old = self.window
+        width = old[2] if width is None else int(width)
+        height = old[3] if height is None else int(height)
+        dx, dy = int(dx), int(dy)
+        counted = getattr(self, "counted", False)
+        held = [e for e in self._held.values()] if counted else []
+        hs = (C.c_void_p * max(1, len(held)))(*[self.m._require_native(q) for q, _ in held])
+        poses = np.array([pose for _, pose in held], dtype=np.float64).reshape(len(held), 3)
+        st = _capi.YmMapReframeStats()
+        rc = self.m._lib.ym_map_reframe(self.m._m, self._h, dx, dy, width, height, hs, poses.ctypes.data_as(C.POINTER(C.c_double)),
+                                        len(held), C.byref(st))
+        out = MapReframeStats(st.kept, st.restamped, st.dropped, st.recomputed, st.mismatch, st.x0, st.y0, st.width, st.height)
+        if st.mismatch != 0:
+            raise RuntimeError("CorrelationMap: the kept cells' counts and the held scans' readings there differ by %d: the map's "
+                               "counts and the scans it is said to hold disagree; nothing was changed (%r)" % (st.mismatch, out))
+        _capi.check(rc)
+        if (dx, dy, width, height) != (0, 0, old[2], old[3]):
+            anchor = self.anchor
+            self._offset = (old[0] + dx, old[1] + dy)
+            self.shape = (height, width)
+            if counted:
+                res = float(self.m._cfg.resolution)
+                self._anchor = anchor
+                self.origin = (anchor[0] + self._offset[0] * res, anchor[1] + self._offset[1] * res)
+            self.revision += 1
+        return out
 
     def stamps(self):
         """the number of readings stamped in each cell of a counted map (uint32, the map's shape)"""
