@@ -402,6 +402,42 @@ int ym_map_track(ym_matcher *m, const ym_map *map, double ox, double oy, ym_scan
                  const int32_t *track_offsets, int n_tracks, int start, int penalize, int refine, const ym_map_search *coarse,
                  double min_response, ym_result *results, int32_t *n_done);
 
+/* ---- scan sets against chains: Scan2DMatcherPy.match_scan_sets (yag_slam/scan_matching.py:56-122; DESIGN.md
+ * section 18).  The point readings of the query scans, at their own poses, are matched as ONE point set against the grid built from
+ * the base scans.
+ *   ym_match_sets       the centre is the mean of the query positions (Python's left-to-right sum / count), heading 0; the grid is the
+ *                       reference's G x G cells, G = int(search_size / res + 1 + 2 range_threshold / res), its corner (G - 1) / 2 cells
+ *                       below the centre; every point reading of every base scan (r <= the scan's threshold, not NaN) passes
+ *                       validate_points with the position of the LAST query scan as view-point (the loop variable the reference leaves
+ *                       behind at :72-80), is rounded half to even to its cell and max-stamped with the smear kernel, stamps and taps
+ *                       outside the grid dropped; a base scan with fewer than two point readings contributes nothing.  Coarse pass:
+ *                       the symmetric find_best_pose around the centre with search_size / 2, 2 res, coarse_search_angle_offset / 2,
+ *                       coarse_angle_resolution and `penalize`, the penalty centred on the grid's centre; if `refine` the fine pass
+ *                       around its result (+-2 res at res, +-0.01745 rad at 0.00349).  out->pose is the corrected centre (x, y,
+ *                       heading), out->cov the coarse pass's xx, yy, xy and the fine pass's th (4 coarse_angle_resolution without it);
+ *                       the caller moves the queries (the reference returns diff (+) query pose, diff = corrected centre (-) centre).
+ *                       Query scans without a point reading add no point, but count in the mean and as the view-point; a set without
+ *                       any point has out->status != 0.
+ *   ym_match_sets_many  n_items such calls in one enqueue and one wait: item i is the set queries[set_offsets[i] .. set_offsets[i+1])
+ *                       against the chain base[chain_offsets[i] .. chain_offsets[i+1]); results[i] is byte for byte the ym_result of
+ *                       ym_match_sets on that item alone, and an item whose status is not 0 leaves its neighbours alone.  A launch
+ *                       serves every item of a chunk; the scratch is bounded (512 MiB of grids, 256 MiB of volumes), more items run
+ *                       as consecutive chunks inside the call and no result depends on the chunk length (debug option 48 forces it).
+ *                       The integer sums of both passes come from yag_map_kernel -- one rounding per (point, lattice column or row)
+ *                       -- for lattices up to 64 positions per axis and from the pair-by-pair kernel for wider ones or when debug
+ *                       option 46 is 0 (ym_debug_counters [8], [9]).
+ * Both use the matcher's synchronous slot and stream and never throw; the matcher's windows, point cache and pair lists are neither
+ * read nor written.  After either, ym_debug_sums (dense [nt][ny][nx] with the item's own dims, as ym_debug_map_sums),
+ * ym_debug_grid / ym_debug_grid_info (the G x G bytes of an item of the last chunk) and ym_debug_query_local (the set's points
+ * relative to its centre) describe the call's items.
+ * YM_ERR_INVALID: a null argument, n_items outside [1, 2^20], a negative offset or chain length, an empty set or one of more than 64
+ * scans, a null scan, a scan on another device.  YM_ERR_UNSUPPORTED: a matcher that is not YM_SEM_YAGPY (Karto has no such call), a
+ * scan of more than 6000 readings, a grid of more than 10^9 cells.  A refused call changes nothing. */
+int ym_match_sets(ym_matcher *m, const ym_scan *const *queries, int n_queries, const ym_scan *const *base, int n_base,
+                  int penalize, int refine, ym_result *out);
+int ym_match_sets_many(ym_matcher *m, const ym_scan *const *queries, const int32_t *set_offsets, const ym_scan *const *base,
+                       const int32_t *chain_offsets, int n_items, int penalize, int refine, ym_result *results);
+
 /* ---- occupancy-grid rendering: karto_scanmatcher.create_occupancy_grid(scans, resolution, range_threshold)
  * (/root/reference/yag_slam/graph_slam.py:341-342, /root/reference/ros1/slam_node_ros1:187-202).  Every scan is ray-traced
  * from its pose (open_karto OccupancyGrid::CreateFromScans): cells count passes and end-point hits, a cell passed more
@@ -773,12 +809,13 @@ int ym_debug_pair_lists(ym_matcher *m, int slot, ym_pair_list_info *info, double
  *   41      n                              items up to which the order-dependent smear rule runs in its split form (8; 0 = never)
  *   45      0                              the pair lists of a single-query batch are built at every call (default: a call whose query,
  *                                          pose, window and lattice equal those of the last list build finds them in place)
- *   46      0 / 2                          YM_SEM_YAGPY, 0: both passes scored pair by pair, the Python rule as written (default: the coarse
+ *   46      0 / 2                          YM_SEM_YAGPY, 0: both passes scored pair by pair, the Python rule as written -- set calls too (default: the coarse
  *                                          pass's integer sums come from the production correlate kernels wherever the item's roundings
  *                                          provably form a lattice: ym_debug_counters; the fine pass's are taken row by row);
  *                                          2: the default, with the fine pass reading its rows byte by byte (the path of a row whose
  *                                          columns do not fit one 8-byte read)
  *   47      n / 0                          items per chunk of ym_match_map_many whatever its scratch budget says / by the budget
+ *   48      n / 0                          items per chunk of ym_match_sets_many whatever its scratch budgets say / by the budgets
  *
  * Options 0, 32, 33, 35, 43 and 44 chose between correlate forms that no longer exist: YM_ERR_INVALID, like any unknown option.
  */
@@ -791,8 +828,10 @@ int ym_debug_option(ym_matcher *m, int option, int value);
  *   [4] single-query batches that found their pair lists in place (option 45);
  *   [5] the coarse correlate the LAST call launched: 0 correlate_kernel, 1 correlate_region_kernel, 2 gather_kernel, -1 none;
  *   [6] items of ym_match_map_many whose sums came from yag_map_kernel, [7] items it left to the pair-by-pair kernel (a coarse
- *   lattice of more than 64 positions on an axis) */
-#define YM_DEBUG_COUNTERS 8
+ *   lattice of more than 64 positions on an axis);
+ *   [8] items of ym_match_sets / ym_match_sets_many whose sums came from yag_map_kernel, [9] items left to the pair-by-pair kernel (a
+ *   coarse lattice of more than 64 positions on an axis, or option 46 = 0) */
+#define YM_DEBUG_COUNTERS 10
 int ym_debug_counters(ym_matcher *m, int64_t *out, int32_t count);
 
 /* test hook: the bytes of device memory and of pinned host memory that the library's handles hold right now, in this process (every

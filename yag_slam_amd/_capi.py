@@ -29,7 +29,7 @@ EXPORTS = (
     "ym_occmap_create", "ym_occmap_accumulate", "ym_occmap_clear", "ym_occmap_get_info", "ym_occmap_read", "ym_occmap_read_counts",
     "ym_occmap_debug_option", "ym_occmap_destroy",
     "ym_map_from_occupancy", "ym_map_from_grid", "ym_map_size", "ym_map_read", "ym_map_destroy", "ym_match_map",
-    "ym_match_map_many", "ym_map_track", "ym_debug_map_sums",
+    "ym_match_map_many", "ym_map_track", "ym_debug_map_sums", "ym_match_sets", "ym_match_sets_many",
     "ym_map_create_empty", "ym_map_add_scans", "ym_map_clear",
     "ym_map_create_counted", "ym_map_update_scans", "ym_map_counted", "ym_map_read_stamps",
     "ym_map_reframe", "ym_map_window", "ym_map_create_counted_window",
@@ -325,6 +325,8 @@ def lib():
     L.ym_map_track.argtypes = [vp, vp, C.c_double, C.c_double, C.POINTER(vp), dp, ip, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.POINTER(YmMapSearch), C.c_double, C.POINTER(YmResult), ip]
     L.ym_debug_map_sums.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_int64]
+    L.ym_match_sets.argtypes = [vp, C.POINTER(vp), C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(YmResult)]
+    L.ym_match_sets_many.argtypes = [vp, C.POINTER(vp), ip, C.POINTER(vp), ip, C.c_int, C.c_int, C.c_int, C.POINTER(YmResult)]
     L.ym_map_create_empty.restype = vp
     L.ym_map_create_empty.argtypes = [vp, C.c_int, C.c_int]
     L.ym_map_add_scans.argtypes = [vp, vp, C.c_double, C.c_double, C.POINTER(vp), C.c_int, C.POINTER(YmMapAddStats)]

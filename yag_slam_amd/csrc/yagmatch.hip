@@ -44,6 +44,7 @@ extern "C" {
 #include "ym_abi_maps.hpp"
 #include "ym_abi_occlive.hpp"
 #include "ym_abi_maptrack.hpp"
+#include "ym_abi_sets.hpp"
 #include "ym_abi_rays.hpp"
 #include "ym_abi_locate.hpp"
 #include "ym_abi_segments.hpp"

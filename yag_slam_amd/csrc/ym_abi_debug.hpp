@@ -1,8 +1,24 @@
 // ym_abi_debug.hpp -- C ABI: introspection for the parity tests, development options, profiling, counters
 // Part of yagmatch.hip (included inside its extern "C" block); not a header of its own.
 // ---- debug getters
+int ym_debug_map_sums(ym_matcher *m, int item, int pass, uint32_t *out, int64_t out_count);
+// the last completed call was ym_match_sets / ym_match_sets_many: the getters below describe its items
+static bool sets_debug(const ym_matcher *m) { return !m->last_valid && m->map_last.valid && m->sets_last.valid; }
 int ym_debug_grid_info(ym_matcher *m, int item, ym_grid_info *info) {
     if (!m || !info) return set_err(YM_ERR_INVALID, "null argument");
+    if (sets_debug(m)) { // the last call matched scan sets: an item's grid is the reference's whole G x G grid
+        const ym_matcher::SetsLast &sl = m->sets_last;
+        if (item < 0 || item >= m->map_last.n_items) return set_err(YM_ERR_INVALID, "no such item in the last call");
+        std::memset(info, 0, sizeof *info);
+        info->width = info->height = info->pitch = sl.G;
+        info->storage_w = info->storage_h = info->roi_w = info->roi_h = sl.G;
+        YmItemState s;
+        DEV_GUARD(m->device);
+        HIP_TRY(hipStreamSynchronize(m->stream));
+        HIP_TRY(hipMemcpy(&s, m->states.p + item, sizeof s, hipMemcpyDeviceToHost));
+        info->offset_x = s.off_x; info->offset_y = s.off_y;
+        return YM_OK;
+    }
     if (!m->last_valid || item < 0 || item >= m->last_B) return set_err(YM_ERR_INVALID, "no such item in the last call");
     const YmGeom &g = m->last_geom;
     info->width = g.win_w; info->height = g.win_w; info->pitch = g.pitch;
@@ -19,6 +35,17 @@ int ym_debug_grid_info(ym_matcher *m, int item, ym_grid_info *info) {
 
 int ym_debug_grid(ym_matcher *m, int item, uint8_t *out, int64_t out_bytes) {
     if (!m || !out) return set_err(YM_ERR_INVALID, "null argument");
+    if (sets_debug(m)) {
+        const ym_matcher::SetsLast &sl = m->sets_last;
+        if (item < 0 || item >= m->map_last.n_items) return set_err(YM_ERR_INVALID, "no such item in the last call");
+        if (item < sl.first_grid) return set_err(YM_ERR_INVALID, "the grid of item %d was overwritten: the call keeps those of its last chunk, from item %d on", item, sl.first_grid);
+        const int64_t need_s = (int64_t)sl.G * sl.G;
+        if (out_bytes < need_s) return set_err(YM_ERR_INVALID, "grid buffer too small: need %lld bytes", (long long)need_s);
+        DEV_GUARD(m->device);
+        HIP_TRY(hipStreamSynchronize(m->stream));
+        HIP_TRY(hipMemcpy(out, m->sets_grid.p + (size_t)(item - sl.first_grid) * sl.grid_stride, (size_t)need_s, hipMemcpyDeviceToHost));
+        return YM_OK;
+    }
     if (!m->last_valid || item < 0 || item >= m->last_B) return set_err(YM_ERR_INVALID, "no such item in the last call");
     const int64_t need = (int64_t)m->last_geom.pitch * m->last_geom.win_w;
     if (out_bytes < need) return set_err(YM_ERR_INVALID, "grid buffer too small: need %lld bytes", (long long)need);
@@ -30,6 +57,7 @@ int ym_debug_grid(ym_matcher *m, int item, uint8_t *out, int64_t out_bytes) {
 
 int ym_debug_sums(ym_matcher *m, int item, int pass, uint32_t *out, int64_t out_count) {
     if (!m || !out || pass < 0 || pass > 1) return set_err(YM_ERR_INVALID, "bad argument");
+    if (sets_debug(m)) return ym_debug_map_sums(m, item, pass, out, out_count); // (dense [k][iy][ix] with the item's own nx, ny, nt)
     if (!m->last_valid || item < 0 || item >= m->last_B) return set_err(YM_ERR_INVALID, "no such item in the last call");
     const size_t n = m->last_sums_stride[pass];
     if (n == 0) return set_err(YM_ERR_INVALID, "pass %d did not run", pass);
@@ -45,7 +73,9 @@ int ym_debug_sums(ym_matcher *m, int item, int pass, uint32_t *out, int64_t out_
 
 int ym_debug_query_local(ym_matcher *m, int item, double *out_xy, int32_t cap, int32_t *n) {
     if (!m || !out_xy || !n) return set_err(YM_ERR_INVALID, "null argument");
-    if (!m->last_valid || item < 0 || item >= m->last_B) return set_err(YM_ERR_INVALID, "no such item in the last call");
+    const bool sets = sets_debug(m); // (the points of the set, relative to its centre)
+    if (sets ? (item < 0 || item >= m->map_last.n_items) : (!m->last_valid || item < 0 || item >= m->last_B))
+        return set_err(YM_ERR_INVALID, "no such item in the last call");
     YmItemState s;
     DEV_GUARD(m->device);
     HIP_TRY(hipStreamSynchronize(m->stream));
@@ -168,6 +198,7 @@ int ym_debug_option(ym_matcher *m, int option, int value) {
     else if (option == 45) { m->list_cache_on = value != 0; m->list_key_valid = false; }
     else if (option == 46) m->yag_fast = value < 0 ? 0 : value > 2 ? 1 : value;
     else if (option == 47) m->map_chunk_forced = value > 0 ? value : 0;
+    else if (option == 48) m->sets_chunk_forced = value > 0 ? value : 0;
     else if (option == 34) m->corr_region_rsplit = value;
     else if (option == 36) m->raster_planes_only = value;
     else if (option == 37) m->raster_no_rowtab = value;
@@ -244,15 +275,17 @@ int ym_debug_counters(ym_matcher *m, int64_t *out, int32_t count) {
     std::memset(v, 0, sizeof v);
     if (m->yag_counters.p) {
         DEV_GUARD(m->device);
-        unsigned long long c[6];
+        unsigned long long c[8];
         HIP_TRY(hipStreamSynchronize(m->stream));
         HIP_TRY(hipMemcpy(c, m->yag_counters.p, sizeof c, hipMemcpyDeviceToHost));
         for (int i = 0; i < 4; i++) v[i] = (int64_t)c[i];
         v[6] = (int64_t)c[4]; v[7] = (int64_t)c[5];
+        v[8] = (int64_t)c[6]; v[9] = (int64_t)c[7];
     }
     v[4] = m->list_cache_hits;
     v[5] = m->last_corr_form;
     v[7] += m->map_fallback_host;
+    v[9] += m->sets_fallback_host;
     for (int i = 0; i < std::min<int>(count, YM_DEBUG_COUNTERS); i++) out[i] = v[i];
     return YM_OK;
 }

@@ -617,6 +617,7 @@ int ym_match_map(ym_matcher *m, const ym_map *mp, double ox, double oy, const ym
     out->n_query_points = r.nq;
     out->status = r.status;
     m->last_valid = false; // the debug getters describe match_scan calls
+    m->sets_last.valid = false;
     m->map_last.valid = true; m->map_last.n_items = 1; m->map_last.first_kept = 0; m->map_last.passes = refine ? 2 : 1; // (ym_debug_map_sums)
     m->map_last.vol = vol; m->map_last.pass_offset[0] = 0; m->map_last.pass_offset[1] = vol;
     return YM_OK;

@@ -158,6 +158,7 @@ int ym_match_map_many(ym_matcher *m, const ym_map *mp, double ox, double oy, con
         out->status = r.status;
     }
     m->last_valid = false; // the debug getters describe match_scan calls
+    m->sets_last.valid = false;
     m->map_last.valid = true; m->map_last.n_items = n_items; m->map_last.first_kept = first_kept; m->map_last.passes = passes;
     m->map_last.vol = vol; m->map_last.pass_offset[0] = 0; m->map_last.pass_offset[1] = sums_items * vol;
     return YM_OK;

@@ -164,6 +164,16 @@ struct ym_matcher {
     // what ym_debug_map_sums needs of the last map call: how many items, entries per item volume, where each pass starts in `sums`,
     // the first item whose volume is still there (a call too large to keep them all keeps its last chunk's)
     struct MapLast { bool valid = false; int n_items = 0, first_kept = 0, passes = 0; size_t vol = 0, pass_offset[2] = {0, 0}; } map_last;
+    // scan sets against chains (ym_match_sets_many, ym_abi_sets.hpp): the grids of one chunk's items, its (base scan, item) pairs and
+    // view-points, the byte table of the taps.  None of it is read or written by any other call.
+    DevBuf<uint8_t> sets_grid;
+    DevBuf<unsigned char> sets_desc;
+    DevBuf<uint8_t> sets_ktab;
+    int sets_chunk_forced = 0;       // option 48: items per chunk whatever the scratch budgets say (tests)
+    int64_t sets_fallback_host = 0;  // items of chunks whose lattice is so wide, or whose path is forced so, that yag_map_kernel was not launched
+    // what the debug getters need of the last set call (valid only while map_last is, and only for a set call): the grid's side, the
+    // bytes between two items' grids, the first item whose grid is still there (the last chunk's)
+    struct SetsLast { bool valid = false; int G = 0, first_grid = 0; size_t grid_stride = 0; } sets_last;
     DevBuf<double2> yrot;      // yagpy: points rotated per angle
     DevBuf<double> seq_pose;   // device-chained sequences: [0..2] the next step's odometry prior, [4 + 3k ..] the pose step k of the segment found
     DevBuf<int32_t> seq_fault; // ... and the first step the host has to repeat (0: none)

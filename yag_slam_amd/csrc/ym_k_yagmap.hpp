@@ -55,6 +55,8 @@ __global__ __launch_bounds__(1024) void map_points_many_kernel(MapPointsManyArgs
 // A few items alone leave the device empty -- one item is 21 blocks, each walking a thousand points one latency after the other -- so
 // on small calls map_split blocks share the points of an (item, angle): each adds its partial sums to the zeroed volume with integer
 // atomics (exact whatever the order) and yag_map_score_kernel scores the finished sums.  map_split = 1: the block scores its own.
+// YagArgs::map_sets (match_scan_sets, ym_k_sets.hpp): the map is the item's own grid (grid_stride), its corner the item's off_x, off_y,
+// and the penalty find_best_pose's, centred on the grid; the items are counted apart.
 #define YM_YAG_MAP_DIM 64
 #define YM_YAG_MAP_TILE 32
 __global__ __launch_bounds__(256) void yag_map_kernel(YagArgs a) {
@@ -68,14 +70,14 @@ __global__ __launch_bounds__(256) void yag_map_kernel(YagArgs a) {
     const YmItemState &st = a.states[b];
     const int nx = st.ydims[a.pass][0], ny = st.ydims[a.pass][1], nt = st.ydims[a.pass][2];
     const bool served = nx <= D && ny <= D;
-    if (a.counters && a.pass == 0 && k == 0 && part == 0 && tid == 0) atomicAdd(&a.counters[served ? 4 : 5], 1ull);
+    if (a.counters && a.pass == 0 && k == 0 && part == 0 && tid == 0) atomicAdd(&a.counters[(served ? 4 : 5) + (a.map_sets ? 2 : 0)], 1ull);
     if (!served || k >= nt || nx * ny == 0) return; // (block-uniform)
     const double *ax = a.axes + (size_t)b * 3 * YM_YAG_MAX_DIM;
     const double xv = lane < nx ? ax[lane] : 0.0, yv = lane < ny ? ax[YM_YAG_MAX_DIM + lane] : 0.0, tv = ax[2 * YM_YAG_MAX_DIM + k];
     if (tid == 0) s_cs = make_double2(cos(tv), sin(tv));
     __syncthreads();
     const double rc = s_cs.x, rs = s_cs.y;
-    const double ox = a.map_ox, oy = a.map_oy, res = a.map_res, rres = 1.0 / res;
+    const double ox = a.map_sets ? st.off_x : a.map_ox, oy = a.map_sets ? st.off_y : a.map_oy, res = a.map_res, rres = 1.0 / res;
     const int GW = a.map_w, GH = a.map_h;
     const double2 *__restrict__ ql = reinterpret_cast<const double2 *>(st.ql);
     const uint8_t *__restrict__ grid = a.grid + (size_t)b * a.grid_stride;
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(256) void yag_map_kernel(YagArgs a) {
         for (int j = 0; j < R; j++) {
             const int iy = w + NW * j;
             if (iy >= ny) continue;
-            if (S == 1) yag_store_score(a, st, b, k, iy, lane, nx, ny, acc[j], np, xv, ax[YM_YAG_MAX_DIM + iy], tv, ox, oy, res, GW, true);
+            if (S == 1) yag_store_score(a, st, b, k, iy, lane, nx, ny, acc[j], np, xv, ax[YM_YAG_MAX_DIM + iy], tv, ox, oy, res, GW, !a.map_sets);
             else if (acc[j]) atomicAdd(&a.sums[(size_t)b * a.vol_stride + ((size_t)k * ny + iy) * nx + lane], acc[j]);
         }
 }
@@ -141,8 +143,8 @@ __global__ __launch_bounds__(256) void yag_map_score_kernel(YagArgs a) {
     const int iy = c / nx, ix = c - iy * nx;
     const double *ax = a.axes + (size_t)b * 3 * YM_YAG_MAX_DIM;
     const unsigned sum = a.sums[(size_t)b * a.vol_stride + ((size_t)k * ny + iy) * nx + ix];
-    yag_store_score(a, st, b, k, iy, ix, nx, ny, sum, st.nq, ax[ix], ax[YM_YAG_MAX_DIM + iy], ax[2 * YM_YAG_MAX_DIM + k], a.map_ox, a.map_oy, a.map_res,
-                    a.map_w, true);
+    yag_store_score(a, st, b, k, iy, ix, nx, ny, sum, st.nq, ax[ix], ax[YM_YAG_MAX_DIM + iy], ax[2 * YM_YAG_MAX_DIM + k], a.map_sets ? st.off_x : a.map_ox,
+                    a.map_sets ? st.off_y : a.map_oy, a.map_res, a.map_w, !a.map_sets);
 }
 
 }  // namespace ym

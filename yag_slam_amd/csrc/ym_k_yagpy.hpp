@@ -55,6 +55,9 @@ struct YagArgs {
                                   // [4] map items yag_map_kernel served, [5] map items it left to yag_score_kernel (a lattice wider than its limit)
     int32_t map_dim, map_split;   // map batches: yag_map_kernel has scored the items whose lattice is at most map_dim wide per axis (0: it did
                                   // not run); map_split > 1: that many blocks share the points of an (item, angle) and add their sums up in `sums`
+    int32_t map_sets, map_pad;    // match_scan_sets (ym_k_sets.hpp): every item has a grid of its own (grid_stride) whose corner is its state's
+                                  // off_x, off_y, the penalty is find_best_pose's -- centred on the grid's centre -- and the items are
+                                  // counted in counters [6], [7]
 };
 
 // numpy.arange(start, stop, step) for float64: length and i-th value (DOUBLE_fill)
@@ -209,7 +212,8 @@ __global__ __launch_bounds__(256) void yag_score_kernel(YagArgs a) {
     const double *ax = a.axes + (size_t)b * 3 * YM_YAG_MAX_DIM;
     const double xv = ax[ix], yv = ax[YM_YAG_MAX_DIM + iy], tv = ax[2 * YM_YAG_MAX_DIM + k];
     const bool map = a.map_w > 0;
-    const double ox = map ? a.map_ox : st.off_x, oy = map ? a.map_oy : st.off_y, res = map ? a.map_res : a.g.res;
+    const bool shared = map && !a.map_sets; // (one map for all items, at the call's corner)
+    const double ox = shared ? a.map_ox : st.off_x, oy = shared ? a.map_oy : st.off_y, res = map ? a.map_res : a.g.res;
     const int GW = map ? a.map_w : a.g.roi_w, GH = map ? a.map_h : a.g.roi_w;
     const int w0 = map ? 0 : a.g.win_origin, ww = map ? a.map_w : a.g.win_w, wh = map ? a.map_h : a.g.win_w;
     const int pitch = map ? a.map_w : a.g.pitch;
@@ -234,7 +238,7 @@ __global__ __launch_bounds__(256) void yag_score_kernel(YagArgs a) {
         }
     }
     }
-    yag_store_score(a, st, b, k, iy, ix, nx, ny, sum, np, xv, yv, tv, ox, oy, res, GW, map);
+    yag_store_score(a, st, b, k, iy, ix, nx, ny, sum, np, xv, yv, tv, ox, oy, res, GW, shared);
 }
 
 // rint(d / res) without the division wherever that is provably the same integer.  With rres = fl(1 / res): q = fl(d * rres) and the

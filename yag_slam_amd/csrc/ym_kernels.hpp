@@ -29,6 +29,7 @@
 #include "ym_k_gather.hpp"
 #include "ym_k_yagpy.hpp"
 #include "ym_k_yagmap.hpp"
+#include "ym_k_sets.hpp"
 #include "ym_k_mapgrow.hpp"
 #include "ym_k_occupancy.hpp"
 #include "ym_k_raytrace.hpp"

@@ -473,6 +473,65 @@ class ScanMatcher(object):
             out.append(_map_set_result(res, s))
         return out
 
+    # ---- scan sets against chains ----------------------------------------------------------------
+    def match_scan_sets(self, query_scans, base_scans, penalty=True, do_fine=True):
+        """The reference's signature (scan_matching.py:56): the point readings of all `query_scans` (1 to 64) are matched as one
+        set against the grid built from `base_scans` -- centred on the mean query position, filtered from the position of the
+        LAST query scan, as the reference does.  Returns ScanMatcherResult(response, covariance, [pose of every query scan], meta);
+        the poses are the reference's `diff + q.corrected_pose` (:121), which is not a rigid motion of the set:
+        meta["rigid_poses"] is.  meta also holds "centre", "corrected_centre", "coarse_response", "coarse_dims", "fine_dims",
+        "n_query_points".  `"yagpy"` matchers only; a set without a point reading raises YmError."""
+        qs, bs = list(query_scans), list(base_scans)
+        if not qs:
+            raise ValueError("match_scan_sets: no query scan")
+        hq = (C.c_void_p * len(qs))(*[self._require_native(q) for q in qs])
+        hb = (C.c_void_p * max(1, len(bs)))(*[self._require_native(b) for b in bs])
+        res = _capi.YmResult()
+        _capi.check(self._lib.ym_match_sets(self._m, hq, len(qs), hb, len(bs), int(bool(penalty)), int(bool(do_fine)), C.byref(res)))
+        if res.status != 0:
+            raise _capi.YmError(res.status, "empty search lattice or no query point")
+        return _scan_set_result(res, qs)
+
+    def match_scan_sets_batch(self, query_sets, chains, penalty=True, do_fine=True, strict=True):
+        """N independent `match_scan_sets` calls in ONE enqueue (`ym_match_sets_many`): item i matches the scans of
+        `query_sets[i]` as one point set against `chains[i]`.  A single set -- a flat list of scans -- given with N chains is matched
+        against each of them (the loop-closure use).  Returns a list of ScanMatcherResult, each built exactly as `match_scan_sets`
+        builds its own for that item alone.  An item the matcher cannot serve (no query point, empty lattice) raises as the single
+        call does, or with strict=False is None in the list; its neighbours are unaffected.  Empty input or an empty set:
+        ValueError before the library is touched."""
+        sets, chs = list(query_sets), [list(c) for c in chains]
+        if not sets or not chs:
+            raise ValueError("match_scan_sets_batch: no query set or no chain")
+        if not isinstance(sets[0], (list, tuple)):
+            sets = [sets] * len(chs)  # one set, broadcast over the chains
+        else:
+            sets = [list(s) for s in sets]
+        if len(sets) != len(chs):
+            raise ValueError("match_scan_sets_batch: %d query sets and %d chains" % (len(sets), len(chs)))
+        for i, s in enumerate(sets):
+            if not s:
+                raise ValueError("match_scan_sets_batch: query set %d is empty" % i)
+        fq, oq, fb, ob = [], [0], [], [0]
+        for s, c in zip(sets, chs):
+            fq.extend(s)
+            oq.append(len(fq))
+            fb.extend(c)
+            ob.append(len(fb))
+        hq = (C.c_void_p * len(fq))(*[self._require_native(q) for q in fq])
+        hb = (C.c_void_p * max(1, len(fb)))(*[self._require_native(b) for b in fb])
+        per = (_capi.YmResult * len(sets))()
+        _capi.check(self._lib.ym_match_sets_many(self._m, hq, (C.c_int32 * len(oq))(*oq), hb, (C.c_int32 * len(ob))(*ob), len(sets),
+                                                 int(bool(penalty)), int(bool(do_fine)), per))
+        out = []
+        for i, (s, res) in enumerate(zip(sets, per)):
+            if res.status != 0:
+                if strict:
+                    raise _capi.YmError(res.status, "empty search lattice or no query point (item %d)" % i)
+                out.append(None)
+                continue
+            out.append(_scan_set_result(res, s))
+        return out
+
     def track_in_map(self, cmap, ox, oy, tracks, start=1, penalty=True, do_fine=True, coarse=None, min_response=0.0):
         """Follow scan streams through a resident map without growing a graph (`ym_map_track`).  `tracks`: a list of scans
         (one stream) or a list of such lists (streams in lock-step: step i of every track that still has a scan i is one
@@ -680,10 +739,11 @@ class ScanMatcher(object):
 
     def debug_counters(self):
         """dict of the matcher's counters since it was created (include/yagmatch.h, ym_debug_counters)"""
-        buf = (C.c_int64 * 8)()
-        _capi.check(self._lib.ym_debug_counters(self._m, buf, 8))
+        buf = (C.c_int64 * 10)()
+        _capi.check(self._lib.ym_debug_counters(self._m, buf, 10))
         return dict(yag_fast_items=int(buf[0]), yag_fallback_items=int(buf[1]), yag_pairs_checked=int(buf[2]),
                     yag_pairs_failed=int(buf[3]), list_cache_hits=int(buf[4]), map_kernel_items=int(buf[6]), map_fallback_items=int(buf[7]),
+                    sets_kernel_items=int(buf[8]), sets_fallback_items=int(buf[9]),
                     last_correlate={-1: None, 0: "correlate_kernel", 1: "correlate_region_kernel", 2: "gather_kernel"}[int(buf[5])])
 
     def profile(self, on=True):
@@ -939,6 +999,22 @@ def _map_set_result(res, query_scans):
     c0, c1 = r.meta["centre"], r.meta["corrected_centre"]
     r.meta["rigid_poses"] = _move_rigidly([q.corrected_pose for q in query_scans], c0[0], c0[1], c1[0], c1[1], c1[2] - c0[2])
     return ScanMatcherResult(r.response, r.covariance, [q.corrected_pose + diff for q in query_scans], r.meta)
+
+
+def _scan_set_result(res, query_scans):
+    """the ScanMatcherResult `match_scan_sets` builds from the library's ym_result of one set"""
+    r = _result(res)
+    # scan_matching.py:68-71,116-121: the centre is the mean query position with heading 0; every query is moved by
+    # (corrected centre - centre), composed from the LEFT: diff + q.corrected_pose, the reference's operand order
+    xs = [float(q.corrected_pose.x) for q in query_scans]
+    ys = [float(q.corrected_pose.y) for q in query_scans]
+    oxy = Transform.from_position_euler(sum(xs) / float(len(xs)), sum(ys) / float(len(ys)), 0, 0, 0, 0)
+    diff = r.best_pose - oxy
+    r.meta["centre"] = (oxy.x, oxy.y, 0.0)
+    r.meta["corrected_centre"] = (r.best_pose.x, r.best_pose.y, r.best_pose.euler[-1])
+    c0, c1 = r.meta["centre"], r.meta["corrected_centre"]
+    r.meta["rigid_poses"] = _move_rigidly([q.corrected_pose for q in query_scans], c0[0], c0[1], c1[0], c1[1], c1[2] - c0[2])
+    return ScanMatcherResult(r.response, r.covariance, [diff + q.corrected_pose for q in query_scans], r.meta)
 
 
 def _pick_polished(polished, meta):
