@@ -21,7 +21,11 @@ void enqueue_prepare(ym_matcher *m, const CallPlan &P) {
     const size_t lds = YM_PREP_LDS_BYTES(P.max_n);
     if (P.split_prepare) {
         if (P.n_jobs > 0) hipLaunchKernelGGL(ym::points_kernel, dim3(P.n_jobs), dim3(YM_POINTS_THREADS), lds, m->stream, a);
-        hipLaunchKernelGGL(ym::cells_kernel, dim3(P.max_base + 1, P.B), dim3(256), 0, m->stream, a);
+        // a scan's points staged in LDS while that leaves a CU as many blocks as the register path has (ym_k_prepare.hpp)
+        if (P.max_n <= YM_CELLS_STAGED_MAX_N)
+            hipLaunchKernelGGL(ym::cells_kernel<true>, dim3(P.max_base + 1, P.B), dim3(256), YM_CELLS_STAGED_LDS_BYTES(P.max_n), m->stream, a);
+        else
+            hipLaunchKernelGGL(ym::cells_kernel<false>, dim3(P.max_base + 1, P.B), dim3(256), 0, m->stream, a);
     } else {
         // (query, base scans, item).  One item: 1024 threads per scan -- a 1081-beam scan is then one pass of every phase
         // plus a tail instead of three passes, and the blocks have the chip to themselves

@@ -8,8 +8,17 @@ namespace ym {
 #define YM_PREP_LDS_BYTES(max_n) ((size_t)(max_n) * 25 + ((size_t)(max_n) / 64 + 2) * 4 + 16)
 #define YM_INLINE_SCANS 16
 #ifndef YM_CELLS_Q
-#define YM_CELLS_Q 3         // chunks of 256 points cells_kernel keeps in flight (see cells_from_cache)
+#define YM_CELLS_Q 3         // chunks of 256 points the REGISTER path of the cells stage keeps in flight (cells_from_cache: the fused
+                             // prepare_kernel and cells_kernel<false>); the staged path (cells_from_cache_staged) does not read it
 #endif
+// the staged path of cells_kernel (cells_from_cache_staged): chunks of 256 points whose loads one group issues together -- a
+// 1081-reading scan is one group -- and the longest scan of a call that still takes it.  A block stages 16 bytes per reading of
+// max_n in LDS, and the path is only worth having while a CU holds at least the seven blocks the register path's 72 VGPRs give
+// it: 160 KiB / 7 = 23 405 bytes, rounded down to the LDS allocation granule (1280 bytes) 23 040 = 1440 readings.  Argued from
+// occupancy; the crossover itself was not measured.
+#define YM_CELLS_GROUP 5
+#define YM_CELLS_STAGED_MAX_N 1440
+#define YM_CELLS_STAGED_LDS_BYTES(max_n) ((size_t)(max_n) * 16)
 struct YmInlineDesc {        // call descriptor passed in the kernel arguments (single item, few scans)
     YmItem item;
     YmScanRef scans[YM_INLINE_SCANS];
@@ -342,7 +351,8 @@ __device__ __forceinline__ void clear_slot(const PrepareArgs &a, int b, int slot
     for (int i = threadIdx.x; i < n_cchunks; i += NT) bbox[i] = make_int4(INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN);
 }
 
-// one base scan of one item from the point cache: no LDS, no barrier.  Two dependent rounds of loads (who decides point i,
+// one base scan of one item from the point cache, REGISTER path (the fused prepare_kernel's cache hits, and cells_kernel<false>
+// for calls whose scans are too long for the staged path below): no LDS, no barrier.  Two dependent rounds of loads (who decides point i,
 // with the point itself -> the two deciding points) are issued for Q chunks of the scan at a time, so a block waits two
 // round trips per Q * NT points instead of two per NT.  The kernel is bound by those round trips times the blocks a CU
 // holds, not by its bytes: a point is turned into its cell (one register) before its deciding points (eight) are asked for,
@@ -420,6 +430,108 @@ __device__ __forceinline__ void cells_from_cache(const PrepareArgs &a, int b, in
             const int x0 = row16_reduce(has ? c.x : INT32_MAX, OpMinI()), y0 = row16_reduce(has ? c.y : INT32_MAX, OpMinI());
             const int x1 = row16_reduce(has ? c.x : INT32_MIN, OpMaxI()), y1 = row16_reduce(has ? c.y : INT32_MIN, OpMaxI());
             if ((tid & (YM_BOX_CELLS - 1)) == 0 && i / YM_BOX_CELLS < n_cchunks) bbox[i / YM_BOX_CELLS] = make_int4(x0, y0, x1, y1);
+        }
+    }
+}
+
+// The same cells and boxes with the second round of loads taken out of the vector memory pipeline (cells_kernel<true>, calls whose
+// longest scan has at most YM_CELLS_STAGED_MAX_N readings).  The deciding points of a scan's readings are points of the same
+// scan, and the block loads every one of them anyway.  Round one: the loads of the point and of who decides it, for all chunks of
+// a group (YM_CELLS_GROUP chunks: a 1081-reading scan is one group) at once; a point that arrives becomes its cell -- one register
+// -- and goes to LDS at its index (lp, 16 bytes per reading).  One barrier.  Round two, chunk by chunk: the deciding pair from
+// LDS, the side test (the same operations in the same order as above), the store, the box.  A block waits ONE round trip to
+// memory per scan instead of two per Q chunks, and holds the eight registers of a deciding pair only for the chunk it is finishing.
+// A scan of more than one group stages all its points first; the groups after the first then fetch their deciding records in
+// round two (one more round trip per group) and take their own points back from LDS.
+template <int NT>
+__device__ __forceinline__ void cells_from_cache_staged(const PrepareArgs &a, int b, int slot, const YmScanRef &sr, const YmScanRef &qr, bool yag,
+                                                        double2 *lp /* LDS, [max_n] */) {
+    constexpr int G = YM_CELLS_GROUP;
+    // The cache's records through GLOBAL loads.  A pointer read from the scan table is a flat address to the compiler, and a flat
+    // load counts against the LDS counter as well as the memory counter: on this path, which waits on LDS, that cost 17 of 209 us.
+    typedef const __attribute__((address_space(1))) double *global_f64;
+    typedef const __attribute__((address_space(1))) YmGov *global_gov;
+    const global_f64 cpts = (global_f64)reinterpret_cast<const double *>(sr.cache + YM_CACHE_HEADER);
+    const global_gov cgov = (global_gov)reinterpret_cast<const YmGov *>(sr.cache + YM_CACHE_HEADER + (size_t)sr.n * 16);
+    auto point = [&](int i) { return make_double2(cpts[2 * (size_t)i], cpts[2 * (size_t)i + 1]); }; // (one 16-byte load)
+    const int np = *reinterpret_cast<const int *>(sr.cache);
+    const double off_x = qr.pose[0] - (0.5 * (a.g.roi_w - 1) * a.g.res);
+    const double off_y = qr.pose[1] - (0.5 * (a.g.roi_w - 1) * a.g.res);
+    const double vpx = qr.pose[0], vpy = qr.pose[1];
+    const int tid = threadIdx.x;
+    const int n_cchunks = YM_N_BOXES(a.max_n);
+    const int n_pad = n_cchunks * YM_BOX_CELLS;
+    YmCell *cells = a.cells + ((size_t)b * a.max_base + slot) * a.max_n;
+    int4 *bbox = a.bbox + ((size_t)b * a.max_base + slot) * n_cchunks;
+    auto cell_of = [&](const double2 &p) {
+        int gx, gy;
+        if (yag) {
+            gx = (int)rint((p.x - off_x) / a.g.res);
+            gy = (int)rint((p.y - off_y) / a.g.res);
+        } else {
+            gx = world_to_grid(p.x, off_x, a.g.scale);
+            gy = world_to_grid(p.y, off_y, a.g.scale);
+        }
+        return (gx >= 0 && gx < a.g.roi_w && gy >= 0 && gy < a.g.roi_w) ? ym_cell_pack(gx + a.g.border - a.g.win_origin, gy + a.g.border - a.g.win_origin)
+                                                                         : ym_cell_none();
+    };
+    // round one.  The first group: points and deciding records; what stays in registers is the record and the cell
+    YmGov g[G];
+    YmCell cw[G];
+    {
+        double2 p[G];
+#pragma unroll
+        for (int q = 0; q < G; q++) {
+            const int i = q * NT + tid;
+            g[q] = i < np ? cgov[i] : ym_gov_pack(make_int2(-1, np));
+            p[q] = point(i < np ? i : 0);
+        }
+#pragma unroll
+        for (int q = 0; q < G; q++) {
+            const int i = q * NT + tid;
+            if (i < np) lp[i] = p[q]; // (np <= sr.n <= max_n)
+            cw[q] = cell_of(p[q]);
+        }
+    }
+    // ... the groups after it (scans of more than G * NT readings): their points only
+    for (int i = G * NT + tid; i < np; i += NT) lp[i] = point(i);
+    __syncthreads();
+    // round two
+    auto finish = [&](int i, YmGov gv, YmCell cell) { // chunk by chunk; a row of 16 lanes covers one chunk of YM_BOX_CELLS cells
+        const int2 st = ym_gov_unpack(gv);
+        bool keep = false;
+        if (i < np && st.x >= 0 && st.y < np) {
+            const double2 f = lp[st.x], t = lp[st.y];
+            const double fx = f.x, fy = f.y, cx = t.x, cy = t.y;
+            const double aa = vpy - fy;
+            const double bb = fx - vpx;
+            const double cc = fy * vpx - fx * vpy;
+            const double ss = cx * aa + cy * bb + cc;
+            keep = yag ? (ss > 0.0) : !(ss < 0.0);
+        }
+        const YmCell w = keep ? cell : ym_cell_none();
+        const int2 c = ym_cell_unpack(w);
+        const bool has = c.x != YM_CELL_NONE;
+        if (i < a.max_n) cells[i] = w;
+        chain_check_cell(a, c);
+        const int x0 = row16_reduce(has ? c.x : INT32_MAX, OpMinI()), y0 = row16_reduce(has ? c.y : INT32_MAX, OpMinI());
+        const int x1 = row16_reduce(has ? c.x : INT32_MIN, OpMaxI()), y1 = row16_reduce(has ? c.y : INT32_MIN, OpMaxI());
+        if ((tid & (YM_BOX_CELLS - 1)) == 0 && i / YM_BOX_CELLS < n_cchunks) bbox[i / YM_BOX_CELLS] = make_int4(x0, y0, x1, y1);
+    };
+#pragma unroll
+    for (int q = 0; q < G; q++)
+        if (q * NT < n_pad) finish(q * NT + tid, g[q], cw[q]); // block-uniform
+    for (int i0 = G * NT; i0 < n_pad; i0 += G * NT) {
+        YmGov g2[G];
+#pragma unroll
+        for (int q = 0; q < G; q++) {
+            const int i = i0 + q * NT + tid;
+            g2[q] = i < np ? cgov[i] : ym_gov_pack(make_int2(-1, np));
+        }
+#pragma unroll
+        for (int q = 0; q < G; q++) {
+            const int i = i0 + q * NT + tid;
+            if (i0 + q * NT < n_pad) finish(i, g2[q], i < np ? cell_of(lp[i]) : ym_cell_none());
         }
     }
 }
@@ -583,9 +695,14 @@ __global__ __launch_bounds__(YM_POINTS_THREADS) void points_kernel(PrepareArgs a
     store_cache<NT>(sr, l, np, yag);
 }
 
-// ---- K1 for batches, second half: grid (max_base + 1, B), 256 threads, no dynamic LDS.  Block 0 of an item sets the
+// ---- K1 for batches, second half: grid (max_base + 1, B), 256 threads.  Block 0 of an item sets the
 // item up around its query's slot; block 1 + j turns base scan j's cached points into this item's cells.
+// STAGED (the host: max_n <= YM_CELLS_STAGED_MAX_N): dynamic LDS = YM_CELLS_STAGED_LDS_BYTES(max_n), a scan's points staged there
+// (cells_from_cache_staged); otherwise no dynamic LDS and the register path.  Block 0 and the cleared slots are the same in both
+// and use none of it.
+template <bool STAGED>
 __global__ __launch_bounds__(256) void cells_kernel(PrepareArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     constexpr int NT = 256;
     const int b = blockIdx.y;
     if (a.tile_max_zero && blockIdx.x == 0 && b == 0 && threadIdx.x == 0) *a.tile_max_zero = 0;
@@ -604,7 +721,8 @@ __global__ __launch_bounds__(256) void cells_kernel(PrepareArgs a) {
         clear_slot<NT>(a, b, slot);
         return;
     }
-    cells_from_cache<NT>(a, b, slot, a.scans[it.base_begin + slot], qr, a.g.semantics == 1);
+    if (STAGED) cells_from_cache_staged<NT>(a, b, slot, a.scans[it.base_begin + slot], qr, a.g.semantics == 1, reinterpret_cast<double2 *>(lds_raw));
+    else cells_from_cache<NT>(a, b, slot, a.scans[it.base_begin + slot], qr, a.g.semantics == 1);
 }
 
 // ================================================================== K1c tiles: the raster kernel's work list (batches)
@@ -615,7 +733,13 @@ __global__ __launch_bounds__(256) void cells_kernel(PrepareArgs a) {
 // bytes from an earlier call and only need clearing.  The raster kernel then runs one block per list entry.
 // (Doing this in the last prepare block to finish needs a device-scope release per block, which on this part
 // writes the XCD's L2 back: measured 98 -> 771 us for the prepare kernel.  A kernel boundary is cheaper.)
+// The one block of an item is a chain of short phases, so what it waits for is round trips to memory: ONE now.  The
+// item's boxes and the tile_zero bytes of the launched rectangle depend on nothing the kernel computes and are loaded
+// together before the first barrier; a thread keeps its first YM_TILES_KEEP boxes in registers for the second pass
+// (the hit slots) and re-reads only what lies beyond them, as it reads tile_zero bytes beyond its first YM_TILES_KEEP_Z.
 #define YM_TILES_THREADS 256
+#define YM_TILES_KEEP 3      // chunk boxes a thread keeps in registers between the two passes (the metric's 680 boxes: three a thread)
+#define YM_TILES_KEEP_Z 2    // tile_zero bytes a thread loads with them (tiles of the launched rectangle, 256 a round)
 struct TilesArgs {
     const int4 *bbox;        // [B][max_base][YM_N_BOXES(max_n)]
     uint32_t *tile_list;     // [B][tile_cap] tile index (tiy * tiles_x + tix), | 0x8000 = only needs clearing, | hits << 16 (0xffff =
@@ -644,18 +768,32 @@ __global__ __launch_bounds__(YM_TILES_THREADS) void tiles_kernel(TilesArgs a) {
     const int ltx = lx1 - lx0 + 1, lty = ly1 - ly0 + 1, nsub = ltx * lty;
     int *cnt = reinterpret_cast<int *>(tile_bits + nwords); // [nsub] hits per tile of the rectangle
     int *fill = cnt + nsub;                                 // [nsub] list position << 16 | hit slots filled
+    // everything the kernel reads that depends on nothing it computes, in ONE round of loads ahead of the first barrier: the
+    // thread's first YM_TILES_KEEP boxes (kept for the second pass) and the tile_zero bytes of its first YM_TILES_KEEP_Z tiles
+    const int n_boxes = a.max_base * YM_N_BOXES(a.max_n);
+    const int4 *bbox = a.bbox + (size_t)b * n_boxes;
+    const uint8_t *tz = a.tile_zero + (size_t)b * ntiles;
+    int4 mine[YM_TILES_KEEP];
+    uint8_t zero_of[YM_TILES_KEEP_Z];
+#pragma unroll
+    for (int k = 0; k < YM_TILES_KEEP; k++) {
+        const int c = k * NT + tid;
+        mine[k] = c < n_boxes ? bbox[c] : make_int4(INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN);
+    }
+#pragma unroll
+    for (int k = 0; k < YM_TILES_KEEP_Z; k++) {
+        const int i = k * NT + tid;
+        zero_of[k] = i < nsub ? tz[(ly0 + i / ltx) * a.tiles_x + lx0 + i % ltx] : (uint8_t)1;
+    }
     for (int i = tid; i < nwords; i += NT) tile_bits[i] = 0u;
     if (a.hits)
         for (int i = tid; i < nsub; i += NT) cnt[i] = 0;
     if (tid == 0) s_n = 0;
     __syncthreads();
-    const int n_boxes = a.max_base * YM_N_BOXES(a.max_n);
-    const int4 *bbox = a.bbox + (size_t)b * n_boxes;
     const int th_shift = a.tile_h == YM_TILE_H_TALL ? 6 : 5; // (tile heights are 32 or 64: a runtime division costs ~25 instructions)
     static_assert(YM_TILE_H == 32 && YM_TILE_H_TALL == 64, "tile heights as shifts");
-    for (int c = tid; c < n_boxes; c += NT) {
-        const int4 bb = bbox[c];
-        if (bb.x > bb.z) continue;
+    auto mark = [&](const int4 &bb) {
+        if (bb.x > bb.z) return;
         // tiles whose halo-extended rectangle [t*T - h, t*T + T + h - 1] meets the box (the raster kernel's own test)
         const int tx0 = max(lx0, max(bb.x - h, 0) / YM_TILE_W), tx1 = min(lx1, (bb.z + h) / YM_TILE_W);
         const int ty0 = max(ly0, max(bb.y - h, 0) >> th_shift), ty1 = min(ly1, (bb.w + h) >> th_shift);
@@ -665,32 +803,38 @@ __global__ __launch_bounds__(YM_TILES_THREADS) void tiles_kernel(TilesArgs a) {
                 atomicOr(&tile_bits[t >> 5], 1u << (t & 31));
                 if (a.hits) atomicAdd(&cnt[(ty - ly0) * ltx + (tx - lx0)], 1);
             }
-    }
+    };
+#pragma unroll
+    for (int k = 0; k < YM_TILES_KEEP; k++) mark(mine[k]);
+    for (int c = YM_TILES_KEEP * NT + tid; c < n_boxes; c += NT) mark(bbox[c]);
     __syncthreads();
-    const uint8_t *tz = a.tile_zero + (size_t)b * ntiles;
     uint32_t *list = a.tile_list + (size_t)b * a.tile_cap;
-    for (int i = tid; i < nsub; i += NT) {
+    auto enlist = [&](int i, bool zero) {
         const int ty = ly0 + i / ltx, tx = lx0 + i % ltx, t = ty * a.tiles_x + tx;
         const bool hit = (tile_bits[t >> 5] >> (t & 31)) & 1u;
-        if (hit || tz[t] == 0) {
+        if (hit || !zero) {
             const int at = atomicAdd(&s_n, 1);
             const uint32_t nh = !a.hits ? 0xffffu : cnt[i] > a.hit_limit ? 0xffffu : (uint32_t)cnt[i];
             list[at] = (uint32_t)(t | (hit ? 0 : 0x8000)) | nh << 16;
             if (a.hits) fill[i] = at << 16;
         }
-    }
+    };
+#pragma unroll
+    for (int k = 0; k < YM_TILES_KEEP_Z; k++)
+        if (k * NT + tid < nsub) enlist(k * NT + tid, zero_of[k] != 0);
+    for (int i = YM_TILES_KEEP_Z * NT + tid; i < nsub; i += NT) enlist(i, tz[(ly0 + i / ltx) * a.tiles_x + lx0 + i % ltx] != 0);
     __syncthreads();
     if (tid == 0) {
         a.tile_count[b] = s_n;
         if (s_n > *reinterpret_cast<volatile int32_t *>(a.tile_max)) atomicMax(a.tile_max, s_n); // (few blocks raise it)
     }
     if (!a.hits) return;
-    // the hit slots: every box again, to the entries of the tiles it reaches (in any order: the raster ORs bits)
+    // the hit slots: every box again -- the kept ones from their registers, the rest re-read --, to the entries of the tiles it
+    // reaches (in any order: the raster ORs bits)
     uint16_t *hits = a.hits + (size_t)b * a.tile_cap * YM_TILE_HITS;
     const int n_cchunks = YM_N_BOXES(a.max_n);
-    for (int c = tid; c < n_boxes; c += NT) {
-        const int4 bb = bbox[c];
-        if (bb.x > bb.z) continue;
+    auto scatter = [&](int c, const int4 &bb) {
+        if (bb.x > bb.z) return;
         const int slot = c / n_cchunks;
         const uint16_t first_cell = (uint16_t)(slot * a.max_n + (c - slot * n_cchunks) * YM_BOX_CELLS); // (the host: max_base * max_n < 65536)
         const int tx0 = max(lx0, max(bb.x - h, 0) / YM_TILE_W), tx1 = min(lx1, (bb.z + h) / YM_TILE_W);
@@ -702,7 +846,10 @@ __global__ __launch_bounds__(YM_TILES_THREADS) void tiles_kernel(TilesArgs a) {
                 const int old = atomicAdd(&fill[i], 1);
                 hits[(size_t)(old >> 16) * YM_TILE_HITS + (old & 0xffff)] = first_cell;
             }
-    }
+    };
+#pragma unroll
+    for (int k = 0; k < YM_TILES_KEEP; k++) scatter(k * NT + tid, mine[k]);
+    for (int c = YM_TILES_KEEP * NT + tid; c < n_boxes; c += NT) scatter(c, bbox[c]);
 }
 
 // ================================================================== K1b select (only when the smear kernel has taps == 100 off-centre)
