@@ -1661,6 +1661,37 @@ def test_order_dependent_smear_split_form():
     compare(cfg, q, base[3:8], True, True)
 
 
+def test_order_dependent_smear_three_forms_in_one_batch():
+    """The three forms of the "value already set" rule -- split (the default on a few items), the one-block kernel (debug option
+    41 = 0) and the global-memory kernel (debug option 10 = 1) -- on ONE ragged batch of chains of 1, 3 and 2 scans: three items is
+    the smallest batch with a non-zero item index (every form's per-item offsets into its tables) and an unused chain slot.  Twice
+    on each matcher (the split form's tables must come back clean).  Surviving cells and grid of every item, responses and
+    covariances are equal across the forms; item 1 equals its single call, and that chain the oracle's sequential rule."""
+    from yag_slam_amd.scan_matching import ScanMatcher
+    q, base = cfg2_scans(range_threshold=12.0)
+    nq, nb = _mk_native(q), [_mk_native(b) for b in base]
+    cfg = dict(resolution=0.005, smear_deviation=0.05, range_threshold=12.0)
+    ms = [ScanMatcher(cfg), ScanMatcher(cfg), ScanMatcher(cfg)]
+    ms[1].debug_option(41, 0)
+    ms[2].debug_option(10, 1)
+    chains = [nb[:1], nb[1:4], nb[4:6]]
+    for _ in range(2):
+        per = [m.match_scan_batch(nq, chains, True, True)[0] for m in ms]
+        for item in range(len(chains)):
+            cells = [m.debug_cells(item)[0] for m in ms]
+            grids = [m.debug_grid(item)[0] for m in ms]
+            for f in (1, 2):
+                assert np.array_equal(cells[0], cells[f]), (item, f)
+                assert np.array_equal(grids[0], grids[f]), (item, f)
+                assert per[0][item].response == per[f][item].response and per[0][item].covariance == per[f][item].covariance, (item, f)
+    for m, p in zip(ms, per):
+        z = m.match_scan(nq, chains[1], True, True)
+        assert p[1].response == z.response and p[1].covariance == z.covariance
+    for m in ms:
+        m.close()
+    compare(cfg, q, base[1:4], True, True)
+
+
 @pytest.mark.parametrize("seed", [11, 12, 13, 14])
 def test_order_dependent_smear_random_chains(seed):
     """Random chains (a random subset of the base scans in random order, poses jittered by up to 3 cm / 0.02 rad, one scan

@@ -562,3 +562,10 @@ def test_kernels_have_no_scratch_and_the_dominant_kernel_keeps_three_blocks_per_
     assert len(dom) == 1 and dom[0]["VGPRs"] <= 80 and dom[0]["Occupancy"] >= 6, dom
     binp = [v for k, v in kernels.items() if k.startswith("void ym::bin_kernel<false, 18>")]
     assert len(binp) == 1 and binp[0]["VGPRs"] <= 64, binp
+    # the occupancies DESIGN.md rests the cells stage on: seven waves per SIMD in both forms of cells_kernel (the register
+    # path's Q and the staged path's LDS budget are sized by them), and the four that select_kernel's 1024-thread block needs
+    for form in ("true", "false"):
+        cells = [v for k, v in kernels.items() if k.startswith("void ym::cells_kernel<%s>(" % form)]
+        assert len(cells) == 1 and cells[0]["Occupancy"] >= 7, (form, cells)
+    sel = [v for k, v in kernels.items() if "ym::select_kernel(" in k]  # (not a template: the demangler prints no "void " before it)
+    assert len(sel) == 1 and sel[0]["Occupancy"] >= 4, sel

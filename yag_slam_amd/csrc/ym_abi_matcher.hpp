@@ -39,9 +39,9 @@ ym_matcher *ym_create(const ym_config *cfg, int device) {
     m->stream = m->own_stream;
     pool_register_stream(device, m->own_stream, true);
     if (upload_lut(m) != YM_OK) { ym_destroy(m); return nullptr; }
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ym::select_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 9 * 16384);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ym::select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 9 * 16384);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ym::select_relax_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 16384);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ym::select_global_kernel<5>), hipFuncAttributeMaxDynamicSharedMemorySize, 1 << 17);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ym::select_global_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 1 << 17);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ym::prepare_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)YM_PREP_LDS_BYTES(YM_MAX_BEAMS));
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(ym::prepare_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize,

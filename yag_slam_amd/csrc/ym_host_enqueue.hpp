@@ -47,21 +47,20 @@ int enqueue_select(ym_matcher *m, const CallPlan &P) {
                        m->cfg.smear_deviation / m->cfg.resolution);
     if (log2cap > 14 || m->select_global) { // too long for one CU's LDS: the same rule with its tables in global memory
         const size_t cap = (size_t)1 << log2cap;
-        const int nb = 5; // (z2max <= 1 always: build_geometry)
-        int rc = m->sel_scratch.ensure((size_t)P.B * cap * (3 + (nb - 1)));
+        int rc = m->sel_scratch.ensure((size_t)P.B * cap * (3 + ym::SELECT_NEIGHBOURS)); // keys, states, earliest points, neighbour slots
         if (rc) return rc;
         ym::SelectGlobalArgs g;
-        g.cells = m->cells.p; g.max_n = P.max_n; g.max_base = P.max_base; g.z2max = m->z2max; g.log2cap = log2cap;
+        g.cells = m->cells.p; g.max_n = P.max_n; g.max_base = P.max_base; g.log2cap = log2cap;
         g.keys = m->sel_scratch.p; g.status = g.keys + (size_t)P.B * cap; g.minidx = g.status + (size_t)P.B * cap; g.nbr = g.minidx + (size_t)P.B * cap;
         HIP_TRY(hipMemsetAsync(g.keys, 0, (size_t)2 * P.B * cap * sizeof(unsigned), m->stream));
         HIP_TRY(hipMemsetAsync(g.minidx, 0xff, (size_t)P.B * cap * sizeof(unsigned), m->stream));
         const size_t lds = cap; // one byte per slot: the threads' lists of undecided slots
-        hipLaunchKernelGGL(ym::select_global_kernel<5>, dim3(P.B), dim3(1024), lds, m->stream, g);
+        hipLaunchKernelGGL(ym::select_global_kernel, dim3(P.B), dim3(1024), lds, m->stream, g);
         return YM_OK;
     }
-    if (m->z2max <= 1 && P.B <= m->select_split_max) {
+    if (P.B <= m->select_split_max) {
         // a few items: the parallel steps (hash, earlier neighbours) as launches over all points, the chain of decisions in one
-        // block per item (ym_k_prepare.hpp, select_relax_kernel)
+        // block per item (ym_k_select.hpp, select_relax_kernel)
         const size_t cap = (size_t)1 << log2cap;
         const size_t had = m->sel_tables.cap;
         int rc = m->sel_tables.ensure((size_t)2 * P.B * cap);
@@ -79,9 +78,9 @@ int enqueue_select(ym_matcher *m, const CallPlan &P) {
         return YM_OK;
     }
     ym::SelectArgs a;
-    a.cells = m->cells.p; a.max_n = P.max_n; a.max_base = P.max_base; a.z2max = m->z2max; a.log2cap = log2cap; a.stamps = P.stamps;
+    a.cells = m->cells.p; a.max_n = P.max_n; a.max_base = P.max_base; a.log2cap = log2cap; a.stamps = P.stamps;
     const size_t lds = (size_t)9 << log2cap;
-    hipLaunchKernelGGL(ym::select_kernel<5>, dim3(P.B), dim3(1024), lds, m->stream, a);
+    hipLaunchKernelGGL(ym::select_kernel, dim3(P.B), dim3(1024), lds, m->stream, a);
     return YM_OK;
 }
 

@@ -111,7 +111,7 @@ int upload_lut(ym_matcher *m) {
         if (lut[i] == YM_OCCUPIED) m->z2max = i;
     // (smear_deviation <= 10 * resolution, the reference's own assertion checked above, keeps the kernel below 100 from squared
     //  distance 2 on: 100 * exp(-0.5 * 2 / 100) rounds to 99.  The nine-neighbour form of the select rule is therefore never
-    //  needed and no longer instantiated -- select_kernel<9> spilled 240 bytes per lane.)
+    //  needed, and the select stage (ym_k_select.hpp) is written for the four neighbours of the plus-shaped disc alone.)
     if (m->z2max > 1) return set_err(YM_ERR_UNSUPPORTED, "smear kernel holds 100 out to squared distance %d", m->z2max);
     std::vector<uint8_t> q(n + 8, 0);
     for (int i = 0; i < n; i++) {

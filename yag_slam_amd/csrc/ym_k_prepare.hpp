@@ -1,4 +1,6 @@
-// ym_k_prepare.hpp -- K1 prepare_kernel, K1c tiles_kernel, K1b select_kernel.
+// ym_k_prepare.hpp -- K1 prepare: the scan projection and trigger chain (prepare_kernel, points_kernel, K0 structure_kernel), the
+// cells stage in its three drivers (prepare_cells fused, cells_from_cache in registers, cells_from_cache_staged through LDS) over one
+// statement of each cell rule (roi_offset, side_keeps, window_cell, store_cell), and K1c tiles_kernel.  K1b select: ym_k_select.hpp.
 // Part of ym_kernels.hpp (include that, not this file).
 #pragma once
 
@@ -285,71 +287,98 @@ __device__ __forceinline__ void init_item(const PrepareArgs &a, int b, const YmI
     }
 }
 
-__device__ __forceinline__ void chain_check_cell(const PrepareArgs &a, int2 c) {
-    if (a.fault && c.x != YM_CELL_NONE && (c.x < a.cell_box[0] || c.y < a.cell_box[1] || c.x > a.cell_box[2] || c.y > a.cell_box[3]))
-        atomicCAS(a.fault, 0, a.step);
+// ---- the rules of the cells stage, each stated once.  Window cells and grids are compared bit for bit with the oracle: the fp64
+// operations below are the oracle's, in its order.
+
+// world offset of ROI cell (0, 0) along one axis: MatchScan, "set scan pose to be center of grid"
+__device__ __forceinline__ double roi_offset(const YmGeom &g, double pose) { return pose - (0.5 * (g.roi_w - 1) * g.res); }
+
+// The query-dependent half of FindValidPoints: a point is kept iff its run's trigger pair (f, t) puts t on the far side of the
+// line through the viewpoint and f.
+__device__ __forceinline__ bool side_keeps(double vpx, double vpy, const double2 &f, const double2 &t, bool yag) {
+    const double fx = f.x, fy = f.y, cx = t.x, cy = t.y;
+    const double aa = vpy - fy;
+    const double bb = fx - vpx;
+    const double cc = fy * vpx - fx * vpy;
+    const double ss = cx * aa + cy * bb + cc;
+    return yag ? (ss > 0.0) : !(ss < 0.0);
 }
 
-// The query-dependent half of FindValidPoints + AddScan's cell lookup for one base scan of one item: point i is kept
-// iff its run's trigger pair (s, t) puts t on the far side of the line through the viewpoint and s; kept points
-// become window cells, 64 consecutive cells share a bounding box.  PT(i) / GOV(i) read point i and its (s, t) from
-// LDS (scan just projected) or from the matcher's point cache.
+// AddScan's cell lookup.  The ROI cell of world point p: Karto's WorldToGrid, or the Python matcher's rint.
+// (Into g by reference: with the cell returned by value, or as two ints, the compiler packs a window cell of the register path in
+//  three vector instructions instead of two; this way cells_kernel<false> keeps the instruction stream it had before the rule was
+//  shared -- scripts/kernel_asm_diff.py tells.)
+__device__ __forceinline__ void roi_cell(const PrepareArgs &a, bool yag, const double2 &p, double off_x, double off_y, int2 &g) {
+    int gx, gy;
+    if (yag) {
+        gx = (int)rint((p.x - off_x) / a.g.res);
+        gy = (int)rint((p.y - off_y) / a.g.res);
+    } else {
+        gx = world_to_grid(p.x, off_x, a.g.scale);
+        gy = world_to_grid(p.y, off_y, a.g.scale);
+    }
+    g = make_int2(gx, gy);
+}
+// ... and its window cell, "no cell" outside the ROI
+__device__ __forceinline__ YmCell window_cell(const PrepareArgs &a, bool yag, const double2 &p, double off_x, double off_y) {
+    int2 g;
+    roi_cell(a, yag, p, off_x, off_y, g);
+    return (g.x >= 0 && g.x < a.g.roi_w && g.y >= 0 && g.y < a.g.roi_w) ? ym_cell_pack(g.x + a.g.border - a.g.win_origin, g.y + a.g.border - a.g.win_origin)
+                                                                         : ym_cell_none();
+}
+
+// where base scan `slot` of item b leaves its cells and the boxes of its chunks (YM_BOX_CELLS consecutive cells share a box)
+struct CellSink {
+    YmCell *cells;
+    int4 *bbox;
+    int n_cchunks;
+};
+__device__ __forceinline__ CellSink cell_sink(const PrepareArgs &a, int b, int slot) {
+    CellSink o;
+    o.n_cchunks = YM_N_BOXES(a.max_n);
+    o.cells = a.cells + ((size_t)b * a.max_base + slot) * a.max_n;
+    o.bbox = a.bbox + ((size_t)b * a.max_base + slot) * o.n_cchunks;
+    return o;
+}
+// the tail of reading i: its cell (or "no cell") stored, a chained step's fault raised, and -- a row of 16 lanes covers one chunk,
+// so every lane of the row comes here -- the chunk's bounding box: the raster kernel reads a chunk only when this box touches its tile
+__device__ __forceinline__ void store_cell(const PrepareArgs &a, const CellSink &o, int i, YmCell w) {
+    const int2 c = ym_cell_unpack(w);
+    const bool has = c.x != YM_CELL_NONE;
+    if (i < a.max_n) o.cells[i] = w;
+    if (a.fault && has && (c.x < a.cell_box[0] || c.y < a.cell_box[1] || c.x > a.cell_box[2] || c.y > a.cell_box[3])) atomicCAS(a.fault, 0, a.step);
+    const int x0 = row16_reduce(has ? c.x : INT32_MAX, OpMinI()), y0 = row16_reduce(has ? c.y : INT32_MAX, OpMinI());
+    const int x1 = row16_reduce(has ? c.x : INT32_MIN, OpMaxI()), y1 = row16_reduce(has ? c.y : INT32_MIN, OpMaxI());
+    if ((threadIdx.x & (YM_BOX_CELLS - 1)) == 0 && i / YM_BOX_CELLS < o.n_cchunks) o.bbox[i / YM_BOX_CELLS] = make_int4(x0, y0, x1, y1);
+}
+
+// One base scan of one item, just projected (the fused prepare_kernel): kept points become window cells.  PT(i) / GOV(i) read
+// point i and its trigger pair from LDS or from the scan's known structure.
 template <int NT, typename PT, typename GOV>
 __device__ __forceinline__ void prepare_cells(const PrepareArgs &a, int b, int slot, int np, bool yag, double vpx, double vpy,
                                               double off_x, double off_y, PT pt_of, GOV gov_of) {
-    const int tid = threadIdx.x;
-    const int n_cchunks = YM_N_BOXES(a.max_n);
-    YmCell *cells = a.cells + ((size_t)b * a.max_base + slot) * a.max_n;
-    int4 *bbox = a.bbox + ((size_t)b * a.max_base + slot) * n_cchunks;
-    for (int i0 = 0; i0 < n_cchunks * YM_BOX_CELLS; i0 += NT) {
-        const int i = i0 + tid; // a row of 16 lanes covers one chunk of YM_BOX_CELLS cells
-        int2 c = make_int2(YM_CELL_NONE, YM_CELL_NONE);
+    const CellSink o = cell_sink(a, b, slot);
+    for (int i0 = 0; i0 < o.n_cchunks * YM_BOX_CELLS; i0 += NT) {
+        const int i = i0 + (int)threadIdx.x;
+        YmCell w = ym_cell_none();
         if (i < np) {
-            bool keep = false;
             const int2 g = gov_of(i);
-            if (g.x >= 0 && g.y < np) {
-                const double2 f = pt_of(g.x), cp = pt_of(g.y);
-                const double fx = f.x, fy = f.y, cx = cp.x, cy = cp.y;
-                const double aa = vpy - fy;
-                const double bb = fx - vpx;
-                const double cc = fy * vpx - fx * vpy;
-                const double ss = cx * aa + cy * bb + cc;
-                keep = yag ? (ss > 0.0) : !(ss < 0.0);
-            }
-            if (keep) {
-                const double2 p = pt_of(i);
-                int gx, gy;
-                if (yag) {
-                    gx = (int)rint((p.x - off_x) / a.g.res);
-                    gy = (int)rint((p.y - off_y) / a.g.res);
-                } else {
-                    gx = world_to_grid(p.x, off_x, a.g.scale);
-                    gy = world_to_grid(p.y, off_y, a.g.scale);
-                }
-                if (gx >= 0 && gx < a.g.roi_w && gy >= 0 && gy < a.g.roi_w)
-                    c = make_int2(gx + a.g.border - a.g.win_origin, gy + a.g.border - a.g.win_origin);
-            }
+            if (g.x >= 0 && g.y < np && side_keeps(vpx, vpy, pt_of(g.x), pt_of(g.y), yag)) w = window_cell(a, yag, pt_of(i), off_x, off_y);
         }
-        const bool has = c.x != YM_CELL_NONE;
-        if (i < a.max_n) cells[i] = has ? ym_cell_pack(c.x, c.y) : ym_cell_none();
-        chain_check_cell(a, c);
-        // bounding box of the chunk's rasterised cells: the raster kernel reads a chunk only when
-        // this box touches its tile
-        const int x0 = row16_reduce(has ? c.x : INT32_MAX, OpMinI()), y0 = row16_reduce(has ? c.y : INT32_MAX, OpMinI());
-        const int x1 = row16_reduce(has ? c.x : INT32_MIN, OpMaxI()), y1 = row16_reduce(has ? c.y : INT32_MIN, OpMaxI());
-        if ((tid & (YM_BOX_CELLS - 1)) == 0 && i / YM_BOX_CELLS < n_cchunks) bbox[i / YM_BOX_CELLS] = make_int4(x0, y0, x1, y1);
+        store_cell(a, o, i, w);
     }
 }
 
 // an unused chain slot of a ragged batch: no points (select_kernel walks every slot's cells), empty boxes
 template <int NT>
 __device__ __forceinline__ void clear_slot(const PrepareArgs &a, int b, int slot) {
-    const int n_cchunks = YM_N_BOXES(a.max_n);
-    YmCell *cells = a.cells + ((size_t)b * a.max_base + slot) * a.max_n;
-    int4 *bbox = a.bbox + ((size_t)b * a.max_base + slot) * n_cchunks;
-    for (int i = threadIdx.x; i < a.max_n; i += NT) cells[i] = ym_cell_none();
-    for (int i = threadIdx.x; i < n_cchunks; i += NT) bbox[i] = make_int4(INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN);
+    const CellSink o = cell_sink(a, b, slot);
+    for (int i = threadIdx.x; i < a.max_n; i += NT) o.cells[i] = ym_cell_none();
+    for (int i = threadIdx.x; i < o.n_cchunks; i += NT) o.bbox[i] = make_int4(INT32_MAX, INT32_MAX, INT32_MIN, INT32_MIN);
 }
+
+// the record of a reading past the scan's last: nobody decides it
+__device__ __forceinline__ YmGov gov_undecided(int np) { return ym_gov_pack(make_int2(-1, np)); }
 
 // one base scan of one item from the point cache, REGISTER path (the fused prepare_kernel's cache hits, and cells_kernel<false>
 // for calls whose scans are too long for the staged path below): no LDS, no barrier.  Two dependent rounds of loads (who decides point i,
@@ -365,14 +394,12 @@ __device__ __forceinline__ void cells_from_cache(const PrepareArgs &a, int b, in
     const double2 *__restrict__ cpts = reinterpret_cast<const double2 *>(sr.cache + YM_CACHE_HEADER);
     const YmGov *__restrict__ cgov = reinterpret_cast<const YmGov *>(sr.cache + YM_CACHE_HEADER + (size_t)sr.n * 16);
     const int np = *reinterpret_cast<const int *>(sr.cache);
-    const double off_x = qr.pose[0] - (0.5 * (a.g.roi_w - 1) * a.g.res);
-    const double off_y = qr.pose[1] - (0.5 * (a.g.roi_w - 1) * a.g.res);
+    const double off_x = roi_offset(a.g, qr.pose[0]), off_y = roi_offset(a.g, qr.pose[1]);
     const double vpx = qr.pose[0], vpy = qr.pose[1];
     const int tid = threadIdx.x;
-    const int n_cchunks = YM_N_BOXES(a.max_n);
-    YmCell *cells = a.cells + ((size_t)b * a.max_base + slot) * a.max_n;
-    int4 *bbox = a.bbox + ((size_t)b * a.max_base + slot) * n_cchunks;
-    for (int i0 = 0; i0 < n_cchunks * YM_BOX_CELLS; i0 += Q * NT) {
+    const CellSink o = cell_sink(a, b, slot);
+    const int n_pad = o.n_cchunks * YM_BOX_CELLS;
+    for (int i0 = 0; i0 < n_pad; i0 += Q * NT) {
         YmGov g[Q]; // (kept as loaded -- one register a chunk with the packed records -- and taken apart where it is used)
         YmCell cw[Q];
         double2 f[Q], t[Q];
@@ -381,24 +408,13 @@ __device__ __forceinline__ void cells_from_cache(const PrepareArgs &a, int b, in
 #pragma unroll
             for (int q = 0; q < Q; q++) {
                 const int i = i0 + q * NT + tid;
-                g[q] = i < np ? cgov[i] : ym_gov_pack(make_int2(-1, np));
+                g[q] = i < np ? cgov[i] : gov_undecided(np);
                 p[q] = cpts[i < np ? i : 0];
             }
             // where the point lies, before the deciding points are asked for: a cell is one register (two in the wide build), the
             // point was four, and the registers a chunk holds at its widest decide how many chunks a SIMD keeps in flight
 #pragma unroll
-            for (int q = 0; q < Q; q++) {
-                int gx, gy;
-                if (yag) {
-                    gx = (int)rint((p[q].x - off_x) / a.g.res);
-                    gy = (int)rint((p[q].y - off_y) / a.g.res);
-                } else {
-                    gx = world_to_grid(p[q].x, off_x, a.g.scale);
-                    gy = world_to_grid(p[q].y, off_y, a.g.scale);
-                }
-                cw[q] = (gx >= 0 && gx < a.g.roi_w && gy >= 0 && gy < a.g.roi_w) ? ym_cell_pack(gx + a.g.border - a.g.win_origin, gy + a.g.border - a.g.win_origin)
-                                                                                 : ym_cell_none();
-            }
+            for (int q = 0; q < Q; q++) cw[q] = window_cell(a, yag, p[q], off_x, off_y);
         }
         __builtin_amdgcn_sched_barrier(0); // (the deciding points' loads are not to be issued while the points are still held)
 #pragma unroll
@@ -410,26 +426,11 @@ __device__ __forceinline__ void cells_from_cache(const PrepareArgs &a, int b, in
         }
 #pragma unroll
         for (int q = 0; q < Q; q++) {
-            const int i = i0 + q * NT + tid; // a row of 16 lanes covers one chunk of YM_BOX_CELLS cells
-            if (i0 + q * NT >= n_cchunks * YM_BOX_CELLS) break; // block-uniform
+            const int i = i0 + q * NT + tid;
+            if (i0 + q * NT >= n_pad) break; // block-uniform
             const int2 st = ym_gov_unpack(g[q]);
-            bool keep = false;
-            if (i < np && st.x >= 0 && st.y < np) {
-                const double fx = f[q].x, fy = f[q].y, cx = t[q].x, cy = t[q].y;
-                const double aa = vpy - fy;
-                const double bb = fx - vpx;
-                const double cc = fy * vpx - fx * vpy;
-                const double ss = cx * aa + cy * bb + cc;
-                keep = yag ? (ss > 0.0) : !(ss < 0.0);
-            }
-            const YmCell w = keep ? cw[q] : ym_cell_none();
-            const int2 c = ym_cell_unpack(w);
-            const bool has = c.x != YM_CELL_NONE;
-            if (i < a.max_n) cells[i] = w;
-            chain_check_cell(a, c);
-            const int x0 = row16_reduce(has ? c.x : INT32_MAX, OpMinI()), y0 = row16_reduce(has ? c.y : INT32_MAX, OpMinI());
-            const int x1 = row16_reduce(has ? c.x : INT32_MIN, OpMaxI()), y1 = row16_reduce(has ? c.y : INT32_MIN, OpMaxI());
-            if ((tid & (YM_BOX_CELLS - 1)) == 0 && i / YM_BOX_CELLS < n_cchunks) bbox[i / YM_BOX_CELLS] = make_int4(x0, y0, x1, y1);
+            const bool keep = i < np && st.x >= 0 && st.y < np && side_keeps(vpx, vpy, f[q], t[q], yag);
+            store_cell(a, o, i, keep ? cw[q] : ym_cell_none());
         }
     }
 }
@@ -439,7 +440,7 @@ __device__ __forceinline__ void cells_from_cache(const PrepareArgs &a, int b, in
 // scan, and the block loads every one of them anyway.  Round one: the loads of the point and of who decides it, for all chunks of
 // a group (YM_CELLS_GROUP chunks: a 1081-reading scan is one group) at once; a point that arrives becomes its cell -- one register
 // -- and goes to LDS at its index (lp, 16 bytes per reading).  One barrier.  Round two, chunk by chunk: the deciding pair from
-// LDS, the side test (the same operations in the same order as above), the store, the box.  A block waits ONE round trip to
+// LDS, the side test, the store, the box.  A block waits ONE round trip to
 // memory per scan instead of two per Q chunks, and holds the eight registers of a deciding pair only for the chunk it is finishing.
 // A scan of more than one group stages all its points first; the groups after the first then fetch their deciding records in
 // round two (one more round trip per group) and take their own points back from LDS.
@@ -455,26 +456,11 @@ __device__ __forceinline__ void cells_from_cache_staged(const PrepareArgs &a, in
     const global_gov cgov = (global_gov)reinterpret_cast<const YmGov *>(sr.cache + YM_CACHE_HEADER + (size_t)sr.n * 16);
     auto point = [&](int i) { return make_double2(cpts[2 * (size_t)i], cpts[2 * (size_t)i + 1]); }; // (one 16-byte load)
     const int np = *reinterpret_cast<const int *>(sr.cache);
-    const double off_x = qr.pose[0] - (0.5 * (a.g.roi_w - 1) * a.g.res);
-    const double off_y = qr.pose[1] - (0.5 * (a.g.roi_w - 1) * a.g.res);
+    const double off_x = roi_offset(a.g, qr.pose[0]), off_y = roi_offset(a.g, qr.pose[1]);
     const double vpx = qr.pose[0], vpy = qr.pose[1];
     const int tid = threadIdx.x;
-    const int n_cchunks = YM_N_BOXES(a.max_n);
-    const int n_pad = n_cchunks * YM_BOX_CELLS;
-    YmCell *cells = a.cells + ((size_t)b * a.max_base + slot) * a.max_n;
-    int4 *bbox = a.bbox + ((size_t)b * a.max_base + slot) * n_cchunks;
-    auto cell_of = [&](const double2 &p) {
-        int gx, gy;
-        if (yag) {
-            gx = (int)rint((p.x - off_x) / a.g.res);
-            gy = (int)rint((p.y - off_y) / a.g.res);
-        } else {
-            gx = world_to_grid(p.x, off_x, a.g.scale);
-            gy = world_to_grid(p.y, off_y, a.g.scale);
-        }
-        return (gx >= 0 && gx < a.g.roi_w && gy >= 0 && gy < a.g.roi_w) ? ym_cell_pack(gx + a.g.border - a.g.win_origin, gy + a.g.border - a.g.win_origin)
-                                                                         : ym_cell_none();
-    };
+    const CellSink o = cell_sink(a, b, slot);
+    const int n_pad = o.n_cchunks * YM_BOX_CELLS;
     // round one.  The first group: points and deciding records; what stays in registers is the record and the cell
     YmGov g[G];
     YmCell cw[G];
@@ -483,40 +469,24 @@ __device__ __forceinline__ void cells_from_cache_staged(const PrepareArgs &a, in
 #pragma unroll
         for (int q = 0; q < G; q++) {
             const int i = q * NT + tid;
-            g[q] = i < np ? cgov[i] : ym_gov_pack(make_int2(-1, np));
+            g[q] = i < np ? cgov[i] : gov_undecided(np);
             p[q] = point(i < np ? i : 0);
         }
 #pragma unroll
         for (int q = 0; q < G; q++) {
             const int i = q * NT + tid;
             if (i < np) lp[i] = p[q]; // (np <= sr.n <= max_n)
-            cw[q] = cell_of(p[q]);
+            cw[q] = window_cell(a, yag, p[q], off_x, off_y);
         }
     }
     // ... the groups after it (scans of more than G * NT readings): their points only
     for (int i = G * NT + tid; i < np; i += NT) lp[i] = point(i);
     __syncthreads();
     // round two
-    auto finish = [&](int i, YmGov gv, YmCell cell) { // chunk by chunk; a row of 16 lanes covers one chunk of YM_BOX_CELLS cells
+    auto finish = [&](int i, YmGov gv, YmCell cell) { // chunk by chunk
         const int2 st = ym_gov_unpack(gv);
-        bool keep = false;
-        if (i < np && st.x >= 0 && st.y < np) {
-            const double2 f = lp[st.x], t = lp[st.y];
-            const double fx = f.x, fy = f.y, cx = t.x, cy = t.y;
-            const double aa = vpy - fy;
-            const double bb = fx - vpx;
-            const double cc = fy * vpx - fx * vpy;
-            const double ss = cx * aa + cy * bb + cc;
-            keep = yag ? (ss > 0.0) : !(ss < 0.0);
-        }
-        const YmCell w = keep ? cell : ym_cell_none();
-        const int2 c = ym_cell_unpack(w);
-        const bool has = c.x != YM_CELL_NONE;
-        if (i < a.max_n) cells[i] = w;
-        chain_check_cell(a, c);
-        const int x0 = row16_reduce(has ? c.x : INT32_MAX, OpMinI()), y0 = row16_reduce(has ? c.y : INT32_MAX, OpMinI());
-        const int x1 = row16_reduce(has ? c.x : INT32_MIN, OpMaxI()), y1 = row16_reduce(has ? c.y : INT32_MIN, OpMaxI());
-        if ((tid & (YM_BOX_CELLS - 1)) == 0 && i / YM_BOX_CELLS < n_cchunks) bbox[i / YM_BOX_CELLS] = make_int4(x0, y0, x1, y1);
+        const bool keep = i < np && st.x >= 0 && st.y < np && side_keeps(vpx, vpy, lp[st.x], lp[st.y], yag);
+        store_cell(a, o, i, keep ? cell : ym_cell_none());
     };
 #pragma unroll
     for (int q = 0; q < G; q++)
@@ -526,14 +496,33 @@ __device__ __forceinline__ void cells_from_cache_staged(const PrepareArgs &a, in
 #pragma unroll
         for (int q = 0; q < G; q++) {
             const int i = i0 + q * NT + tid;
-            g2[q] = i < np ? cgov[i] : ym_gov_pack(make_int2(-1, np));
+            g2[q] = i < np ? cgov[i] : gov_undecided(np);
         }
 #pragma unroll
         for (int q = 0; q < G; q++) {
             const int i = i0 + q * NT + tid;
-            if (i0 + q * NT < n_pad) finish(i, g2[q], i < np ? cell_of(lp[i]) : ym_cell_none());
+            if (i0 + q * NT < n_pad) finish(i, g2[q], i < np ? window_cell(a, yag, lp[i], off_x, off_y) : ym_cell_none());
         }
     }
+}
+
+// scan si of the call, at the pose the device holds for it (a chained step's pose comes from the step before: pose_dev)
+__device__ __forceinline__ YmScanRef call_scan(const PrepareArgs &a, int si) {
+    YmScanRef sr = a.use_inline ? a.inl.scans[si] : a.scans[si];
+    if (sr.pose_dev) { sr.pose[0] = sr.pose_dev[0]; sr.pose[1] = sr.pose_dev[1]; sr.pose[2] = sr.pose_dev[2]; }
+    return sr;
+}
+
+// "project this scan": its point readings -> l.sx, l.sy, their number returned.  A base scan at its pose; a query too, except in
+// the Python matcher's semantics, which match the query's sensor-frame points (identity pose).  With the scan's structure known
+// (cidx, and with it gov: trusted at this pose) the indexed form, with_gov: its deciding pairs into LDS beside the points.
+__device__ __forceinline__ bool scan_indexed(const YmScanRef &sr) { return sr.cidx != nullptr && sr.n > 0; }
+template <int NT>
+__device__ __forceinline__ int project_scan(const YmScanRef &sr, bool is_query, bool yag, const PrepLds &l, int *s_cnt, bool with_gov) {
+    const double px = (is_query && yag) ? 0.0 : sr.pose[0];
+    const double py = (is_query && yag) ? 0.0 : sr.pose[1];
+    const double pt = (is_query && yag) ? 0.0 : sr.pose[2];
+    return scan_indexed(sr) ? project_points_indexed<NT>(sr, px, py, pt, l, with_gov) : project_points<NT>(sr, px, py, pt, yag, l.sx, l.sy, s_cnt);
 }
 
 // ---- K1, fused form (a few items): grid (max_base + 2, B), NT threads, dynamic LDS = YM_PREP_LDS_BYTES(max_n).
@@ -555,11 +544,8 @@ __global__ __launch_bounds__(NT) void prepare_kernel(PrepareArgs a) {
         // the item's block: everything that depends on the query's POSE and the lattice but not on its readings (state,
         // (cos, sin) per coarse angle -- fp64 sin / cos on a handful of lanes is a 1.3 us chain --, hypothesis cells, the
         // cleared maxima) runs beside the query's projection instead of after it
-        YmScanRef qr = a.use_inline ? a.inl.scans[it.query] : a.scans[it.query];
-        if (qr.pose_dev) { qr.pose[0] = qr.pose_dev[0]; qr.pose[1] = qr.pose_dev[1]; qr.pose[2] = qr.pose_dev[2]; }
-        const double off_x = qr.pose[0] - (0.5 * (a.g.roi_w - 1) * a.g.res);
-        const double off_y = qr.pose[1] - (0.5 * (a.g.roi_w - 1) * a.g.res);
-        init_item<NT>(a, b, it, qr, -1, b, a.qlocal + (size_t)b * a.max_n, off_x, off_y);
+        const YmScanRef qr = call_scan(a, it.query);
+        init_item<NT>(a, b, it, qr, -1, b, a.qlocal + (size_t)b * a.max_n, roi_offset(a.g, qr.pose[0]), roi_offset(a.g, qr.pose[1]));
         YM_STAMP_B1(a, 21);
         return;
     }
@@ -568,10 +554,8 @@ __global__ __launch_bounds__(NT) void prepare_kernel(PrepareArgs a) {
         return;
     }
     const int si = is_query ? it.query : it.base_begin + slot;
-    YmScanRef sr = a.use_inline ? a.inl.scans[si] : a.scans[si];
-    YmScanRef qr = a.use_inline ? a.inl.scans[it.query] : a.scans[it.query];
-    if (sr.pose_dev) { sr.pose[0] = sr.pose_dev[0]; sr.pose[1] = sr.pose_dev[1]; sr.pose[2] = sr.pose_dev[2]; }
-    if (qr.pose_dev) { qr.pose[0] = qr.pose_dev[0]; qr.pose[1] = qr.pose_dev[1]; qr.pose[2] = qr.pose_dev[2]; }
+    YmScanRef sr = call_scan(a, si);
+    const YmScanRef qr = call_scan(a, it.query);
     if (a.fault && *a.fault) { // a chained step after a fault: nothing to do (the host repeats it); leave an empty problem
         if (!is_query) { clear_slot<NT>(a, b, slot); return; }
         sr.n = 0;
@@ -582,16 +566,9 @@ __global__ __launch_bounds__(NT) void prepare_kernel(PrepareArgs a) {
         return;
     }
     const PrepLds l = prep_lds(lds_raw, a.max_n);
-    const double px = (is_query && yag) ? 0.0 : sr.pose[0];
-    const double py = (is_query && yag) ? 0.0 : sr.pose[1];
-    const double pt = (is_query && yag) ? 0.0 : sr.pose[2];
-    const bool indexed = sr.cidx != nullptr && sr.n > 0; // (with cidx comes gov: the scan's structure is trusted at this pose)
-    const int np = indexed ? project_points_indexed<NT>(sr, px, py, pt, l, !is_query) : project_points<NT>(sr, px, py, pt, yag, l.sx, l.sy, s_cnt);
+    const int np = project_scan<NT>(sr, is_query, yag, l, s_cnt, !is_query);
     YM_STAMP(a, 1);
     YM_STAMP_B1(a, 20);
-    // world offset of ROI cell (0,0): MatchScan, "set scan pose to be center of grid"
-    const double off_x = qr.pose[0] - (0.5 * (a.g.roi_w - 1) * a.g.res);
-    const double off_y = qr.pose[1] - (0.5 * (a.g.roi_w - 1) * a.g.res);
     if (is_query) {
         store_query_local<NT>(sr, l, np, yag, a.qlocal + (size_t)b * a.max_n);
         if (threadIdx.x == 0) { a.qnp[b] = np; a.states[b].nq = np; } // (the rest of the state: the item's block)
@@ -603,15 +580,14 @@ __global__ __launch_bounds__(NT) void prepare_kernel(PrepareArgs a) {
     if (!known) mark_chain<NT>(l, np, yag);
     YM_STAMP_B1(a, 22);
     if (sr.cache) store_cache<NT>(sr, l, np, yag);
-    if (indexed) // (the deciding pairs came into LDS with the points)
-        prepare_cells<NT>(a, b, slot, np, yag, qr.pose[0], qr.pose[1], off_x, off_y,
-                          [&](int i) { return make_double2(l.sx[i], l.sy[i]); }, [&](int i) { return make_int2(l.nxt[i], l.ex[i]); });
+    const double off_x = roi_offset(a.g, qr.pose[0]), off_y = roi_offset(a.g, qr.pose[1]);
+    auto pt_of = [&](int i) { return make_double2(l.sx[i], l.sy[i]); };
+    if (scan_indexed(sr)) // (the deciding pairs came into LDS with the points)
+        prepare_cells<NT>(a, b, slot, np, yag, qr.pose[0], qr.pose[1], off_x, off_y, pt_of, [&](int i) { return make_int2(l.nxt[i], l.ex[i]); });
     else if (known)
-        prepare_cells<NT>(a, b, slot, np, yag, qr.pose[0], qr.pose[1], off_x, off_y,
-                          [&](int i) { return make_double2(l.sx[i], l.sy[i]); }, [&](int i) { return known[i]; });
+        prepare_cells<NT>(a, b, slot, np, yag, qr.pose[0], qr.pose[1], off_x, off_y, pt_of, [&](int i) { return known[i]; });
     else
-        prepare_cells<NT>(a, b, slot, np, yag, qr.pose[0], qr.pose[1], off_x, off_y,
-                          [&](int i) { return make_double2(l.sx[i], l.sy[i]); }, [&](int i) { return gov_walk(l, i, np, yag); });
+        prepare_cells<NT>(a, b, slot, np, yag, qr.pose[0], qr.pose[1], off_x, off_y, pt_of, [&](int i) { return gov_walk(l, i, np, yag); });
     YM_STAMP_B1(a, 23);
 }
 
@@ -680,11 +656,7 @@ __global__ __launch_bounds__(YM_POINTS_THREADS) void points_kernel(PrepareArgs a
     const YmScanRef sr = a.scans[job & 0x7fffffff];
     const bool yag = a.g.semantics == 1;
     const PrepLds l = prep_lds(lds_raw, a.max_n);
-    const double px = (is_query && yag) ? 0.0 : sr.pose[0];
-    const double py = (is_query && yag) ? 0.0 : sr.pose[1];
-    const double pt = (is_query && yag) ? 0.0 : sr.pose[2];
-    const int np = (sr.cidx && sr.n > 0) ? project_points_indexed<NT>(sr, px, py, pt, l, false)
-                                         : project_points<NT>(sr, px, py, pt, yag, l.sx, l.sy, s_cnt);
+    const int np = project_scan<NT>(sr, is_query, yag, l, s_cnt, false);
     if (is_query) { // into the scan's query slot of the point cache, else into the call's own buffer
         const int qs = a.job_slot[blockIdx.x];
         store_query_local<NT>(sr, l, np, yag, sr.qcache ? reinterpret_cast<double2 *>(sr.qcache + YM_CACHE_HEADER) : a.qlocal + (size_t)qs * a.max_n);
@@ -711,10 +683,9 @@ __global__ __launch_bounds__(256) void cells_kernel(PrepareArgs a) {
     const YmScanRef qr = a.scans[it.query];
     if (blockIdx.x == 0) {
         const int qs = it.pad; // query slot, set by the host
-        const double off_x = qr.pose[0] - (0.5 * (a.g.roi_w - 1) * a.g.res);
-        const double off_y = qr.pose[1] - (0.5 * (a.g.roi_w - 1) * a.g.res);
         const double2 *ql = qr.qcache ? reinterpret_cast<const double2 *>(qr.qcache + YM_CACHE_HEADER) : a.qlocal + (size_t)qs * a.max_n;
-        init_item<NT>(a, b, it, qr, qr.qcache ? *reinterpret_cast<const int *>(qr.qcache) : a.qnp[qs], qs, ql, off_x, off_y);
+        init_item<NT>(a, b, it, qr, qr.qcache ? *reinterpret_cast<const int *>(qr.qcache) : a.qnp[qs], qs, ql,
+                      roi_offset(a.g, qr.pose[0]), roi_offset(a.g, qr.pose[1]));
         return;
     }
     if (slot >= it.base_count) {
@@ -850,460 +821,6 @@ __global__ __launch_bounds__(YM_TILES_THREADS) void tiles_kernel(TilesArgs a) {
 #pragma unroll
     for (int k = 0; k < YM_TILES_KEEP; k++) scatter(k * NT + tid, mine[k]);
     for (int c = YM_TILES_KEEP * NT + tid; c < n_boxes; c += NT) scatter(c, bbox[c]);
-}
-
-// ================================================================== K1b select (only when the smear kernel has taps == 100 off-centre)
-// Karto's AddScan skips a point whose cell already holds 100 ("value already set").  With
-// smear_deviation >= 9.99 * resolution the four neighbours of an occupied cell are stamped 100 as
-// well, so whether a point is rasterised depends on the points before it: a point is EFFECTIVE iff
-// no earlier effective point lies within squared cell distance z2max (the radius of the kernel's
-// 100-valued disc), in Karto's order (base scans in order, beams in order).
-//
-// Parallel form of that greedy rule.  Only the earliest point of a cell can be effective (a later
-// one is knocked out by it, or by whatever knocked it out).  So: (1) hash every cell to its earliest
-// point index (LDS, atomicMin); (2) relax the undecided cells: a cell whose earlier neighbours are
-// all decided "no" becomes effective, a cell with an effective earlier neighbour is out -- decisions
-// are final, so reading a neighbour's fresh or stale state is equally safe, and the globally
-// earliest undecided cell always resolves, so the loop ends; (3) erase every point
-// that is not the earliest of an effective cell from `cells`.  One block per item.
-struct SelectArgs {
-    YmCell *cells;        // [B][max_base][max_n]
-    int32_t max_n, max_base;
-    int32_t z2max;        // largest squared distance whose kernel value is 100
-    int32_t log2cap;      // hash capacity = 1 << log2cap entries (dynamic LDS: 9 bytes per entry)
-    unsigned long long *stamps;
-};
-
-__device__ __forceinline__ unsigned select_key(int x, int y) {
-    return ((unsigned)(y + 32768) << 16) | ((unsigned)(x + 32768) & 0xffffu);
-}
-// The table is open addressing over BUCKETS of four keys (one 16-byte LDS read per probe; a plain
-// linear-probing table made the slowest lane of a wave walk 20-40 slots).  Keys fill a bucket front
-// to back and are never removed, so an empty last slot means "not in this bucket or any later one".
-// slot of `key`, or -1.  bmask = buckets - 1, shift = 32 - log2(buckets).
-__device__ __forceinline__ int select_find(const unsigned *keys, unsigned bmask, int shift, unsigned key) {
-    unsigned bk = (key * 2654435761u) >> shift;
-    for (;;) {
-        const uint4 q = *reinterpret_cast<const uint4 *>(keys + 4 * bk);
-        if (q.x == key) return (int)(4 * bk);
-        if (q.y == key) return (int)(4 * bk + 1);
-        if (q.z == key) return (int)(4 * bk + 2);
-        if (q.w == key) return (int)(4 * bk + 3);
-        if (q.w == 0u) return -1;
-        bk = (bk + 1u) & bmask;
-    }
-}
-// the same search, continued at bucket bk
-__device__ __forceinline__ int select_find_from(const unsigned *keys, unsigned bmask, unsigned bk, unsigned key) {
-    for (;;) {
-        const uint4 q = *reinterpret_cast<const uint4 *>(keys + 4 * bk);
-        if (q.x == key) return (int)(4 * bk);
-        if (q.y == key) return (int)(4 * bk + 1);
-        if (q.z == key) return (int)(4 * bk + 2);
-        if (q.w == key) return (int)(4 * bk + 3);
-        if (q.w == 0u) return -1;
-        bk = (bk + 1u) & bmask;
-    }
-}
-// slot of `key`, inserting it if absent
-__device__ __forceinline__ int select_insert(unsigned *keys, unsigned bmask, int shift, unsigned key) {
-    unsigned bk = (key * 2654435761u) >> shift;
-    for (;;) {
-        const uint4 q = *reinterpret_cast<const uint4 *>(keys + 4 * bk);
-        int j = (q.x == key || q.x == 0u) ? 0 : (q.y == key || q.y == 0u) ? 1 : (q.z == key || q.z == 0u) ? 2 : (q.w == key || q.w == 0u) ? 3 : 4;
-        for (; j < 4; j++) {
-            const unsigned prev = atomicCAS(&keys[4 * bk + j], 0u, key);
-            if (prev == 0u || prev == key) return (int)(4 * bk + j);
-        }
-        bk = (bk + 1u) & bmask;
-    }
-}
-
-// NB = 5 for z2max = 1 (plus-shaped disc), 9 for z2max = 2
-template <int NB>
-__global__ __launch_bounds__(1024) void select_kernel(SelectArgs a) {
-    constexpr int NT = 1024, NW = (NB - 1) / 4;
-    constexpr int PMAX = 12; // points per thread: the host sends at most 12 288 readings here (3 * capacity >= 4 * readings, capacity <= 2^14)
-    constexpr int DX[9] = {0, 1, -1, 0, 0, 1, 1, -1, -1};
-    constexpr int DY[9] = {0, 0, 0, 1, -1, 1, -1, 1, -1};
-    extern __shared__ unsigned sel_lds[];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const unsigned cap = 1u << a.log2cap, bmask = (cap >> 2) - 1u;
-    const int shift = 32 - (a.log2cap - 2);
-    unsigned *keys = sel_lds;
-    unsigned *minidx = sel_lds + cap;
-    unsigned char *status = reinterpret_cast<unsigned char *>(sel_lds + 2 * cap); // 0 undecided, 1 effective, 2 out
-    YM_STAMP(a, 24);
-    // The thread's points: all loaded at once and kept for step (3), with the slots step (1) finds for them.  (The one block
-    // of an item is a latency chain: a load per loop trip -- which the stores of step (3) into the same array keep the
-    // compiler from moving -- cost steps (1) and (3) a memory round trip per point, 14 + 58 of the kernel's 118 us.)
-    YmCell *cells = a.cells + (size_t)b * a.max_base * a.max_n;
-    const int total = a.max_base * a.max_n;
-    int2 mine[PMAX];
-    unsigned short slot_of[PMAX];
-    // A thread takes `per` CONSECUTIVE points and, in steps (2a) / (2b), decides the cells whose earliest point is one of
-    // them, in that order: the earlier neighbours of a cell are mostly the cells of the beams just before it, so a wall's
-    // chain of dependent decisions resolves inside one thread in one sweep instead of hopping from thread to thread once
-    // per sweep (the relaxation took 53 of the kernel's 111 us while a thread owned hash SLOTS).
-    const int per = (total + NT - 1) / NT, e0 = tid * per;
-#pragma unroll
-    for (int q = 0; q < PMAX; q++) {
-        const int e = e0 + q;
-        mine[q] = (q < per && e < total) ? ym_cell_unpack(cells[e]) : make_int2(YM_CELL_NONE, YM_CELL_NONE);
-    }
-    for (unsigned i = tid; i < cap; i += NT) { keys[i] = 0u; minidx[i] = 0xffffffffu; status[i] = 0; }
-    __syncthreads();
-    YM_STAMP(a, 25);
-    // (1) cell -> earliest point index
-#pragma unroll
-    for (int q = 0; q < PMAX; q++) {
-        slot_of[q] = 0;
-        if (mine[q].x == YM_CELL_NONE) continue;
-        const int slot = select_insert(keys, bmask, shift, select_key(mine[q].x, mine[q].y));
-        slot_of[q] = (unsigned short)slot;
-        atomicMin(&minidx[slot], (unsigned)(e0 + q));
-    }
-    __syncthreads();
-    YM_STAMP(a, 26);
-    // (2a) per owned cell (= owned point that is the earliest of its cell): the slots of the neighbour cells that hold an
-    // EARLIER point, packed as 16-bit slot numbers (0xffff = none).  A cell with no earlier neighbour is effective.
-    unsigned long long nb[PMAX][NW];
-    unsigned und = 0;
-#pragma unroll
-    for (int k = 0; k < PMAX; k++) {
-#pragma unroll
-        for (int w = 0; w < NW; w++) nb[k][w] = ~0ull;
-        if (mine[k].x == YM_CELL_NONE) continue;
-        const unsigned s = slot_of[k], me = (unsigned)(e0 + k);
-        if (minidx[s] != me) continue; // a later point of its cell: never effective, nothing to decide
-        const int x = mine[k].x, y = mine[k].y;
-        bool any = false;
-        // the first probe of every neighbour is issued before any is looked at (the probes are latency, not bandwidth)
-        unsigned nkey[NB], nbk[NB];
-        uint4 nq[NB];
-#pragma unroll
-        for (int n = 1; n < NB; n++) {
-            nkey[n] = select_key(x + DX[n], y + DY[n]);
-            nbk[n] = (nkey[n] * 2654435761u) >> shift;
-            nq[n] = *reinterpret_cast<const uint4 *>(keys + 4 * nbk[n]);
-        }
-#pragma unroll
-        for (int n = 1; n < NB; n++) {
-            const uint4 q4 = nq[n];
-            const unsigned key = nkey[n];
-            int t = q4.x == key ? (int)(4 * nbk[n]) : q4.y == key ? (int)(4 * nbk[n] + 1) : q4.z == key ? (int)(4 * nbk[n] + 2)
-                    : q4.w == key ? (int)(4 * nbk[n] + 3) : q4.w == 0u ? -1 : -2;
-            if (t == -2) t = select_find_from(keys, bmask, (nbk[n] + 1u) & bmask, key); // (a full bucket without the key: go on)
-            if (t >= 0 && minidx[t] < me) {
-                any = true;
-                const int j = n - 1;
-                nb[k][j >> 2] &= ~(0xffffull << (16 * (j & 3)));
-                nb[k][j >> 2] |= (unsigned long long)(unsigned)t << (16 * (j & 3));
-            }
-        }
-        if (any) und |= 1u << k;
-        else status[s] = 1;
-    }
-    YM_STAMP(a, 3);
-    // (2b) asynchronous relaxation, no barriers: every wave keeps re-reading the state of the earlier
-    // neighbours of its undecided cells.  A decision is final and is taken only from final states
-    // (a stale "undecided" read merely delays it), and all 16 waves of the block are resident, so
-    // this terminates with the sequential greedy result whatever the interleaving.
-    unsigned char *vst = status;
-    unsigned wmask = 0;
-#pragma unroll
-    for (int k = 0; k < PMAX; k++) wmask |= __ballot((und >> k) & 1u) ? (1u << k) : 0u;
-    while (wmask) {
-        unsigned m = wmask;
-        while (m) {
-            const int k = __builtin_ctz(m); // wave-uniform
-            m &= m - 1;
-            bool still = false;
-            asm volatile("" ::: "memory"); // re-read the states every time
-            if ((und >> k) & 1u) {
-                bool knocked = false, pending = false;
-#pragma unroll
-                for (int j = 0; j < NB - 1; j++) {
-                    const unsigned t = (unsigned)(nb[k][j >> 2] >> (16 * (j & 3))) & 0xffffu;
-                    if (t != 0xffffu) {
-                        const unsigned char stt = vst[t];
-                        knocked |= stt == 1;
-                        pending |= stt == 0;
-                    }
-                }
-                const unsigned s = slot_of[k];
-                if (knocked) vst[s] = 2;
-                else if (!pending) vst[s] = 1;
-                else still = true;
-                if (!still) und &= ~(1u << k);
-            }
-            if (__ballot(still) == 0ull) wmask &= ~(1u << k);
-        }
-    }
-    __syncthreads();
-    YM_STAMP(a, 30);
-    // (3) keep only the earliest point of every effective cell
-#pragma unroll
-    for (int q = 0; q < PMAX; q++) {
-        if (mine[q].x == YM_CELL_NONE) continue;
-        const int e = e0 + q, t = slot_of[q];
-        if (!(status[t] == 1 && minidx[t] == (unsigned)e)) cells[e] = ym_cell_none();
-    }
-    YM_STAMP(a, 31);
-}
-
-// ---- the same rule on a FEW items (z2max = 1), split by what is parallel and what is not (round 4).  Steps (1) and (2a) of
-// select_kernel are parallel work that one block does alone: 45 of its 79 us are 16 waves issuing ~4000 instructions each on
-// one CU.  Here they are two launches over all points (hash and earliest-point table in global memory, left zeroed for the
-// next call), and the one block per item that remains only runs the chain of dependent decisions (2b) and the erase (3) from
-// a 16-byte record per point (SelectSplitArgs::rec): rec.x = slot | owned << 16 | effective << 17 (0xffffffff: no point), rec.y / rec.z = the slots of
-// the neighbour cells with an earlier point, 16 bits each (0xffff: none).
-struct SelectSplitArgs {
-    YmCell *cells;        // [B][max_base][max_n]
-    int32_t max_n, max_base;
-    int32_t log2cap, pad;
-    unsigned *keys;       // [B][cap]  zero between calls
-    unsigned *mx;         // [B][cap]  zero between calls: max over the cell's points of ~index (= its earliest point)
-    unsigned *slot_of;    // [B][max_base * max_n]  the point's slot (0xffffffff: no cell)
-    uint4 *rec;           // [B][12 * 1024]  the record of point e = t * per + q at [q * 1024 + t]: thread t of select_relax_kernel reads its
-                          //                 `per` = ceil(points / 1024) consecutive points with coalesced loads
-    unsigned long long *stamps;
-};
-#define YM_SELECT_SPLIT_THREADS 256
-// (1) grid (ceil(total / 256), B)
-__global__ __launch_bounds__(YM_SELECT_SPLIT_THREADS) void select_hash_kernel(SelectSplitArgs a) {
-    const int b = blockIdx.y, e = blockIdx.x * YM_SELECT_SPLIT_THREADS + threadIdx.x;
-    const int total = a.max_base * a.max_n;
-    if (e >= total) return;
-    const unsigned cap = 1u << a.log2cap, bmask = (cap >> 2) - 1u;
-    const int shift = 32 - (a.log2cap - 2);
-    const int2 c = ym_cell_unpack(a.cells[(size_t)b * total + e]);
-    unsigned slot = 0xffffffffu;
-    if (c.x != YM_CELL_NONE) {
-        slot = (unsigned)select_insert(a.keys + (size_t)b * cap, bmask, shift, select_key(c.x, c.y));
-        atomicMax(&a.mx[(size_t)b * cap + slot], ~(unsigned)e);
-    }
-    a.slot_of[(size_t)b * total + e] = slot;
-}
-// (2a) grid (ceil(total / 256), B)
-__global__ __launch_bounds__(YM_SELECT_SPLIT_THREADS) void select_neighbours_kernel(SelectSplitArgs a) {
-    constexpr int DX[5] = {0, 1, -1, 0, 0};
-    constexpr int DY[5] = {0, 0, 0, 1, -1};
-    const int b = blockIdx.y, e = blockIdx.x * YM_SELECT_SPLIT_THREADS + threadIdx.x;
-    const int total = a.max_base * a.max_n;
-    if (e >= total) return;
-    const unsigned cap = 1u << a.log2cap, bmask = (cap >> 2) - 1u;
-    const int shift = 32 - (a.log2cap - 2);
-    const unsigned *keys = a.keys + (size_t)b * cap, *mx = a.mx + (size_t)b * cap;
-    const int per = (total + 1023) / 1024;
-    uint4 *rec = a.rec + (size_t)b * 12 * 1024 + (size_t)(e % per) * 1024 + e / per;
-    const unsigned s = a.slot_of[(size_t)b * total + e];
-    const int2 c = ym_cell_unpack(a.cells[(size_t)b * total + e]); // (a point without a cell: YM_CELL_NONE, any bucket)
-    // the first probe of every neighbour leaves before the point's own entry is looked at: one round trip, not two
-    unsigned nkey[5], nbk[5];
-    uint4 nq[5];
-#pragma unroll
-    for (int n = 1; n < 5; n++) {
-        nkey[n] = select_key(c.x + DX[n], c.y + DY[n]);
-        nbk[n] = (nkey[n] * 2654435761u) >> shift;
-        nq[n] = *reinterpret_cast<const uint4 *>(keys + 4 * nbk[n]);
-    }
-    if (s == 0xffffffffu) {
-        *rec = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0u);
-        return;
-    }
-    const unsigned mine = ~(unsigned)e;
-    if (mx[s] != mine) { // a later point of its cell: never effective, nothing to decide
-        *rec = make_uint4(s, 0xffffffffu, 0xffffffffu, 0u);
-        return;
-    }
-    int tn[5];
-#pragma unroll
-    for (int n = 1; n < 5; n++) {
-        const uint4 q4 = nq[n];
-        const unsigned key = nkey[n];
-        int t = q4.x == key ? (int)(4 * nbk[n]) : q4.y == key ? (int)(4 * nbk[n] + 1) : q4.z == key ? (int)(4 * nbk[n] + 2)
-                : q4.w == key ? (int)(4 * nbk[n] + 3) : q4.w == 0u ? -1 : -2;
-        if (t == -2) t = select_find_from(keys, bmask, (nbk[n] + 1u) & bmask, key); // (a full bucket without the key: go on)
-        tn[n] = t;
-    }
-    unsigned mt[5];
-#pragma unroll
-    for (int n = 1; n < 5; n++) mt[n] = mx[tn[n] >= 0 ? tn[n] : (int)s]; // (the four entries together)
-    unsigned nbv[4];
-    bool any = false;
-#pragma unroll
-    for (int n = 1; n < 5; n++) {
-        const bool earlier = tn[n] >= 0 && mt[n] > mine; // (~index larger = index smaller)
-        nbv[n - 1] = earlier ? (unsigned)tn[n] : 0xffffu;
-        any |= earlier;
-    }
-    *rec = make_uint4(s | 1u << 16 | (any ? 0u : 1u << 17), nbv[0] | nbv[1] << 16, nbv[2] | nbv[3] << 16, 0u);
-}
-// (2b) + (3): grid (B), 1024 threads, dynamic LDS = one state byte per slot
-__global__ __launch_bounds__(1024) void select_relax_kernel(SelectSplitArgs a) {
-    constexpr int NT = 1024, PMAX = 12;
-    extern __shared__ unsigned sel_lds[];
-    unsigned char *status = reinterpret_cast<unsigned char *>(sel_lds); // 0 undecided, 1 effective, 2 out
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const unsigned cap = 1u << a.log2cap;
-    const int total = a.max_base * a.max_n;
-    YmCell *cells = a.cells + (size_t)b * total;
-    const uint4 *rec = a.rec + (size_t)b * 12 * 1024;
-    // a thread takes `per` CONSECUTIVE points (see select_kernel: a wall's chain of decisions resolves inside one thread)
-    const int per = (total + NT - 1) / NT, e0 = tid * per;
-    YM_STAMP(a, 24);
-    uint4 r[PMAX];
-#pragma unroll
-    for (int q = 0; q < PMAX; q++) {
-        const int e = e0 + q;
-        r[q] = (q < per && e < total) ? rec[q * NT + tid] : make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0u);
-    }
-    for (unsigned i = tid; i < cap / 4; i += NT) sel_lds[i] = 0u;
-    __syncthreads();
-    unsigned und = 0;
-#pragma unroll
-    for (int q = 0; q < PMAX; q++) {
-        if (r[q].x == 0xffffffffu || !(r[q].x & (1u << 16))) continue;
-        if (r[q].x & (1u << 17)) status[r[q].x & 0xffffu] = 1;
-        else und |= 1u << q;
-    }
-    YM_STAMP(a, 3);
-    // asynchronous relaxation, no barriers (select_kernel, step (2b))
-    unsigned char *vst = status;
-    unsigned wmask = 0;
-#pragma unroll
-    for (int k = 0; k < PMAX; k++) wmask |= __ballot((und >> k) & 1u) ? (1u << k) : 0u;
-    while (wmask) {
-#pragma unroll
-        for (int k = 0; k < PMAX; k++) { // (unrolled: r[k] stays in registers; a point without undecided lanes costs a scalar test)
-            if (!((wmask >> k) & 1u)) continue;
-            bool still = false;
-            asm volatile("" ::: "memory"); // re-read the states every time
-            if ((und >> k) & 1u) {
-                bool knocked = false, pending = false;
-                const unsigned nbs[4] = {r[k].y & 0xffffu, r[k].y >> 16, r[k].z & 0xffffu, r[k].z >> 16};
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    if (nbs[j] != 0xffffu) {
-                        const unsigned char stt = vst[nbs[j]];
-                        knocked |= stt == 1;
-                        pending |= stt == 0;
-                    }
-                }
-                const unsigned s = r[k].x & 0xffffu;
-                if (knocked) vst[s] = 2;
-                else if (!pending) vst[s] = 1;
-                else still = true;
-                if (!still) und &= ~(1u << k);
-            }
-            if (__ballot(still) == 0ull) wmask &= ~(1u << k);
-        }
-    }
-    __syncthreads();
-    YM_STAMP(a, 30);
-    // (3) keep only the earliest point of every effective cell
-#pragma unroll
-    for (int q = 0; q < PMAX; q++) {
-        if (r[q].x == 0xffffffffu) continue;
-        if (!((r[q].x & (1u << 16)) && status[r[q].x & 0xffffu] == 1)) cells[e0 + q] = ym_cell_none();
-    }
-    // the tables as the next call expects them
-    uint4 *k4 = reinterpret_cast<uint4 *>(a.keys + (size_t)b * cap), *m4 = reinterpret_cast<uint4 *>(a.mx + (size_t)b * cap);
-    for (unsigned i = tid; i < cap / 4; i += NT) { k4[i] = make_uint4(0u, 0u, 0u, 0u); m4[i] = make_uint4(0u, 0u, 0u, 0u); }
-    YM_STAMP(a, 31);
-}
-
-// ---- the same rule for chains too long for one CU's LDS (more than 12 288 readings): hash, earliest-point index, neighbour
-// lists and states live in global memory (one 1024-thread block per item again -- the relaxation is a chain of
-// dependent decisions, not a parallel job -- but its reads now cost an L2 round trip instead of an LDS one).  LDS only
-// holds each thread's shrinking list of undecided slots.  Capacity 2^17 slots = 98 304 readings at load factor 0.75.
-struct SelectGlobalArgs {
-    YmCell *cells;        // [B][max_base][max_n]
-    int32_t max_n, max_base;
-    int32_t z2max, log2cap;
-    unsigned *keys;       // [B][cap]           zeroed by the host
-    unsigned *status;     // [B][cap]           zeroed by the host: 0 undecided, 1 effective, 2 out
-    unsigned *minidx;     // [B][cap]           set to 0xffffffff by the host
-    unsigned *nbr;        // [B][NB - 1][cap]   slot of the neighbour cell if it holds an earlier point, else 0xffffffff
-};
-
-template <int NB>
-__global__ __launch_bounds__(1024) void select_global_kernel(SelectGlobalArgs a) {
-    constexpr int NT = 1024;
-    constexpr int DX[9] = {0, 1, -1, 0, 0, 1, 1, -1, -1};
-    constexpr int DY[9] = {0, 0, 0, 1, -1, 1, -1, 1, -1};
-    extern __shared__ unsigned char und_list[]; // [cap / NT][NT]: ordinals k of the slots tid + k * NT still undecided
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const unsigned cap = 1u << a.log2cap, bmask = (cap >> 2) - 1u;
-    const int shift = 32 - (a.log2cap - 2);
-    unsigned *keys = a.keys + (size_t)b * cap, *minidx = a.minidx + (size_t)b * cap, *status = a.status + (size_t)b * cap;
-    unsigned *nbr = a.nbr + (size_t)b * (NB - 1) * cap;
-    YmCell *cells = a.cells + (size_t)b * a.max_base * a.max_n;
-    const int total = a.max_base * a.max_n;
-    // (1) cell -> earliest point index
-    for (int e = tid; e < total; e += NT) {
-        const int2 c = ym_cell_unpack(cells[e]);
-        if (c.x == YM_CELL_NONE) continue;
-        const int slot = select_insert(keys, bmask, shift, select_key(c.x, c.y));
-        atomicMin(&minidx[slot], (unsigned)e);
-    }
-    // the tables were built by atomics in L2: make them visible to this CU's plain loads (its L1 may hold lines fetched
-    // while they were still being filled)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    // (2a) earlier neighbours of every cell; a cell without one is effective
-    int n_und = 0;
-    for (unsigned s = tid, k = 0; s < cap; s += NT, k++) {
-        const unsigned key = keys[s];
-        if (key == 0u) continue;
-        const unsigned me = minidx[s];
-        const int x = (int)(key & 0xffffu) - 32768, y = (int)(key >> 16) - 32768;
-        bool any = false;
-#pragma unroll
-        for (int n = 1; n < NB; n++) {
-            const int t = select_find(keys, bmask, shift, select_key(x + DX[n], y + DY[n]));
-            const bool earlier = t >= 0 && minidx[t] < me;
-            nbr[(size_t)(n - 1) * cap + s] = earlier ? (unsigned)t : 0xffffffffu;
-            any |= earlier;
-        }
-        if (any) und_list[(size_t)(n_und++) * NT + tid] = (unsigned char)k;
-        else __hip_atomic_store(&status[s], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // (2b) asynchronous relaxation (see select_kernel): decisions are final and only taken from final states, so stale
-    // reads merely delay; every wave of the block is resident, so the earliest undecided cell always gets decided
-    while (__ballot(n_und > 0)) {
-        int kept = 0;
-        for (int i = 0; i < n_und; i++) {
-            const unsigned k = und_list[(size_t)i * NT + tid], s = tid + k * NT;
-            bool knocked = false, pending = false;
-#pragma unroll
-            for (int j = 0; j < NB - 1; j++) {
-                const unsigned t = nbr[(size_t)j * cap + s];
-                if (t != 0xffffffffu) {
-                    const unsigned stt = __hip_atomic_load(&status[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    knocked |= stt == 1u;
-                    pending |= stt == 0u;
-                }
-            }
-            if (knocked) __hip_atomic_store(&status[s], 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else if (!pending) __hip_atomic_store(&status[s], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else und_list[(size_t)(kept++) * NT + tid] = (unsigned char)k;
-        }
-        n_und = kept;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    // (3) keep only the earliest point of every effective cell
-    for (int e = tid; e < total; e += NT) {
-        const int2 c = ym_cell_unpack(cells[e]);
-        if (c.x == YM_CELL_NONE) continue;
-        const int t = select_find(keys, bmask, shift, select_key(c.x, c.y));
-        if (!(t >= 0 && __hip_atomic_load(&status[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1u && minidx[t] == (unsigned)e))
-            cells[e] = ym_cell_none();
-    }
 }
 
 }  // namespace ym

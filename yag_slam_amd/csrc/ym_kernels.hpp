@@ -22,6 +22,7 @@
 // the kernels, one header per stage
 #include "ym_k_common.hpp"
 #include "ym_k_prepare.hpp"
+#include "ym_k_select.hpp"
 #include "ym_k_raster.hpp"
 #include "ym_k_correlate.hpp"
 #include "ym_k_finish.hpp"
