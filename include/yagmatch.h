@@ -709,9 +709,29 @@ int ym_segments_labels(ym_segments *sg, int32_t *labels, int64_t n);
  *                                  exact != 0 (use_csparse): relative residual 1e-10, at most min(9 N, 20000) iterations,
  *                                  cg_tol and max_cg_iters ignored; else those two.  A solve that reaches its cap still
  *                                  yields a step, which is kept or not by the same rule.
+ *   ym_graph_hold / _held          (no SPA2d call: the held set.)  Every node is held or free; node 0 is always held and cannot
+ *                                  be released; a node is free when added.  ym_graph_hold holds (hold = 1) or releases (0) the
+ *                                  n nodes given; a node that is in that state already stays so.  ym_graph_held writes 1 per
+ *                                  held node into mask[n_nodes], n_nodes the graph's node count.  The set may change between
+ *                                  calls; the next launch sees the new set.
+ * The held set.  One step solves (H + lambda diag H) delta = -g over the FREE nodes; H, g and diag H are summed over all
+ * constraints.  A constraint between a free and a held node adds its own diagonal block and gradient to the free node and
+ * nothing else; one between two held nodes adds only its chi2 term, a constant that ym_graph_chi2, the report and the stop
+ * rules count.  delta of a held node is exactly 0 and its pose after ym_graph_optimize is bit for bit the pose before (theta
+ * is not wrapped); ym_graph_set_poses may still move it.  Solve order: slot 0 stands for the held nodes (identity row,
+ * right-hand side zero), the free nodes take the slots 1 .. F in index order; with only node 0 held slot(i) = i.  The band
+ * lives in slots: the block (a, b) is in the band iff both nodes are free and |slot(a) - slot(b)| <= band; band -1 picks the
+ * largest |slot(a) - slot(b)| <= 16 among the constraints whose ends are free or node 0, 0 if there is none, and
+ * ym_opt_report.band and band_used report it.  (A constraint at node 0 has no block in the band; it counts because it always
+ * did, so that a graph with nothing else held picks the band it picked before.  One at any other held node does not count.)  The iteration cap of exact solves stays min(9 N, 20000), N the node count.  No free node, or no
+ * constraint with a free end: ym_graph_optimize succeeds with zero steps (chi2_initial = chi2_final = the constant) and
+ * ym_graph_solve returns zeros.  A free component without a held node behaves as a component not connected to node 0: the
+ * damping keeps it definite.  ym_graph_linearise returns diag and grad of every node, held ones included; ym_graph_solve
+ * returns [N][3] arrays whose rows of held nodes are zero.  The held set is not part of a map file: re-hold after loading.
  * Errors (ym_last_error): a node index out of range, a constraint from a node to itself, a value that is not finite, an
- * information matrix without a positive diagonal.  Fewer than two nodes or no constraint: ym_graph_optimize succeeds with
- * zero steps.  The adds and ym_graph_size / _get_poses / _set_poses touch no device.  Synchronous, on the handle's stream. */
+ * information matrix without a positive diagonal, a release of node 0 (ym_graph_hold applies nothing of a call it refuses).
+ * Fewer than two nodes or no constraint: ym_graph_optimize succeeds with zero steps.  The adds, ym_graph_hold / _held and
+ * ym_graph_size / _get_poses / _set_poses touch no device.  Synchronous, on the handle's stream. */
 typedef struct ym_graph ym_graph;
 ym_graph *ym_graph_create(int device);
 void ym_graph_destroy(ym_graph *g);
@@ -720,6 +740,8 @@ int ym_graph_add_constraints(ym_graph *g, const int32_t *from_to, const double *
 int ym_graph_size(const ym_graph *g, int32_t *nodes, int32_t *constraints);
 int ym_graph_set_poses(ym_graph *g, int first, const double *xyt, int n);
 int ym_graph_get_poses(const ym_graph *g, int first, double *xyt, int n);
+int ym_graph_hold(ym_graph *g, const int32_t *nodes, int n, int hold /* 1: hold, 0: release */);
+int ym_graph_held(const ym_graph *g, uint8_t *mask, int n_nodes); /* 1 per held node */
 int ym_graph_chi2(ym_graph *g, double *chi2);
 int ym_graph_linearise(ym_graph *g, double *chi2, double *diag9 /* [N][9] */, double *grad3 /* [N][3] */);
 int ym_graph_solve(ym_graph *g, int band /* -1 auto, 0 .. 16 */, double lambda, double cg_tol, int max_cg_iters /* >= 0 */,

@@ -39,6 +39,7 @@ EXPORTS = (
     "ym_segments_destroy", "ym_map_free_space", "ym_segments_from_map", "ym_segments_labels",
     "ym_graph_create", "ym_graph_destroy", "ym_graph_add_nodes", "ym_graph_add_constraints", "ym_graph_size", "ym_graph_set_poses",
     "ym_graph_get_poses", "ym_graph_chi2", "ym_graph_linearise", "ym_graph_solve", "ym_graph_optimize",
+    "ym_graph_hold", "ym_graph_held",
 )
 
 
@@ -377,6 +378,8 @@ def lib():
     L.ym_graph_size.argtypes = [vp, ip, ip]
     L.ym_graph_set_poses.argtypes = [vp, C.c_int, dp, C.c_int]
     L.ym_graph_get_poses.argtypes = [vp, C.c_int, dp, C.c_int]
+    L.ym_graph_hold.argtypes = [vp, ip, C.c_int, C.c_int]
+    L.ym_graph_held.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int]
     L.ym_graph_chi2.argtypes = [vp, dp]
     L.ym_graph_linearise.argtypes = [vp, dp, dp, dp]
     L.ym_graph_solve.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, dp, dp, ip, ip, dp, ip]

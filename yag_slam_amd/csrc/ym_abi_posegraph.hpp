@@ -2,15 +2,21 @@
 // Part of yagmatch.hip (included inside its extern "C" block); not a header of its own.
 // The host keeps every node and constraint (poses are copied back after an optimisation), so the device arrays are plain
 // mirrors: whatever changed since the last launch is uploaded whole before the next one.
+// Every node is held or free (held[i]; node 0 always held).  The solve order -- slot[N], 0 for a held node and 1 .. F for the
+// free ones in index order, and node_of_slot[F + 1] -- is rebuilt on the host whenever the set or the node count changed.
 struct ym_graph {
     int device;
     OwnStream stream;
     std::vector<double> pose, mean, info;
     std::vector<int32_t> from_to;
+    std::vector<uint8_t> held;                   // [N]: 1 for a held node
+    std::vector<int32_t> slot, node_of_slot;     // the solve order (valid unless slots_stale)
+    bool free_edge = false;                      // some edge has a free end (valid unless slots_stale)
+    bool slots_stale = true, slots_unsent = true; // the solve order is behind `held` / the device's copy behind the host's
     bool poses_stale = true, edges_stale = true; // the device mirrors are behind the host's vectors
     int cur = 0;                                 // which of d_pose[2] holds the poses (the other takes the trial step)
     DevBuf<double> d_pose[2], d_mean, d_info, e_blk, e_grad, e_chi, diag, grad, aband, uband, ubandT, vec, partial, record;
-    DevBuf<int32_t> d_from_to, node_ptr, inc;
+    DevBuf<int32_t> d_from_to, node_ptr, inc, d_slot, d_node_of_slot;
 };
 
 ym_graph *ym_graph_create(int device) {
@@ -40,7 +46,30 @@ int ym_graph_add_nodes(ym_graph *g, const double *xyt, int n) {
     if (!graph_finite(xyt, 3 * (size_t)n)) return set_err(YM_ERR_INVALID, "a pose that is not finite");
     if (g->pose.size() / 3 + (size_t)n > (size_t)(INT32_MAX / 64)) return set_err(YM_ERR_UNSUPPORTED, "too many nodes");
     g->pose.insert(g->pose.end(), xyt, xyt + 3 * (size_t)n);
-    if (n) g->poses_stale = g->edges_stale = true; // (the incidence lists are per node)
+    g->held.resize(g->pose.size() / 3, 0); // (free when added)
+    if (!g->held.empty()) g->held[0] = 1;
+    if (n) g->poses_stale = g->edges_stale = g->slots_stale = true; // (the incidence lists are per node)
+    return YM_OK;
+}
+
+int ym_graph_hold(ym_graph *g, const int32_t *nodes, int n, int hold) {
+    if (!g || n < 0 || (n > 0 && !nodes)) return set_err(YM_ERR_INVALID, "bad argument");
+    const int64_t N = (int64_t)g->held.size();
+    for (int i = 0; i < n; i++) { // (nothing is applied unless every index is good)
+        if (nodes[i] < 0 || nodes[i] >= N) return set_err(YM_ERR_INVALID, "hold: node %d out of range (%lld nodes)", nodes[i], (long long)N);
+        if (!hold && nodes[i] == 0) return set_err(YM_ERR_INVALID, "hold: node 0 is always held and cannot be released");
+    }
+    for (int i = 0; i < n; i++) {
+        const uint8_t v = hold ? 1 : 0;
+        if (g->held[(size_t)nodes[i]] != v) { g->held[(size_t)nodes[i]] = v; g->slots_stale = true; }
+    }
+    return YM_OK;
+}
+
+int ym_graph_held(const ym_graph *g, uint8_t *mask, int n_nodes) {
+    if (!g || n_nodes < 0 || (n_nodes > 0 && !mask)) return set_err(YM_ERR_INVALID, "bad argument");
+    if ((size_t)n_nodes != g->held.size()) return set_err(YM_ERR_INVALID, "held: a mask of %d, the graph has %lld nodes", n_nodes, (long long)g->held.size());
+    std::copy(g->held.begin(), g->held.end(), mask);
     return YM_OK;
 }
 
@@ -67,7 +96,7 @@ int ym_graph_add_constraints(ym_graph *g, const int32_t *from_to, const double *
         for (int r = 0; r < 3; r++)
             for (int c = 0; c < 3; c++) g->info.push_back((L[3 * r + c] + L[3 * c + r]) / 2.0);
     }
-    if (n) g->edges_stale = true;
+    if (n) g->edges_stale = g->slots_stale = true; // (free_edge is per edge)
     return YM_OK;
 }
 
@@ -101,10 +130,36 @@ int ym_graph_get_poses(const ym_graph *g, int first, double *xyt, int n) {
     return YM_OK;
 }
 
-// the device mirrors, the incidence lists and the work arrays of a system of band W; `a` is filled in for the launches
+// the solve order of the held set as it stands, on the host (no device)
+static void graph_slots(ym_graph *g) {
+    if (!g->slots_stale) return;
+    const size_t N = g->held.size();
+    g->slot.assign(N, 0);
+    g->node_of_slot.assign(1, 0);
+    for (size_t i = 0; i < N; i++)
+        if (!g->held[i]) {
+            g->slot[i] = (int32_t)g->node_of_slot.size();
+            g->node_of_slot.push_back((int32_t)i);
+        }
+    g->free_edge = false;
+    for (size_t e = 0; e < g->from_to.size() && !g->free_edge; e++) g->free_edge = g->slot[(size_t)g->from_to[e]] != 0;
+    g->slots_stale = false;
+    g->slots_unsent = true;
+}
+
+// the device mirrors, the incidence lists, the solve order and the work arrays of a system of band W; `a` is filled in for
+// the launches
 static int graph_sync(ym_graph *g, int W, ym::PgArgs *a) {
     const size_t N = g->pose.size() / 3, M = g->from_to.size() / 2, rowlen = 9 * ((size_t)W + 1);
     int rc;
+    graph_slots(g);
+    const size_t S = g->node_of_slot.size();
+    if (g->slots_unsent) {
+        if ((rc = g->d_slot.ensure(N)) || (rc = g->d_node_of_slot.ensure(S))) return rc;
+        HIP_TRY(hipMemcpy(g->d_slot.p, g->slot.data(), N * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(g->d_node_of_slot.p, g->node_of_slot.data(), S * sizeof(int32_t), hipMemcpyHostToDevice));
+        g->slots_unsent = false;
+    }
     if ((rc = g->d_pose[0].ensure(3 * N)) || (rc = g->d_pose[1].ensure(3 * N))) return rc;
     if (g->poses_stale) {
         HIP_TRY(hipMemcpy(g->d_pose[g->cur].p, g->pose.data(), 3 * N * sizeof(double), hipMemcpyHostToDevice));
@@ -128,12 +183,13 @@ static int graph_sync(ym_graph *g, int W, ym::PgArgs *a) {
         g->edges_stale = false;
     }
     if ((rc = g->e_blk.ensure(27 * M)) || (rc = g->e_grad.ensure(6 * M)) || (rc = g->e_chi.ensure(M)) || (rc = g->diag.ensure(9 * N)) ||
-        (rc = g->grad.ensure(3 * N)) || (rc = g->aband.ensure(N * rowlen)) || (rc = g->uband.ensure(N * rowlen)) ||
-        (rc = g->ubandT.ensure(N * rowlen)) || (rc = g->vec.ensure(15 * N)) || (rc = g->partial.ensure((M + 255) / 256)) ||
+        (rc = g->grad.ensure(3 * N)) || (rc = g->aband.ensure(S * rowlen)) || (rc = g->uband.ensure(S * rowlen)) ||
+        (rc = g->ubandT.ensure(S * rowlen)) || (rc = g->vec.ensure(15 * S)) || (rc = g->partial.ensure((M + 255) / 256)) ||
         (rc = g->record.ensure(ym::kPgRecWords)))
         return rc;
     *a = ym::PgArgs{};
     a->n_nodes = (int32_t)N; a->n_edges = (int32_t)M; a->band = W;
+    a->n_slots = (int32_t)S; a->slot = g->d_slot.p; a->node_of_slot = g->d_node_of_slot.p;
     a->pose = g->d_pose[g->cur].p; a->trial = g->d_pose[g->cur ^ 1].p;
     a->from_to = g->d_from_to.p; a->mean = g->d_mean.p; a->info = g->d_info.p; a->node_ptr = g->node_ptr.p; a->inc = g->inc.p;
     a->e_blk = g->e_blk.p; a->e_grad = g->e_grad.p; a->e_chi = g->e_chi.p; a->diag = g->diag.p; a->grad = g->grad.p;
@@ -194,17 +250,20 @@ int ym_graph_linearise(ym_graph *g, double *chi2, double *diag9, double *grad3) 
 
 // the argument checks a solve shares (iters: of the Levenberg-Marquardt loop; cg: whether the tolerance and the cap count, the
 // cap at least min_cg) and the band it runs with
-static int graph_solve_args(const ym_graph *g, int iters, double lambda, int band, bool cg, int max_cg_iters, int min_cg, double cg_tol, int *W_out) {
+static int graph_solve_args(ym_graph *g, int iters, double lambda, int band, bool cg, int max_cg_iters, int min_cg, double cg_tol, int *W_out) {
     if (iters < 0 || !(lambda > 0.0) || !std::isfinite(lambda)) return set_err(YM_ERR_INVALID, "iters >= 0 and lambda0 > 0 are required");
     if (band < -1 || band > ym::kPgMaxBand) return set_err(YM_ERR_INVALID, "band %d: -1 (automatic) or 0 .. %d", band, ym::kPgMaxBand);
     if (cg && (max_cg_iters < min_cg || !(cg_tol > 0.0) || !std::isfinite(cg_tol)))
         return set_err(YM_ERR_INVALID, "max_cg_iters >= %d and cg_tol > 0 are required", min_cg);
     int W = band;
-    if (W < 0) { // the largest |a - b| among the edges that are at most kPgMaxBand apart
+    if (W < 0) { // the largest |slot(a) - slot(b)| <= kPgMaxBand among the edges whose ends are free or node 0.  (An edge at
+        // node 0 has no block in the band; it counts because it always did: with nothing else held this is the largest |a - b|.)
         W = 0;
+        graph_slots(g);
         for (size_t e = 0; e < g->from_to.size() / 2; e++) {
-            const int d = std::abs(g->from_to[2 * e] - g->from_to[2 * e + 1]);
-            if (d <= ym::kPgMaxBand && d > W) W = d;
+            const int32_t na = g->from_to[2 * e], nb = g->from_to[2 * e + 1];
+            const int sa = g->slot[(size_t)na], sb = g->slot[(size_t)nb], d = std::abs(sa - sb);
+            if ((sa != 0 || na == 0) && (sb != 0 || nb == 0) && d <= ym::kPgMaxBand && d > W) W = d;
         }
     }
     *W_out = W;
@@ -224,24 +283,32 @@ int ym_graph_solve(ym_graph *g, int band, double lambda, double cg_tol, int max_
     *flags = 0;
     std::fill(delta3, delta3 + 3 * N, 0.0);
     if (precond3) std::fill(precond3, precond3 + 3 * N, 0.0);
-    if (N < 2 || M == 0) return YM_OK;
+    graph_slots(g);
+    if (N < 2 || M == 0 || !g->free_edge) return YM_OK; // (no free node has no edge with a free end either)
     DEV_GUARD(g->device);
     ym::PgArgs a;
     if ((rc = graph_sync(g, W, &a)) != YM_OK) return rc;
+    const size_t S = (size_t)a.n_slots;
     a.lambda = lambda;
     a.cg_tol = cg_tol;
     a.cg_cap = max_cg_iters;
     double chi2 = 0.0;
     if ((rc = graph_linearise(g, a, &chi2)) != YM_OK) return rc;
-    HIP_TRY(hipMemsetAsync(a.vec, 0, 15 * N * sizeof(double), g->stream)); // (a right-hand side of zero leaves z unwritten)
+    HIP_TRY(hipMemsetAsync(a.vec, 0, 15 * S * sizeof(double), g->stream)); // (a right-hand side of zero leaves z unwritten)
     hipLaunchKernelGGL(ym::pg_assemble_kernel, dim3(graph_blocks(a.n_nodes)), dim3(256), 0, g->stream, a);
     hipLaunchKernelGGL(ym::pg_solve_kernel, dim3(1), dim3(ym::kPgSolveThreads), 0, g->stream, a);
     HIP_TRY(hipGetLastError());
     double rec[ym::kPgRecWords];
     HIP_TRY(hipMemcpyAsync(rec, a.record, sizeof rec, hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
-    HIP_TRY(hipMemcpy(delta3, a.vec, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
-    if (precond3) HIP_TRY(hipMemcpy(precond3, a.vec + 6 * N, 3 * N * sizeof(double), hipMemcpyDeviceToHost));
+    // x and z come back in solve order; the rows of the held nodes stay zero
+    std::vector<double> by_slot(9 * S);
+    HIP_TRY(hipMemcpy(by_slot.data(), a.vec, 9 * S * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t sl = 1; sl < S; sl++) {
+        const size_t i = (size_t)g->node_of_slot[sl];
+        std::copy(by_slot.begin() + 3 * sl, by_slot.begin() + 3 * sl + 3, delta3 + 3 * i);
+        if (precond3) std::copy(by_slot.begin() + 6 * S + 3 * sl, by_slot.begin() + 6 * S + 3 * sl + 3, precond3 + 3 * i);
+    }
     *cg_iterations = (int32_t)rec[ym::kPgRecCg];
     *residual = rec[ym::kPgRecResidual];
     *flags = (int32_t)rec[ym::kPgRecFlags];
@@ -261,6 +328,12 @@ int ym_graph_optimize(ym_graph *g, const ym_opt_params *p, ym_opt_report *out) {
     DEV_GUARD(g->device);
     ym::PgArgs a;
     if ((rc = graph_sync(g, W, &a)) != YM_OK) return rc;
+    if (!g->free_edge) { // nothing can move: zero steps, and the constant chi2 of the edges between held nodes
+        double held_chi2 = 0.0;
+        if ((rc = graph_linearise(g, a, &held_chi2)) != YM_OK) return rc;
+        out->chi2_initial = out->chi2_final = held_chi2;
+        return YM_OK;
+    }
     g->poses_stale = true; // (until the poses are back on the host: a call that fails leaves the graph as it was)
     a.cg_tol = p->exact ? 1e-10 : p->cg_tol;
     a.cg_cap = p->exact ? (int32_t)std::min<size_t>(9 * N, 20000) : p->max_cg_iters;

@@ -4,23 +4,31 @@
 // Node i: pose (x, y, theta).  Edge a -> b with mean z and information L (3 x 3, symmetric):
 //     e_xy = R(theta_a)^T (t_b - t_a) - z_xy,   e_theta = wrap(theta_b - theta_a - z_theta) into (-pi, pi],   chi2 = sum e^T L e
 //     J_a = [[-c, -s, -s dx + c dy], [s, -c, -c dx - s dy], [0, 0, -1]],   J_b = [[c, s, 0], [-s, c, 0], [0, 0, 1]]
-// (c, s = cos, sin theta_a; d = t_b - t_a).  A step solves (H + lambda diag(H)) delta = -g over the nodes 1 .. N-1; node 0 is
-// held: its row and column are replaced by the identity and its right-hand side by zero, so delta_0 = 0 exactly.
+// (c, s = cos, sin theta_a; d = t_b - t_a).  Every node is held or free; node 0 is always held.  A step solves
+// (H + lambda diag(H)) delta = -g over the free nodes: H, g and diag(H) are summed over all edges, so an edge between a free
+// and a held node gives the free node its diagonal block and gradient and nothing else, and an edge between two held nodes
+// only its chi2 term.  delta of a held node is exactly 0, and its trial pose is a copy of its pose (no wrap).
+// Solve order: slot 0 stands for all held nodes (identity row, right-hand side zero), the F free nodes take the slots 1 .. F
+// in index order (slot[N], 0 for a held node; node_of_slot[F + 1], entry 0 is node 0).  With only node 0 held slot(i) = i.
+// The band rows, the factor and the CG vectors are laid out by slot: [F + 1] rows, not [N].
 //
 // pg_linearise_kernel  one lane per edge: e, the edge's chi2 term, J_a^T L J_a, J_a^T L J_b, J_b^T L J_b, J_a^T L e, J_b^T L e
 // pg_assemble_kernel   one lane per node: walks the node's incident edges (a CSR the host builds, in edge order) and sums the
-//                      diagonal block and the gradient; the blocks (i, j), 0 < j - i <= W, go into the node's own row of the
-//                      band A[N][W+1] (block k of row i = A(i, i + k)), so no two lanes write one address.  Blocks further
-//                      from the diagonal stay with their edges: the mat-vec reads every off-diagonal block from its edge.
-// pg_solve_kernel      ONE workgroup.  Wave 0 factors band(A, W) = U^T U, a sweep over the N block rows with the rows
+//                      diagonal block and the gradient (of every node, held ones too); the blocks between two free nodes
+//                      with 0 < slot(j) - slot(i) <= W go into the row of slot(i) of the band A[F+1][W+1] (block k of row s =
+//                      A(s, s + k)); a held node writes no row, node 0 writes slot 0's, so no two lanes write one address.
+//                      Blocks further from the diagonal stay with their edges: the mat-vec reads every off-diagonal block
+//                      from its edge.
+// pg_solve_kernel      ONE workgroup.  Wave 0 factors band(A, W) = U^T U, a sweep over the F + 1 block rows with the rows
 //                      j .. j + W in an LDS window of (W+1)^2 blocks whose trailing update the lanes share; U is written row by
 //                      row and column by column, so both substitutions read one contiguous row a step and keep their W + 1
 //                      pending block rows in registers, one scalar a lane (the solved row's three are read with readlane; the
 //                      loads of the next rows are in flight several steps ahead).  The whole workgroup then runs
-//                      conjugate gradients preconditioned by that factor to the tolerance or the cap: mat-vec by node over the
-//                      CSR, axpys, and dot products reduced in a fixed shape (a strided partial a thread, a shuffle tree a wave,
-//                      the waves' sums in order).  W = 0 (block-Jacobi) factors and applies by node, all threads.
-// pg_update_kernel     trial = pose + delta, theta wrapped
+//                      conjugate gradients preconditioned by that factor to the tolerance or the cap: mat-vec by slot over the
+//                      free node's incidence list (neighbours of slot 0 skipped), axpys, and dot products reduced in a fixed
+//                      shape (a strided partial a thread, a shuffle tree a wave, the waves' sums in order).  W = 0
+//                      (block-Jacobi) factors and applies by slot, all threads.
+// pg_update_kernel     trial = pose + delta(slot), theta wrapped; a held node's trial is its pose, bit for bit
 // pg_chi2_kernel, pg_sum_kernel   chi2 at the trial poses: a partial a block, then one block over the partials
 // No floating-point atomics; every sum has a fixed order, so results are bit-identical from run to run.  Every loop is bounded
 // by N, the degree of a node or the iteration cap.  Plain C++ and vector memory operations only.
@@ -37,6 +45,9 @@ enum { kPgFlagConverged = 1, kPgFlagPivot = 2, kPgFlagBreakdown = 4 };
 
 struct PgArgs {
     int32_t n_nodes, n_edges, band;
+    int32_t n_slots;             // F + 1: slot 0 (the held nodes) and one slot a free node
+    const int32_t *slot;         // [N]: 0 for a held node, else 1 .. F in index order
+    const int32_t *node_of_slot; // [F + 1]: the node of a slot (entry 0: node 0)
     const double *pose;      // [N][3]
     double *trial;           // [N][3]
     const int32_t *from_to;  // [M][2]
@@ -49,9 +60,9 @@ struct PgArgs {
     double *e_chi;           // [M]
     double *diag;            // [N][9] as assembled (no damping, node 0 included)
     double *grad;            // [N][3] as assembled
-    double *aband;           // [N][W+1][9]: the damped system with node 0 held; block 0 is the diagonal block
+    double *aband;           // [F+1][W+1][9]: the damped system in solve order; block 0 is the diagonal block
     double *uband, *ubandT;  // the factor by rows: U(j, j+k) at [j][k]; by columns: U(j-k, j) at [j][k]
-    double *vec;             // x, r, z, p, q: [5][3 N]
+    double *vec;             // x, r, z, p, q: [5][3 (F+1)], in solve order
     double *partial;         // [ceil(M / 256)]
     double *record;          // [kPgRecWords]
     double lambda, cg_tol;
@@ -124,9 +135,11 @@ __global__ __launch_bounds__(256) void pg_linearise_kernel(PgArgs a) {
 __global__ __launch_bounds__(256) void pg_assemble_kernel(PgArgs a) {
     const int i = (int)(blockIdx.x * 256u + threadIdx.x);
     if (i >= a.n_nodes) return;
-    const int W = a.band, rowlen = (W + 1) * 9;
-    double *row = a.aband + (size_t)i * rowlen;
-    for (int k = 9; k < rowlen; k++) row[k] = 0.0;
+    const int W = a.band, rowlen = (W + 1) * 9, si = a.slot[i];
+    const bool rowed = si != 0 || i == 0; // (a held node but node 0 has no row of its own)
+    double *row = a.aband + (size_t)si * rowlen;
+    if (rowed)
+        for (int k = 9; k < rowlen; k++) row[k] = 0.0;
     double d[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};
     for (int q = a.node_ptr[i]; q < a.node_ptr[i + 1]; q++) {
         const int v = a.inc[q], e = v >> 1, side = v & 1;
@@ -137,8 +150,8 @@ __global__ __launch_bounds__(256) void pg_assemble_kernel(PgArgs a) {
 #pragma unroll
         for (int t = 0; t < 3; t++) g[t] += ge[t];
         const int other = a.from_to[2 * e + 1 - side];
-        const int k = other - i;
-        if (i != 0 && other != 0 && k > 0 && k <= W) {
+        const int so = a.slot[other], k = so - si;
+        if (si != 0 && so != 0 && k > 0 && k <= W) {
             double *dst = row + 9 * k;
 #pragma unroll
             for (int r = 0; r < 3; r++)
@@ -150,6 +163,7 @@ __global__ __launch_bounds__(256) void pg_assemble_kernel(PgArgs a) {
     for (int t = 0; t < 9; t++) a.diag[9 * (size_t)i + t] = d[t];
 #pragma unroll
     for (int t = 0; t < 3; t++) a.grad[3 * (size_t)i + t] = g[t];
+    if (!rowed) return;
     if (i == 0) {
 #pragma unroll
         for (int t = 0; t < 9; t++) row[t] = (t == 0 || t == 4 || t == 8) ? 1.0 : 0.0;
@@ -219,7 +233,7 @@ __device__ inline double pg_block_sum(double v, double *sh) {
 
 // wave 0: band(A, W) = U^T U with the rows j .. j + W in the LDS window `win`; returns whether a pivot was not positive
 __device__ inline bool pg_factor_band(const PgArgs &a, double *win, unsigned char *pk1, unsigned char *pk2) {
-    const int N = a.n_nodes, W = a.band, W1 = W + 1, rowlen = W1 * 9, lane = (int)threadIdx.x;
+    const int N = a.n_slots, W = a.band, W1 = W + 1, rowlen = W1 * 9, lane = (int)threadIdx.x;
     const int npairs = W * (W + 1) / 2;
     if (lane == 0) {
         int t = 0;
@@ -282,7 +296,7 @@ constexpr int kPgPrefetch = 6; // rows whose loads are in flight ahead of a subs
 // the scalar of step s + W + 1, which takes the slot over
 template <bool FWD>
 __device__ inline PgRow pg_row_load(const PgArgs &a, const double *src, int s, int slot, int c) {
-    const int N = a.n_nodes, W = a.band, W1 = W + 1, rowlen = W1 * 9, j = FWD ? s : N - 1 - s;
+    const int N = a.n_slots, W = a.band, W1 = W + 1, rowlen = W1 * 9, j = FWD ? s : N - 1 - s;
     const double *U = (FWD ? a.uband : a.ubandT) + (size_t)j * rowlen;
     PgRow r;
     r.t.i00 = U[0]; r.t.u01 = U[1]; r.t.u02 = U[2]; r.t.i11 = U[4]; r.t.u12 = U[5]; r.t.i22 = U[8];
@@ -305,7 +319,7 @@ __device__ inline PgRow pg_row_load(const PgArgs &a, const double *src, int s, i
 // wave 0: FWD: U^T y = src, else U x = src, one block row a step (dst may be src)
 template <bool FWD>
 __device__ inline void pg_sweep(const PgArgs &a, const double *src, double *dst) {
-    const int N = a.n_nodes, W = a.band, W1 = W + 1, lane = (int)threadIdx.x, slot = lane / 3, c = lane - 3 * slot;
+    const int N = a.n_slots, W = a.band, W1 = W + 1, lane = (int)threadIdx.x, slot = lane / 3, c = lane - 3 * slot;
     double p = (slot <= W && slot < N) ? src[3 * (size_t)(FWD ? slot : N - 1 - slot) + c] : 0.0;
     PgRow q[kPgPrefetch];
 #pragma unroll
@@ -331,7 +345,7 @@ __device__ inline void pg_sweep(const PgArgs &a, const double *src, double *dst)
 
 // z = band(A, W)^-1 r, by the whole workgroup (ends with a barrier)
 __device__ inline void pg_precondition(const PgArgs &a, const double *r, double *z) {
-    const int N = a.n_nodes;
+    const int N = a.n_slots;
     if (a.band == 0) {
         for (int i = (int)threadIdx.x; i < N; i += kPgSolveThreads) {
             const double *U = a.uband + 9 * (size_t)i;
@@ -349,18 +363,20 @@ __device__ inline void pg_precondition(const PgArgs &a, const double *r, double 
     __syncthreads();
 }
 
-// rows of node i of q = A p (the damped system, node 0 held): the diagonal block, then every incident edge's off-diagonal block
-__device__ inline void pg_matvec_node(const PgArgs &a, const double *p, int i, double &q0, double &q1, double &q2) {
-    const double *D = a.aband + (size_t)i * (a.band + 1) * 9, *pi = p + 3 * (size_t)i;
+// rows of slot sl of q = A p (the damped system in solve order): the diagonal block, then the off-diagonal block of every edge
+// from the slot's node to another free node
+__device__ inline void pg_matvec_slot(const PgArgs &a, const double *p, int sl, double &q0, double &q1, double &q2) {
+    const double *D = a.aband + (size_t)sl * (a.band + 1) * 9, *pi = p + 3 * (size_t)sl;
     q0 = D[0] * pi[0] + D[1] * pi[1] + D[2] * pi[2];
     q1 = D[3] * pi[0] + D[4] * pi[1] + D[5] * pi[2];
     q2 = D[6] * pi[0] + D[7] * pi[1] + D[8] * pi[2];
-    if (i == 0) return;
+    if (sl == 0) return;
+    const int i = a.node_of_slot[sl];
     for (int q = a.node_ptr[i]; q < a.node_ptr[i + 1]; q++) {
         const int v = a.inc[q], e = v >> 1, side = v & 1;
-        const int other = a.from_to[2 * e + 1 - side];
-        if (other == 0) continue;
-        const double *B = a.e_blk + 27 * (size_t)e + 9, *po = p + 3 * (size_t)other;
+        const int so = a.slot[a.from_to[2 * e + 1 - side]];
+        if (so == 0) continue;
+        const double *B = a.e_blk + 27 * (size_t)e + 9, *po = p + 3 * (size_t)so;
         if (side == 0) {
             q0 += B[0] * po[0] + B[1] * po[1] + B[2] * po[2];
             q1 += B[3] * po[0] + B[4] * po[1] + B[5] * po[2];
@@ -373,13 +389,13 @@ __device__ inline void pg_matvec_node(const PgArgs &a, const double *p, int i, d
     }
 }
 
-// grid: 1, kPgSolveThreads threads.  vec[0 .. 3N) = delta on return; record[kPgRecCg, kPgRecResidual, kPgRecFlags]
+// grid: 1, kPgSolveThreads threads.  vec[0 .. 3 (F+1)) = delta by slot on return; record[kPgRecCg, kPgRecResidual, kPgRecFlags]
 __global__ __launch_bounds__(kPgSolveThreads) void pg_solve_kernel(PgArgs a) {
     __shared__ double win[(kPgMaxBand + 1) * (kPgMaxBand + 1) * 9];
     __shared__ double red[kPgSolveThreads / 64];
     __shared__ unsigned char pk1[kPgMaxBand * (kPgMaxBand + 1) / 2], pk2[kPgMaxBand * (kPgMaxBand + 1) / 2];
     __shared__ int sh_bad;
-    const int N = a.n_nodes, tid = (int)threadIdx.x;
+    const int N = a.n_slots, tid = (int)threadIdx.x; // (every loop below runs over the slots)
     const size_t n3 = 3 * (size_t)N;
     double *x = a.vec, *r = a.vec + n3, *z = a.vec + 2 * n3, *p = a.vec + 3 * n3, *qv = a.vec + 4 * n3;
     if (tid == 0) sh_bad = 0;
@@ -397,10 +413,10 @@ __global__ __launch_bounds__(kPgSolveThreads) void pg_solve_kernel(PgArgs a) {
         const bool bad = pg_factor_band(a, win, pk1, pk2);
         if (bad && tid == 0) sh_bad = 1;
     }
-    // x = 0, r = b = -g with node 0 held
+    // x = 0, r = b = -g of the slot's node, slot 0 zero
     double acc = 0.0;
     for (size_t i = tid; i < n3; i += kPgSolveThreads) {
-        const double b = i < 3 ? 0.0 : -a.grad[i];
+        const double b = i < 3 ? 0.0 : -a.grad[3 * (size_t)a.node_of_slot[i / 3] + i % 3];
         x[i] = 0.0;
         r[i] = b;
         acc += b * b;
@@ -424,7 +440,7 @@ __global__ __launch_bounds__(kPgSolveThreads) void pg_solve_kernel(PgArgs a) {
             acc = 0.0;
             for (int i = tid; i < N; i += kPgSolveThreads) {
                 double q0, q1, q2;
-                pg_matvec_node(a, p, i, q0, q1, q2);
+                pg_matvec_slot(a, p, i, q0, q1, q2);
                 qv[3 * (size_t)i] = q0; qv[3 * (size_t)i + 1] = q1; qv[3 * (size_t)i + 2] = q2;
                 acc += p[3 * (size_t)i] * q0 + p[3 * (size_t)i + 1] * q1 + p[3 * (size_t)i + 2] * q2;
             }
@@ -465,8 +481,13 @@ __global__ __launch_bounds__(kPgSolveThreads) void pg_solve_kernel(PgArgs a) {
 __global__ __launch_bounds__(256) void pg_update_kernel(PgArgs a) {
     const int i = (int)(blockIdx.x * 256u + threadIdx.x);
     if (i >= a.n_nodes) return;
-    const double *p = a.pose + 3 * (size_t)i, *d = a.vec + 3 * (size_t)i;
+    const int sl = a.slot[i];
+    const double *p = a.pose + 3 * (size_t)i, *d = a.vec + 3 * (size_t)sl;
     double *t = a.trial + 3 * (size_t)i;
+    if (sl == 0) { // held: the pose as it is
+        t[0] = p[0]; t[1] = p[1]; t[2] = p[2];
+        return;
+    }
     t[0] = p[0] + d[0];
     t[1] = p[1] + d[1];
     t[2] = pg_wrap(p[2] + d[2]);

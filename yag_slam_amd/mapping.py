@@ -162,7 +162,8 @@ class LoopClosingMapper(SequentialMapper):
         self.verbose = verbose
         self.reject_low_fine = verbose if reject_low_fine is None else reject_low_fine
         self.opt = optimizer
-        self.scans = []           # vertex list, index == scan.num
+        self.held_nums = set()    # vertices held through hold_vertices
+        self.scans = []          # vertex list, index == scan.num
         self.adjacent = []        # adjacency sets by scan.num
         self.constraints = []     # (from_num, to_num, mean Transform, covariance)
         self.index = PoseBuckets(loop_search_dist)
@@ -280,12 +281,24 @@ class LoopClosingMapper(SequentialMapper):
         live.sync(self.scans)
         return live.ros_map(**filter_opts)
 
+    def hold_vertices(self, scans_or_nums):
+        """Keeps these vertices (scans, or their nums) where they are in every later `run_opt`: the optimiser's `hold`
+        (posegraph.PoseGraphOptimizer).  The vertices of a prior map are the case it is for."""
+        if self.opt is None or not hasattr(self.opt, "hold"):
+            raise ValueError("hold_vertices: the mapper has no optimizer with hold()")
+        nums = [int(getattr(v, "num", v)) for v in scans_or_nums]
+        self.opt.hold(nums)
+        self.held_nums.update(nums)
+
     def run_opt(self):
-        """graph_slam.py:262-272; a no-op without an optimizer except for the spatial index refresh"""
+        """graph_slam.py:262-272; a no-op without an optimizer except for the spatial index refresh.  Held vertices are not
+        written: their `corrected_pose` keeps its bits."""
         if self.opt is not None:
             self.opt.compute(100, 1.0e-4, True, 1.0e-9, 50)
             n = min(len(self.opt.nodes), len(self.scans))  # (zip's length, as graph_slam.py:268)
-            set_corrected_poses(self.scans[:n], [Transform(node.x, node.y, 0.0, node.yaw) for node in self.opt.nodes[:n]])
+            free = [k for k in range(n) if k not in self.held_nums] if self.held_nums else range(n)
+            nodes = self.opt.nodes
+            set_corrected_poses([self.scans[k] for k in free], [Transform(nodes[k].x, nodes[k].y, 0.0, nodes[k].yaw) for k in free])
         self.index.rebuild(self.scans)
 
     def process_scan(self, scan):

@@ -4,7 +4,9 @@ reference's `GraphSlam.opt`: the four calls they make on `sba_cpp.SPA2d` (`add_n
 one device.  The formulation is SPA2d's (Konolige et al. 2010); `sba_cpp` itself is not available to this project, so
 parity with it is NOT pinned: the semantics are DESIGN.md's ("Pose-graph optimiser"), pinned by tests/posegraph_ref.py.
 
-Adds are validated at once and buffered on the host; what is new goes to the library at the next `compute` / `chi2`.  The
+Beyond SPA2d: `hold(nodes)` / `release(nodes)` / `held` keep any set of nodes where they are (a prior map's vertices, a
+survey pose, the old part of a long log); `compute` then solves over the free nodes only.
+Adds and holds are validated at once and buffered on the host; what is new goes to the library at the next `compute` / `chi2`.  The
 native handle is created then: without a device that raises `YmError`, nothing is computed on the CPU instead.
 """
 import ctypes as C
@@ -70,7 +72,9 @@ class PoseGraphOptimizer(object):
         self._new_nodes = []           # rows of _xyt the library has not seen
         self._new_edges = []           # (a, b, x, y, yaw, info 3 x 3)
         self._n_edges = 0
-        self.band = -1                 # compute's preconditioner band: -1 automatic, 0 .. 16 (0: block-Jacobi)
+        self._held = {0}               # the held nodes as the library will know them after the next flush
+        self._new_holds = []           # (int32 array of nodes, 1: hold / 0: release), in call order
+        self.band = -1                # compute's preconditioner band: -1 automatic, 0 .. 16 (0: block-Jacobi)
         self.last_report = None
 
     # ---- the SPA2d surface
@@ -125,6 +129,40 @@ class PoseGraphOptimizer(object):
             return np.concatenate([self._xyt, np.array(self._new_nodes, dtype=np.float64).reshape(-1, 3)])
         return self._xyt
 
+    def hold(self, nodes):
+        """Holds the nodes where they are: `compute` solves over the others and leaves a held node's pose bit for bit
+        (DESIGN.md section 9).  Node 0 is always held.  Validated at once, buffered like the adds."""
+        self._set_held(nodes, 1)
+
+    def release(self, nodes):
+        """Frees nodes held before; node 0 cannot be released."""
+        self._set_held(nodes, 0)
+
+    @property
+    def held(self):
+        """the held nodes: a sorted int array that always contains 0"""
+        return np.array(sorted(self._held), dtype=np.int64)
+
+    def _set_held(self, nodes, flag):
+        what = "hold" if flag else "release"
+        arr = np.asarray(list(nodes) if not isinstance(nodes, np.ndarray) else nodes)
+        if arr.size and not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError("%s: node indices must be integers" % what)
+        arr = arr.astype(np.int64).reshape(-1)
+        n = len(self._xyt) + len(self._new_nodes)
+        bad = arr[(arr < 0) | (arr >= n)]
+        if bad.size:
+            raise ValueError("%s: node %d out of range (%d nodes)" % (what, int(bad[0]), n))
+        if not flag and (arr == 0).any():
+            raise ValueError("release: node 0 is always held and cannot be released")
+        if not arr.size:
+            return
+        if flag:
+            self._held.update(int(v) for v in arr)
+        else:
+            self._held.difference_update(int(v) for v in arr)
+        self._new_holds.append((np.ascontiguousarray(arr, dtype=np.int32), flag))
+
     @property
     def n_constraints(self):
         return self._n_edges
@@ -147,7 +185,8 @@ class PoseGraphOptimizer(object):
     def solve_step(self, lam, band=None, cg_tol=1.0e-10, max_cg_iters=0):
         """One damped solve at the current poses, which stay (ym_graph_solve, a test hook): (delta (N, 3), z (N, 3), band,
         iterations, residual, flags).  delta is the conjugate-gradient iterate and z the last application of the
-        preconditioner; with max_cg_iters = 0 delta is 0 and z = band(A, band)^-1 b.  band None: `self.band`."""
+        preconditioner; with max_cg_iters = 0 delta is 0 and z = band(A, band)^-1 b.  band None: `self.band`.  The rows of
+        held nodes are zero; the rows of the free nodes in index order are the solve order's slots 1 .. F."""
         L = self._flush()
         n = len(self._xyt)
         delta, z = np.zeros((n, 3)), np.zeros((n, 3))
@@ -197,6 +236,9 @@ class PoseGraphOptimizer(object):
             _capi.check(L.ym_graph_add_constraints(self._h, ft.ctypes.data_as(ip), mean.ctypes.data_as(dp), info.ctypes.data_as(dp),
                                                    len(ft)))
             self._new_edges = []
+        for arr, flag in self._new_holds:
+            _capi.check(L.ym_graph_hold(self._h, arr.ctypes.data_as(ip), len(arr), flag))
+        self._new_holds = []
         return L
 
 

@@ -449,19 +449,26 @@ def map_to_graph(map_image, resolution, origin, segments=None, layout="reference
     return virtual_scans(im, resolution, origin, centroids, layout=layout, device=device), edges
 
 
-def map_to_graphslam(mapper, map_image, resolution, origin, segments=None, layout="reference", device=0, density=1):
+def map_to_graphslam(mapper, map_image, resolution, origin, segments=None, layout="reference", device=0, density=1, hold=False):
     """map_to_graphslam (splicing.py:109-126) into an EMPTY `mapping.LoopClosingMapper`: `add_vertex` for every scan of
     `map_to_graph` in order, `link_scans(scan[a], scan[b], identity * 1e-12)` for every edge; `running_scans` stays empty, so
     the first live scan goes through `mapper.splice_first_scan`.  All scans stay: the reference's "get rid of any nodes that
     did not have edges" assigns an attribute (`slam_fake.vertices`) that nothing reads, and its renumbering over
-    `graph.vertices` is the identity -- no vertex is removed there, and none is here.  Returns the mapper."""
+    `graph.vertices` is the identity -- no vertex is removed there, and none is here.  Returns the mapper.
+    hold=True (not in the reference) holds every vertex added here through `mapper.hold_vertices`, after adding them: the
+    prior map stays where it is and a later closure re-poses the robot's own scans only.  It needs a mapper whose optimizer
+    has `hold` (`posegraph.PoseGraphOptimizer`); without one it raises ValueError before anything is added."""
     if mapper.scans or mapper.running_scans:
         raise ValueError("map_to_graphslam: the mapper already holds %d vertices and %d running scans; it must be empty"
                          % (len(mapper.scans), len(mapper.running_scans)))
+    if hold and not hasattr(getattr(mapper, "opt", None), "hold"):
+        raise ValueError("map_to_graphslam: hold=True needs a mapper with an optimizer that has hold()")
     more = {"density": density} if density != 1 else {}  # (the default is map_to_graph's own)
     scans, edges = map_to_graph(map_image, resolution, origin, segments, layout=layout, device=device, **more)
     for scan in scans:
         mapper.add_vertex(scan)
     for a, b in edges:
         mapper.link_scans(scans[a], scans[b], np.identity(3) * 1e-12)
+    if hold:
+        mapper.hold_vertices(scans)
     return mapper
