@@ -688,7 +688,7 @@ int ym_segments_labels(ym_segments *sg, int32_t *labels, int64_t n);
  *   ym_graph_add_constraints       SPA2d.add_constraint(a, b, x, y, yaw, info), n at a time
  *   ym_graph_get_poses / _size     SPA2d.nodes (x, y, yaw of every node) and its length
  *   ym_graph_set_poses             (no SPA2d call: re-seeds poses, e.g. to replay an optimisation)
- *   ym_graph_chi2                  (no SPA2d call: the cost at the current poses)
+ *   ym_graph_chi2                  (no SPA2d call: chi2 at the current poses, over the enabled constraints; see ym_graph_cost)
  *   ym_graph_linearise             (test hook: chi2, the diagonal blocks of H = J^T L J and the gradient J^T L e, undamped,
  *                                  node 0 included)
  *   ym_graph_solve                 (test hook: ONE damped solve at the current poses, which do not change.  It linearises,
@@ -750,6 +750,33 @@ int ym_graph_solve(ym_graph *g, int band /* -1 auto, 0 .. 16 */, double lambda, 
 typedef struct ym_opt_params { int32_t iters, exact, max_cg_iters, band /* -1 auto */; double lambda0, cg_tol; } ym_opt_params;
 typedef struct ym_opt_report { double chi2_initial, chi2_final, lambda_final; int32_t lm_steps, accepted, cg_iterations, band, status; } ym_opt_report;
 int ym_graph_optimize(ym_graph *g, const ym_opt_params *p, ym_opt_report *out);
+
+/* Robust kernels and switchable constraints.  A constraint's index is its place in the order of
+ * ym_graph_add_constraints.  Each has a kind, a parameter p > 0 and an enabled flag; it is YM_ROBUST_NONE and enabled when
+ * added.  With s = e^T L e its cost term is rho(s) and its weight w(s) = rho'(s):
+ *   YM_ROBUST_NONE            rho = s                                       w = 1
+ *   YM_ROBUST_HUBER (k)       rho = s if s <= k^2, else 2 k sqrt(s) - k^2   w = 1 if s <= k^2, else k / sqrt(s)
+ *   YM_ROBUST_CAUCHY (c)      rho = c^2 log1p(s / c^2)                      w = 1 / (1 + s / c^2)
+ *   YM_ROBUST_GEMAN_MCCLURE   rho = c^2 s / (c^2 + s)                       w = (c^2 / (c^2 + s))^2
+ *   disabled (any kind)       rho = 0                                       w = 0
+ * The objective is F = sum rho.  A step of ym_graph_optimize linearises with H = sum w J^T L J and g = sum w J^T L e, the
+ * weights taken at the current poses (first-order re-weighting, no second-order term), and every rule that speaks of chi2 --
+ * keep or reject, the gain stop, the 1e-18 stop -- uses F; ym_opt_report.chi2_initial and chi2_final hold F.  ym_graph_linearise
+ * returns F and the weighted blocks and gradient, ym_graph_solve solves the weighted system.  A graph whose constraints are
+ * all YM_ROBUST_NONE and enabled gets, bit for bit, what it got before there were kinds (w = 1.0, rho = s).
+ *   ym_graph_set_robust    the kind and parameter of the n constraints given (the parameter is stored for YM_ROBUST_NONE too)
+ *   ym_graph_enable        enables (enable = 1) or disables (0) the n constraints given.  Disabling is refused if it would
+ *                          leave a free node without an enabled constraint (its block would be singular); a node held at the
+ *                          time of the call is not checked, and a later release of it is the caller's business
+ *   ym_graph_edge_terms    s[M] and w[M] at the current poses; s of a disabled constraint is still its e^T L e, its w is 0
+ *   ym_graph_cost          F at the current poses.  ym_graph_chi2 stays the plain sum of s over the enabled constraints
+ * Errors: a constraint index out of range, a kind that is none of the four, a parameter that is not finite and positive, the
+ * refused disable.  A call that fails applies nothing.  ym_graph_set_robust and ym_graph_enable touch no device. */
+enum { YM_ROBUST_NONE = 0, YM_ROBUST_HUBER = 1, YM_ROBUST_CAUCHY = 2, YM_ROBUST_GEMAN_MCCLURE = 3 };
+int ym_graph_set_robust(ym_graph *g, const int32_t *edges, int n, int kind, double param);
+int ym_graph_enable(ym_graph *g, const int32_t *edges, int n, int enable /* 1: enable, 0: disable */);
+int ym_graph_edge_terms(ym_graph *g, double *s /* [M] */, double *w /* [M] */);
+int ym_graph_cost(ym_graph *g, double *cost);
 
 /* ---- introspection for parity tests (state of the LAST completed synchronous match) ---- */
 typedef struct ym_grid_info {

@@ -39,7 +39,7 @@ EXPORTS = (
     "ym_segments_destroy", "ym_map_free_space", "ym_segments_from_map", "ym_segments_labels",
     "ym_graph_create", "ym_graph_destroy", "ym_graph_add_nodes", "ym_graph_add_constraints", "ym_graph_size", "ym_graph_set_poses",
     "ym_graph_get_poses", "ym_graph_chi2", "ym_graph_linearise", "ym_graph_solve", "ym_graph_optimize",
-    "ym_graph_hold", "ym_graph_held",
+    "ym_graph_hold", "ym_graph_held", "ym_graph_set_robust", "ym_graph_enable", "ym_graph_edge_terms", "ym_graph_cost",
 )
 
 
@@ -384,6 +384,10 @@ def lib():
     L.ym_graph_linearise.argtypes = [vp, dp, dp, dp]
     L.ym_graph_solve.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_int, dp, dp, ip, ip, dp, ip]
     L.ym_graph_optimize.argtypes = [vp, C.POINTER(YmOptParams), C.POINTER(YmOptReport)]
+    L.ym_graph_set_robust.argtypes = [vp, ip, C.c_int, C.c_int, C.c_double]
+    L.ym_graph_enable.argtypes = [vp, ip, C.c_int, C.c_int]
+    L.ym_graph_edge_terms.argtypes = [vp, dp, dp]
+    L.ym_graph_cost.argtypes = [vp, dp]
     _lib = L
     return L
 

@@ -10,6 +10,9 @@ struct ym_graph {
     std::vector<double> pose, mean, info;
     std::vector<int32_t> from_to;
     std::vector<uint8_t> held;                   // [N]: 1 for a held node
+    std::vector<uint8_t> kind, enabled;          // [M]: the robust kernel of a constraint (YM_ROBUST_*), 0 for a disabled one
+    std::vector<double> param;                   // [M]: the kernel's parameter
+    bool robust_stale = true;                    // the device's copy of kind / enabled / param is behind the host's
     std::vector<int32_t> slot, node_of_slot;     // the solve order (valid unless slots_stale)
     bool free_edge = false;                      // some edge has a free end (valid unless slots_stale)
     bool slots_stale = true, slots_unsent = true; // the solve order is behind `held` / the device's copy behind the host's
@@ -17,7 +20,11 @@ struct ym_graph {
     int cur = 0;                                 // which of d_pose[2] holds the poses (the other takes the trial step)
     DevBuf<double> d_pose[2], d_mean, d_info, e_blk, e_grad, e_chi, diag, grad, aband, uband, ubandT, vec, partial, record;
     DevBuf<int32_t> d_from_to, node_ptr, inc, d_slot, d_node_of_slot;
+    DevBuf<uint8_t> d_kind, d_enabled;
+    DevBuf<double> d_param, e_s, e_w;
 };
+static_assert(YM_ROBUST_NONE == ym::kPgRobustNone && YM_ROBUST_HUBER == ym::kPgRobustHuber && YM_ROBUST_CAUCHY == ym::kPgRobustCauchy &&
+              YM_ROBUST_GEMAN_MCCLURE == ym::kPgRobustGemanMcClure, "the kernels read the header's kinds");
 
 ym_graph *ym_graph_create(int device) {
     if (check_device(device) != YM_OK) return nullptr;
@@ -96,7 +103,55 @@ int ym_graph_add_constraints(ym_graph *g, const int32_t *from_to, const double *
         for (int r = 0; r < 3; r++)
             for (int c = 0; c < 3; c++) g->info.push_back((L[3 * r + c] + L[3 * c + r]) / 2.0);
     }
-    if (n) g->edges_stale = g->slots_stale = true; // (free_edge is per edge)
+    const size_t M = g->from_to.size() / 2;
+    g->kind.resize(M, YM_ROBUST_NONE); // (plain and enabled when added)
+    g->enabled.resize(M, 1);
+    g->param.resize(M, 1.0);
+    if (n) g->edges_stale = g->slots_stale = g->robust_stale = true; // (free_edge is per edge)
+    return YM_OK;
+}
+
+// the index checks the per-constraint setters share (nothing is applied unless every index is good)
+static int graph_edge_indices(const ym_graph *g, const char *what, const int32_t *edges, int n) {
+    if (!g || n < 0 || (n > 0 && !edges)) return set_err(YM_ERR_INVALID, "bad argument");
+    const int64_t M = (int64_t)g->kind.size();
+    for (int i = 0; i < n; i++)
+        if (edges[i] < 0 || edges[i] >= M)
+            return set_err(YM_ERR_INVALID, "%s: constraint %d out of range (%lld constraints)", what, edges[i], (long long)M);
+    return YM_OK;
+}
+
+int ym_graph_set_robust(ym_graph *g, const int32_t *edges, int n, int kind, double param) {
+    int rc = graph_edge_indices(g, "set_robust", edges, n);
+    if (rc != YM_OK) return rc;
+    if (kind < YM_ROBUST_NONE || kind > YM_ROBUST_GEMAN_MCCLURE) return set_err(YM_ERR_INVALID, "set_robust: kind %d is not a YM_ROBUST_ value", kind);
+    if (!std::isfinite(param) || !(param > 0.0)) return set_err(YM_ERR_INVALID, "set_robust: the parameter must be finite and positive");
+    for (int i = 0; i < n; i++) {
+        g->kind[(size_t)edges[i]] = (uint8_t)kind;
+        g->param[(size_t)edges[i]] = param;
+    }
+    if (n) g->robust_stale = true;
+    return YM_OK;
+}
+
+int ym_graph_enable(ym_graph *g, const int32_t *edges, int n, int enable) {
+    int rc = graph_edge_indices(g, "enable", edges, n);
+    if (rc != YM_OK) return rc;
+    const uint8_t v = enable ? 1 : 0;
+    std::vector<uint8_t> after(g->enabled);
+    for (int i = 0; i < n; i++) after[(size_t)edges[i]] = v;
+    if (!enable) { // a free node of a constraint that goes must keep an enabled one: its block would be singular
+        std::vector<int32_t> left(g->held.size(), 0);
+        for (size_t e = 0; e < after.size(); e++)
+            if (after[e]) { left[(size_t)g->from_to[2 * e]]++; left[(size_t)g->from_to[2 * e + 1]]++; }
+        for (int i = 0; i < n; i++)
+            for (int side = 0; side < 2; side++) {
+                const int32_t node = g->from_to[2 * (size_t)edges[i] + side];
+                if (!g->held[(size_t)node] && left[(size_t)node] == 0)
+                    return set_err(YM_ERR_INVALID, "enable: disabling constraint %d would leave the free node %d without an enabled constraint", edges[i], node);
+            }
+    }
+    if (after != g->enabled) { g->enabled.swap(after); g->robust_stale = true; }
     return YM_OK;
 }
 
@@ -182,6 +237,14 @@ static int graph_sync(ym_graph *g, int W, ym::PgArgs *a) {
         HIP_TRY(hipMemcpy(g->inc.p, inc.data(), 2 * M * sizeof(int32_t), hipMemcpyHostToDevice));
         g->edges_stale = false;
     }
+    if (g->robust_stale) {
+        if ((rc = g->d_kind.ensure(M)) || (rc = g->d_enabled.ensure(M)) || (rc = g->d_param.ensure(M))) return rc;
+        HIP_TRY(hipMemcpy(g->d_kind.p, g->kind.data(), M * sizeof(uint8_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(g->d_enabled.p, g->enabled.data(), M * sizeof(uint8_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(g->d_param.p, g->param.data(), M * sizeof(double), hipMemcpyHostToDevice));
+        g->robust_stale = false;
+    }
+    if ((rc = g->e_s.ensure(M)) || (rc = g->e_w.ensure(M))) return rc;
     if ((rc = g->e_blk.ensure(27 * M)) || (rc = g->e_grad.ensure(6 * M)) || (rc = g->e_chi.ensure(M)) || (rc = g->diag.ensure(9 * N)) ||
         (rc = g->grad.ensure(3 * N)) || (rc = g->aband.ensure(S * rowlen)) || (rc = g->uband.ensure(S * rowlen)) ||
         (rc = g->ubandT.ensure(S * rowlen)) || (rc = g->vec.ensure(15 * S)) || (rc = g->partial.ensure((M + 255) / 256)) ||
@@ -195,15 +258,16 @@ static int graph_sync(ym_graph *g, int W, ym::PgArgs *a) {
     a->e_blk = g->e_blk.p; a->e_grad = g->e_grad.p; a->e_chi = g->e_chi.p; a->diag = g->diag.p; a->grad = g->grad.p;
     a->aband = g->aband.p; a->uband = g->uband.p; a->ubandT = g->ubandT.p; a->vec = g->vec.p; a->partial = g->partial.p;
     a->record = g->record.p;
+    a->kind = g->d_kind.p; a->enabled = g->d_enabled.p; a->param = g->d_param.p; a->e_s = g->e_s.p; a->e_w = g->e_w.p;
     return YM_OK;
 }
 
 static unsigned graph_blocks(int n) { return (unsigned)((n + 255) / 256); }
 
-// linearise at a.pose; *chi2 = the sum of the edges' terms
+// linearise at a.pose; *chi2 = the sum of the edges' cost terms, F = sum rho (chi2 itself on a graph without robust kernels)
 static int graph_linearise(ym_graph *g, const ym::PgArgs &a, double *chi2) {
     hipLaunchKernelGGL(ym::pg_linearise_kernel, dim3(graph_blocks(a.n_edges)), dim3(256), 0, g->stream, a);
-    hipLaunchKernelGGL(ym::pg_chi2_kernel<false>, dim3(graph_blocks(a.n_edges)), dim3(256), 0, g->stream, a);
+    hipLaunchKernelGGL(ym::pg_chi2_kernel<ym::kPgSumCost>, dim3(graph_blocks(a.n_edges)), dim3(256), 0, g->stream, a);
     hipLaunchKernelGGL(ym::pg_sum_kernel, dim3(1), dim3(256), 0, g->stream, a);
     HIP_TRY(hipGetLastError());
     double rec[ym::kPgRecWords];
@@ -213,6 +277,11 @@ static int graph_linearise(ym_graph *g, const ym::PgArgs &a, double *chi2) {
     return YM_OK;
 }
 
+// s and w of every constraint at a.pose, left in a.e_s and a.e_w (enqueued, not waited for)
+static void graph_edge_terms(ym_graph *g, const ym::PgArgs &a) {
+    hipLaunchKernelGGL(ym::pg_edge_terms_kernel, dim3(graph_blocks(a.n_edges)), dim3(256), 0, g->stream, a);
+}
+
 int ym_graph_chi2(ym_graph *g, double *chi2) {
     if (!g || !chi2) return set_err(YM_ERR_INVALID, "null argument");
     if (g->from_to.empty()) { *chi2 = 0.0; return YM_OK; }
@@ -220,7 +289,41 @@ int ym_graph_chi2(ym_graph *g, double *chi2) {
     ym::PgArgs a;
     int rc = graph_sync(g, 0, &a);
     if (rc != YM_OK) return rc;
-    return graph_linearise(g, a, chi2);
+    graph_edge_terms(g, a);
+    hipLaunchKernelGGL(ym::pg_chi2_kernel<ym::kPgSumPlain>, dim3(graph_blocks(a.n_edges)), dim3(256), 0, g->stream, a);
+    hipLaunchKernelGGL(ym::pg_sum_kernel, dim3(1), dim3(256), 0, g->stream, a);
+    HIP_TRY(hipGetLastError());
+    double rec[ym::kPgRecWords];
+    HIP_TRY(hipMemcpyAsync(rec, a.record, sizeof rec, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    *chi2 = rec[ym::kPgRecChi2];
+    return YM_OK;
+}
+
+int ym_graph_cost(ym_graph *g, double *cost) {
+    if (!g || !cost) return set_err(YM_ERR_INVALID, "null argument");
+    if (g->from_to.empty()) { *cost = 0.0; return YM_OK; }
+    DEV_GUARD(g->device);
+    ym::PgArgs a;
+    int rc = graph_sync(g, 0, &a);
+    if (rc != YM_OK) return rc;
+    return graph_linearise(g, a, cost);
+}
+
+int ym_graph_edge_terms(ym_graph *g, double *s, double *w) {
+    if (!g || !s || !w) return set_err(YM_ERR_INVALID, "null argument");
+    const size_t M = g->from_to.size() / 2;
+    if (M == 0) return YM_OK;
+    DEV_GUARD(g->device);
+    ym::PgArgs a;
+    int rc = graph_sync(g, 0, &a);
+    if (rc != YM_OK) return rc;
+    graph_edge_terms(g, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(s, a.e_s, M * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(w, a.e_w, M * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return YM_OK;
 }
 
 int ym_graph_linearise(ym_graph *g, double *chi2, double *diag9, double *grad3) {
@@ -328,7 +431,7 @@ int ym_graph_optimize(ym_graph *g, const ym_opt_params *p, ym_opt_report *out) {
     DEV_GUARD(g->device);
     ym::PgArgs a;
     if ((rc = graph_sync(g, W, &a)) != YM_OK) return rc;
-    if (!g->free_edge) { // nothing can move: zero steps, and the constant chi2 of the edges between held nodes
+    if (!g->free_edge) { // nothing can move: zero steps, and the constant cost of the edges between held nodes
         double held_chi2 = 0.0;
         if ((rc = graph_linearise(g, a, &held_chi2)) != YM_OK) return rc;
         out->chi2_initial = out->chi2_final = held_chi2;
@@ -353,7 +456,7 @@ int ym_graph_optimize(ym_graph *g, const ym_opt_params *p, ym_opt_report *out) {
         hipLaunchKernelGGL(ym::pg_assemble_kernel, dim3(graph_blocks(a.n_nodes)), dim3(256), 0, g->stream, a);
         hipLaunchKernelGGL(ym::pg_solve_kernel, dim3(1), dim3(ym::kPgSolveThreads), 0, g->stream, a);
         hipLaunchKernelGGL(ym::pg_update_kernel, dim3(graph_blocks(a.n_nodes)), dim3(256), 0, g->stream, a);
-        hipLaunchKernelGGL(ym::pg_chi2_kernel<true>, dim3(graph_blocks(a.n_edges)), dim3(256), 0, g->stream, a);
+        hipLaunchKernelGGL(ym::pg_chi2_kernel<ym::kPgSumTrial>, dim3(graph_blocks(a.n_edges)), dim3(256), 0, g->stream, a);
         hipLaunchKernelGGL(ym::pg_sum_kernel, dim3(1), dim3(256), 0, g->stream, a);
         HIP_TRY(hipGetLastError());
         double rec[ym::kPgRecWords];

@@ -12,7 +12,8 @@
 // in index order (slot[N], 0 for a held node; node_of_slot[F + 1], entry 0 is node 0).  With only node 0 held slot(i) = i.
 // The band rows, the factor and the CG vectors are laid out by slot: [F + 1] rows, not [N].
 //
-// pg_linearise_kernel  one lane per edge: e, the edge's chi2 term, J_a^T L J_a, J_a^T L J_b, J_b^T L J_b, J_a^T L e, J_b^T L e
+// pg_linearise_kernel  one lane per edge: e, the edge's cost term rho(e^T L e), and w times each of J_a^T L J_a, J_a^T L J_b,
+//                      J_b^T L J_b, J_a^T L e, J_b^T L e
 // pg_assemble_kernel   one lane per node: walks the node's incident edges (a CSR the host builds, in edge order) and sums the
 //                      diagonal block and the gradient (of every node, held ones too); the blocks between two free nodes
 //                      with 0 < slot(j) - slot(i) <= W go into the row of slot(i) of the band A[F+1][W+1] (block k of row s =
@@ -29,7 +30,12 @@
 //                      shape (a strided partial a thread, a shuffle tree a wave, the waves' sums in order).  W = 0
 //                      (block-Jacobi) factors and applies by slot, all threads.
 // pg_update_kernel     trial = pose + delta(slot), theta wrapped; a held node's trial is its pose, bit for bit
-// pg_chi2_kernel, pg_sum_kernel   chi2 at the trial poses: a partial a block, then one block over the partials
+// pg_chi2_kernel, pg_sum_kernel   the cost at the trial poses: a partial a block, then one block over the partials
+// pg_edge_terms_kernel one lane per edge: s = e^T L e and the weight w at the current poses
+// Robust kernels: every edge has a kind, a parameter p > 0 and an enabled flag.  With s = e^T L e the
+// edge's cost term is rho(s) and its blocks and gradient terms are scaled by w = rho'(s), taken at the poses of the
+// linearisation; a disabled edge has rho = w = 0.  The default kind has rho = s and w = 1.0: a product with 1.0 is exact, so a
+// graph without robust or disabled edges gets the bits it got before there were kinds.
 // No floating-point atomics; every sum has a fixed order, so results are bit-identical from run to run.  Every loop is bounded
 // by N, the degree of a node or the iteration cap.  Plain C++ and vector memory operations only.
 // Part of ym_kernels.hpp (include that, not this file).
@@ -42,6 +48,8 @@ constexpr int kPgSolveThreads = 512;  // the solve workgroup
 constexpr double kPgPi = 3.14159265358979323846;
 enum { kPgRecCg = 0, kPgRecResidual = 1, kPgRecFlags = 2, kPgRecChi2 = 3, kPgRecWords = 4 };
 enum { kPgFlagConverged = 1, kPgFlagPivot = 2, kPgFlagBreakdown = 4 };
+enum { kPgRobustNone = 0, kPgRobustHuber = 1, kPgRobustCauchy = 2, kPgRobustGemanMcClure = 3, kPgRobustKinds = 4 };
+enum { kPgSumCost = 0, kPgSumTrial = 1, kPgSumPlain = 2 }; // what pg_chi2_kernel sums
 
 struct PgArgs {
     int32_t n_nodes, n_edges, band;
@@ -53,11 +61,15 @@ struct PgArgs {
     const int32_t *from_to;  // [M][2]
     const double *mean;      // [M][3]
     const double *info;      // [M][9]
+    const uint8_t *kind;     // [M]: kPgRobust...
+    const uint8_t *enabled;  // [M]: 0 for a disabled edge
+    const double *param;     // [M]: the kind's parameter (k or c), > 0
     const int32_t *node_ptr; // [N + 1]
     const int32_t *inc;      // [2 M]: edge << 1 | (0: the node is the edge's a, 1: its b), by node, in edge order
     double *e_blk;           // [M][27]: J_a^T L J_a, J_a^T L J_b, J_b^T L J_b
     double *e_grad;          // [M][6]
-    double *e_chi;           // [M]
+    double *e_chi;           // [M]: rho of the edge at the poses of the linearisation
+    double *e_s, *e_w;       // [M] each: pg_edge_terms_kernel's s and w
     double *diag;            // [N][9] as assembled (no damping, node 0 included)
     double *grad;            // [N][3] as assembled
     double *aband;           // [F+1][W+1][9]: the damped system in solve order; block 0 is the diagonal block
@@ -91,12 +103,38 @@ __device__ inline double pg_quad(const double *L, const double r[3]) {
     return r[0] * l0 + r[1] * l1 + r[2] * l2;
 }
 
-// out = X^T Y (3 x 3, row-major)
-__device__ inline void pg_atb(const double X[9], const double Y[9], double *out) {
+// rho(s) of an enabled edge of kind `kind` with parameter p
+__device__ inline double pg_rho(int kind, double p, double s) {
+    const double p2 = p * p;
+    switch (kind) {
+    case kPgRobustHuber: return s <= p2 ? s : 2.0 * p * sqrt(s) - p2;
+    case kPgRobustCauchy: return p2 * log1p(s / p2);
+    case kPgRobustGemanMcClure: return p2 * s / (p2 + s);
+    default: return s;
+    }
+}
+
+// w(s) = rho'(s)
+__device__ inline double pg_weight(int kind, double p, double s) {
+    const double p2 = p * p;
+    switch (kind) {
+    case kPgRobustHuber: return s <= p2 ? 1.0 : p / sqrt(s);
+    case kPgRobustCauchy: return 1.0 / (1.0 + s / p2);
+    case kPgRobustGemanMcClure: { const double q = p2 / (p2 + s); return q * q; }
+    default: return 1.0;
+    }
+}
+
+// the cost term and the weight of edge e, whose e^T L e is s
+__device__ inline double pg_edge_rho(const PgArgs &a, int e, double s) { return a.enabled[e] ? pg_rho(a.kind[e], a.param[e], s) : 0.0; }
+__device__ inline double pg_edge_weight(const PgArgs &a, int e, double s) { return a.enabled[e] ? pg_weight(a.kind[e], a.param[e], s) : 0.0; }
+
+// out = w X^T Y (3 x 3, row-major)
+__device__ inline void pg_atb(const double X[9], const double Y[9], double w, double *out) {
 #pragma unroll
     for (int r = 0; r < 3; r++)
 #pragma unroll
-        for (int c = 0; c < 3; c++) out[r * 3 + c] = X[r] * Y[c] + X[3 + r] * Y[3 + c] + X[6 + r] * Y[6 + c];
+        for (int c = 0; c < 3; c++) out[r * 3 + c] = w * (X[r] * Y[c] + X[3 + r] * Y[3 + c] + X[6 + r] * Y[6 + c]);
 }
 
 // grid: ceil(M / 256), 256 threads
@@ -118,17 +156,30 @@ __global__ __launch_bounds__(256) void pg_linearise_kernel(PgArgs a) {
         }
         Le[i] = L[i * 3] * r[0] + L[i * 3 + 1] * r[1] + L[i * 3 + 2] * r[2];
     }
+    const double sq = r[0] * Le[0] + r[1] * Le[1] + r[2] * Le[2];
+    const double w = pg_edge_weight(a, e, sq);
     double *blk = a.e_blk + 27 * (size_t)e;
-    pg_atb(Ja, LJa, blk);
-    pg_atb(Ja, LJb, blk + 9);
-    pg_atb(Jb, LJb, blk + 18);
+    pg_atb(Ja, LJa, w, blk);
+    pg_atb(Ja, LJb, w, blk + 9);
+    pg_atb(Jb, LJb, w, blk + 18);
     double *g = a.e_grad + 6 * (size_t)e;
 #pragma unroll
     for (int i = 0; i < 3; i++) {
-        g[i] = Ja[i] * Le[0] + Ja[3 + i] * Le[1] + Ja[6 + i] * Le[2];
-        g[3 + i] = Jb[i] * Le[0] + Jb[3 + i] * Le[1] + Jb[6 + i] * Le[2];
+        g[i] = w * (Ja[i] * Le[0] + Ja[3 + i] * Le[1] + Ja[6 + i] * Le[2]);
+        g[3 + i] = w * (Jb[i] * Le[0] + Jb[3 + i] * Le[1] + Jb[6 + i] * Le[2]);
     }
-    a.e_chi[e] = r[0] * Le[0] + r[1] * Le[1] + r[2] * Le[2];
+    a.e_chi[e] = pg_edge_rho(a, e, sq);
+}
+
+// grid: ceil(M / 256), 256 threads: e_s = e^T L e of every edge (a disabled one too), e_w = its weight, at a.pose
+__global__ __launch_bounds__(256) void pg_edge_terms_kernel(PgArgs a) {
+    const int e = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (e >= a.n_edges) return;
+    double r[3], c, s, dx, dy;
+    pg_residual(a, a.pose, e, r, c, s, dx, dy);
+    const double sq = pg_quad(a.info + 9 * (size_t)e, r);
+    a.e_s[e] = sq;
+    a.e_w[e] = pg_edge_weight(a, e, sq);
 }
 
 // grid: ceil(N / 256), 256 threads
@@ -501,17 +552,20 @@ __device__ inline double pg_block256_sum(double v, double *sh) {
     return sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-// grid: ceil(M / 256), 256 threads.  TRIAL: at a.trial, else the terms pg_linearise_kernel left in e_chi
-template <bool TRIAL>
+// grid: ceil(M / 256), 256 threads.  kPgSumTrial: rho at a.trial; kPgSumCost: the terms pg_linearise_kernel left in e_chi;
+// kPgSumPlain: the plain chi2, pg_edge_terms_kernel's s of the enabled edges
+template <int WHAT>
 __global__ __launch_bounds__(256) void pg_chi2_kernel(PgArgs a) {
     __shared__ double sh[4];
     const int e = (int)(blockIdx.x * 256u + threadIdx.x);
     double v = 0.0;
     if (e < a.n_edges) {
-        if (TRIAL) {
+        if (WHAT == kPgSumTrial) {
             double r[3], c, s, dx, dy;
             pg_residual(a, a.trial, e, r, c, s, dx, dy);
-            v = pg_quad(a.info + 9 * (size_t)e, r);
+            v = pg_edge_rho(a, e, pg_quad(a.info + 9 * (size_t)e, r));
+        } else if (WHAT == kPgSumPlain) {
+            v = a.enabled[e] ? a.e_s[e] : 0.0;
         } else {
             v = a.e_chi[e];
         }

@@ -148,12 +148,22 @@ class LoopClosingMapper(SequentialMapper):
     the closing scan.
 
     The reference rejects a low FINE response only when `verbose` is set (`... and self.verbose`,
-    graph_slam.py:240); `reject_low_fine=None` follows that, True/False overrides it."""
+    graph_slam.py:240); `reject_low_fine=None` follows that, True/False overrides it.
+
+    `robust_closures=(kind, p)` (None, the default: everything as before) gives the constraint a closure adds -- and no other:
+    odometry and running-chain constraints stay plain -- that robust kernel of the optimiser (DESIGN.md section 9.2;
+    `PoseGraphOptimizer.add_constraint(..., robust=)`), so that one false closure cannot bend the trajectory.
+    `closure_weights()` then tells how much each closure still counts, and `drop_closures(max_weight)` takes out the ones
+    that count less than that."""
 
     def __init__(self, seq_matcher, loop_matcher, scan_buffer_len=10, loop_search_dist=3,
                  loop_search_min_chain_size=10, min_response_coarse=0.35, min_response_fine=0.45,
-                 verbose=False, optimizer=None, reject_low_fine=None):
+                 verbose=False, optimizer=None, reject_low_fine=None, robust_closures=None):
         super().__init__(seq_matcher, scan_buffer_len)
+        if robust_closures is not None:
+            from .posegraph import _robust_pair
+            _robust_pair(robust_closures, "LoopClosingMapper: robust_closures")
+        self.robust_closures = robust_closures
         self.loop_matcher = loop_matcher
         self.loop_search_dist = loop_search_dist
         self.loop_search_min_chain_size = loop_search_min_chain_size
@@ -168,6 +178,9 @@ class LoopClosingMapper(SequentialMapper):
         self.constraints = []     # (from_num, to_num, mean Transform, covariance)
         self.index = PoseBuckets(loop_search_dist)
         self.closures = []        # (scan.num, chain nums, coarse result, fine result)
+        self.closure_edges = []   # per closure: the index of its constraint in the optimiser (None: it added none)
+        self.last_edge = None     # the optimiser's index of the constraint the last link_scans added
+        self.dropped_edges = set()  # the constraints drop_closures disabled
 
     # ---- graph bookkeeping (graph_slam.py:132-192) ----
     def add_vertex(self, scan):
@@ -179,7 +192,8 @@ class LoopClosingMapper(SequentialMapper):
             p = scan.corrected_pose
             self.opt.add_node(p.x, p.y, p.euler[-1], scan.num)
 
-    def link_scans(self, from_scan, to_scan, covariance):
+    def link_scans(self, from_scan, to_scan, covariance, robust=None):
+        """robust: the optimiser's robust kernel for this constraint, (kind, p); passed on only when set"""
         if to_scan.num in self.adjacent[from_scan.num] or from_scan.num == to_scan.num:
             return False
         mean = to_scan.corrected_pose - from_scan.corrected_pose
@@ -188,12 +202,15 @@ class LoopClosingMapper(SequentialMapper):
         self.constraints.append((from_scan.num, to_scan.num, mean, covariance))
         if self.opt is not None:
             import numpy as np
-            self.opt.add_constraint(from_scan.num, to_scan.num, mean.x, mean.y, mean.euler[-1],
-                                    np.linalg.inv(np.array(covariance)).tolist())
+            kw = {} if robust is None else {"robust": robust}
+            edge = self.opt.add_constraint(from_scan.num, to_scan.num, mean.x, mean.y, mean.euler[-1],
+                                           np.linalg.inv(np.array(covariance)).tolist(), **kw)
+            # (an optimiser with SPA2d's four calls returns nothing: its constraints are in the order of `constraints`)
+            self.last_edge = edge if isinstance(edge, int) else len(self.constraints) - 1
         return True
 
-    def link_to_closest_scan_in_chain(self, scan, chain, covariance):
-        self.link_scans(min(chain, key=lambda s: _dist2(s, scan)), scan, covariance)
+    def link_to_closest_scan_in_chain(self, scan, chain, covariance, robust=None):
+        return self.link_scans(min(chain, key=lambda s: _dist2(s, scan)), scan, covariance, robust)
 
     def near_linked(self, scan):
         """scans reachable from `scan` through constraints without leaving the loop_search_dist disc
@@ -251,8 +268,9 @@ class LoopClosingMapper(SequentialMapper):
             if res.response < self.min_response_fine and self.reject_low_fine:
                 continue
             scan.corrected_pose = res.best_pose
-            self.link_to_closest_scan_in_chain(scan, chain, res.covariance)
+            linked = self.link_to_closest_scan_in_chain(scan, chain, res.covariance, self.robust_closures)
             self.closures.append((scan.num, [s.num for s in chain], res_coarse, res))
+            self.closure_edges.append(self.last_edge if linked and self.opt is not None else None)
             self.run_opt()
             return True
         return False
@@ -300,6 +318,36 @@ class LoopClosingMapper(SequentialMapper):
             nodes = self.opt.nodes
             set_corrected_poses([self.scans[k] for k in free], [Transform(nodes[k].x, nodes[k].y, 0.0, nodes[k].yaw) for k in free])
         self.index.rebuild(self.scans)
+
+    def closure_weights(self):
+        """[(scan num, constraint index, s, w)] of every closure that added a constraint, at the poses of the last `run_opt`:
+        s = e^T L e and the weight w its robust kernel gives it (`PoseGraphOptimizer.edge_terms`); w of a closure that fits
+        is near 1, of one that contradicts the rest of the graph near 0 (exactly 1 without `robust_closures`)."""
+        if self.opt is None or not hasattr(self.opt, "edge_terms"):
+            raise ValueError("closure_weights: the mapper has no optimizer with edge_terms()")
+        s, w = self.opt.edge_terms()
+        return [(c[0], e, float(s[e]), float(w[e])) for c, e in zip(self.closures, self.closure_edges) if e is not None]
+
+    def drop_closures(self, max_weight):
+        """Disables the constraint of every closure whose weight (`closure_weights`) is below `max_weight`, forgets that the
+        two scans were linked (so that the pair can close again later), runs `run_opt` and returns what it dropped, as
+        `closure_weights` lists it.  The closures leave `closures` and `closure_edges`; the constraints stay in `constraints`
+        and in the optimiser, disabled (their indices are in `dropped_edges`)."""
+        drop = [c for c in self.closure_weights() if c[3] < max_weight]
+        if not drop:
+            return []
+        edges = {c[1] for c in drop}
+        self.opt.disable(sorted(edges))  # (refused, and nothing changed, if a free vertex would lose its last constraint)
+        for e in edges:  # (the optimiser's constraints are in the order of `constraints`: both are filled by the same calls)
+            f, t = self.constraints[e][:2]
+            self.adjacent[f].discard(t)
+            self.adjacent[t].discard(f)
+        keep = [k for k, e in enumerate(self.closure_edges) if e not in edges]
+        self.closures = [self.closures[k] for k in keep]
+        self.closure_edges = [self.closure_edges[k] for k in keep]
+        self.dropped_edges |= edges
+        self.run_opt()
+        return drop
 
     def process_scan(self, scan):
         """Returns (result, closed) like graph_slam.py:306-339; (None, None) for the first scan."""

@@ -6,7 +6,12 @@ parity with it is NOT pinned: the semantics are DESIGN.md's ("Pose-graph optimis
 
 Beyond SPA2d: `hold(nodes)` / `release(nodes)` / `held` keep any set of nodes where they are (a prior map's vertices, a
 survey pose, the old part of a long log); `compute` then solves over the free nodes only.
-Adds and holds are validated at once and buffered on the host; what is new goes to the library at the next `compute` / `chi2`.  The
+Robust kernels: a constraint may carry `("huber" | "cauchy" | "geman_mcclure", p)`, given to
+`add_constraint(..., robust=...)` or `set_robust(edges, robust)`, and can be switched off and on again (`disable`, `enable`);
+`edge_terms()` tells each constraint's s = e^T L e and weight, `cost()` the robust objective.  A constraint's index is the
+order it was added in, which `add_constraint` returns.
+Adds, holds and the per-constraint settings are validated at once and buffered on the host; what is new goes to the library at
+the next `compute` / `chi2` (a `disable` goes at once: the library may refuse it).  The
 native handle is created then: without a device that raises `YmError`, nothing is computed on the CPU instead.
 """
 import ctypes as C
@@ -17,6 +22,7 @@ import numpy as np
 from . import _capi
 
 STATUS = {0: "step limit", 1: "converged", 2: "residual vanished", 3: "lambda limit"}
+ROBUST_KINDS = {"huber": 1, "cauchy": 2, "geman_mcclure": 3}  # YM_ROBUST_*; None is YM_ROBUST_NONE, 0
 
 
 class OptReport(object):
@@ -64,6 +70,25 @@ def _finite(*values):
     return all(math.isfinite(v) for v in values)
 
 
+def _robust_pair(robust, what):
+    """(YM_ROBUST_ kind, parameter) of `robust`: None, or (name, p) with p finite and positive"""
+    if robust is None:
+        return 0, 1.0
+    try:
+        name, p = robust
+    except (TypeError, ValueError):
+        raise ValueError("%s: robust must be None or (kind, parameter), not %r" % (what, robust))
+    if not isinstance(name, str) or name not in ROBUST_KINDS:
+        raise ValueError("%s: robust kind %r: one of %s" % (what, name, ", ".join(sorted(ROBUST_KINDS))))
+    try:
+        p = float(p)
+    except (TypeError, ValueError):
+        raise ValueError("%s: the parameter of a robust kernel must be a number, not %r" % (what, p))
+    if not math.isfinite(p) or not p > 0.0:
+        raise ValueError("%s: the parameter of a robust kernel must be finite and positive, not %r" % (what, p))
+    return ROBUST_KINDS[name], p
+
+
 class PoseGraphOptimizer(object):
     def __init__(self, device=0):
         self.device = int(device)
@@ -73,7 +98,9 @@ class PoseGraphOptimizer(object):
         self._new_edges = []           # (a, b, x, y, yaw, info 3 x 3)
         self._n_edges = 0
         self._held = {0}               # the held nodes as the library will know them after the next flush
-        self._new_holds = []           # (int32 array of nodes, 1: hold / 0: release), in call order
+        # what the library has not heard of the held set and of the constraints' kernels and switches, in call order:
+        # ("hold", int32 nodes, 1 / 0), ("robust", int32 edges, kind, p), ("enable", int32 edges, 1 / 0)
+        self._new_ops = []
         self.band = -1                # compute's preconditioner band: -1 automatic, 0 .. 16 (0: block-Jacobi)
         self.last_report = None
 
@@ -87,7 +114,8 @@ class PoseGraphOptimizer(object):
             raise ValueError("add_node: a pose that is not finite")
         self._new_nodes.append((x, y, yaw))
 
-    def add_constraint(self, a, b, x, y, yaw, info):
+    def add_constraint(self, a, b, x, y, yaw, info, robust=None):
+        """`SPA2d.add_constraint`; robust: None or ("huber" | "cauchy" | "geman_mcclure", p).  Returns the constraint's index."""
         n = len(self._xyt) + len(self._new_nodes)
         a, b = int(a), int(b)
         if not (0 <= a < n and 0 <= b < n):
@@ -102,8 +130,12 @@ class PoseGraphOptimizer(object):
             raise ValueError("add_constraint: a value that is not finite")
         if not (np.diag(info) > 0).all():
             raise ValueError("add_constraint: an information matrix without a positive diagonal")
+        kind, p = _robust_pair(robust, "add_constraint")
         self._new_edges.append((a, b, x, y, yaw, info))
         self._n_edges += 1
+        if kind:
+            self._new_ops.append(("robust", np.array([self._n_edges - 1], dtype=np.int32), kind, p))
+        return self._n_edges - 1
 
     def compute(self, iters=100, lam=1.0e-4, use_csparse=True, init_tol=1.0e-9, max_cg_iters=50):
         """`SPA2d.compute`.  use_csparse: every step solved to a relative residual of 1e-10 (init_tol and max_cg_iters are
@@ -161,11 +193,57 @@ class PoseGraphOptimizer(object):
             self._held.update(int(v) for v in arr)
         else:
             self._held.difference_update(int(v) for v in arr)
-        self._new_holds.append((np.ascontiguousarray(arr, dtype=np.int32), flag))
+        self._new_ops.append(("hold", np.ascontiguousarray(arr, dtype=np.int32), flag))
 
     @property
     def n_constraints(self):
         return self._n_edges
+
+    def _edge_indices(self, edges, what):
+        arr = np.asarray(list(edges) if not isinstance(edges, np.ndarray) else edges)
+        if arr.size and not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError("%s: constraint indices must be integers" % what)
+        arr = arr.astype(np.int64).reshape(-1)
+        bad = arr[(arr < 0) | (arr >= self._n_edges)]
+        if bad.size:
+            raise ValueError("%s: constraint %d out of range (%d constraints)" % (what, int(bad[0]), self._n_edges))
+        return np.ascontiguousarray(arr, dtype=np.int32)
+
+    def set_robust(self, edges, robust):
+        """The robust kernel of these constraints: ("huber" | "cauchy" | "geman_mcclure", p), or None for the plain square."""
+        kind, p = _robust_pair(robust, "set_robust")
+        arr = self._edge_indices(edges, "set_robust")
+        if arr.size:
+            self._new_ops.append(("robust", arr, kind, p))
+
+    def enable(self, edges):
+        """Switches constraints disabled before on again."""
+        arr = self._edge_indices(edges, "enable")
+        if arr.size:
+            self._new_ops.append(("enable", arr, 1))
+
+    def disable(self, edges):
+        """Takes these constraints out of the objective (cost and weight 0) without forgetting them.  Goes to the library at
+        once: it raises `YmError`, and changes nothing, if a free node would be left without an enabled constraint."""
+        arr = self._edge_indices(edges, "disable")
+        if arr.size:
+            self._new_ops.append(("enable", arr, 0))
+            self._flush()
+
+    def edge_terms(self):
+        """(s, w): s = e^T L e of every constraint at the current poses and its weight w = rho'(s); w of a disabled one is 0"""
+        L = self._flush()
+        s, w = np.zeros(self._n_edges), np.zeros(self._n_edges)
+        dp = C.POINTER(C.c_double)
+        _capi.check(L.ym_graph_edge_terms(self._h, s.ctypes.data_as(dp), w.ctypes.data_as(dp)))
+        return s, w
+
+    def cost(self):
+        """F = the sum of rho(s) over the constraints, what `compute` lowers; `chi2()` is the plain sum of s over the enabled ones"""
+        L = self._flush()
+        out = C.c_double()
+        _capi.check(L.ym_graph_cost(self._h, C.byref(out)))
+        return out.value
 
     def chi2(self):
         L = self._flush()
@@ -174,7 +252,8 @@ class PoseGraphOptimizer(object):
         return out.value
 
     def linearise(self):
-        """(chi2, diagonal blocks (N, 3, 3), gradient (N, 3)) of the undamped system at the current poses, node 0 included"""
+        """(cost, diagonal blocks (N, 3, 3), gradient (N, 3)) of the undamped, weighted system at the current poses, node 0
+        included; the cost is chi2 on a graph without robust kernels"""
         L = self._flush()
         n = len(self._xyt)
         chi2, diag, grad = C.c_double(), np.zeros((n, 3, 3)), np.zeros((n, 3))
@@ -236,9 +315,14 @@ class PoseGraphOptimizer(object):
             _capi.check(L.ym_graph_add_constraints(self._h, ft.ctypes.data_as(ip), mean.ctypes.data_as(dp), info.ctypes.data_as(dp),
                                                    len(ft)))
             self._new_edges = []
-        for arr, flag in self._new_holds:
-            _capi.check(L.ym_graph_hold(self._h, arr.ctypes.data_as(ip), len(arr), flag))
-        self._new_holds = []
+        while self._new_ops:  # (an op the library refuses is dropped with the error it raises)
+            op = self._new_ops.pop(0)
+            if op[0] == "hold":
+                _capi.check(L.ym_graph_hold(self._h, op[1].ctypes.data_as(ip), len(op[1]), op[2]))
+            elif op[0] == "robust":
+                _capi.check(L.ym_graph_set_robust(self._h, op[1].ctypes.data_as(ip), len(op[1]), op[2], op[3]))
+            else:
+                _capi.check(L.ym_graph_enable(self._h, op[1].ctypes.data_as(ip), len(op[1]), op[2]))
         return L
 
 
