@@ -29,7 +29,7 @@ namespace ym {
 #define YM_RG_PROF 0
 #endif
 #if YM_RG_PROF
-#if YM_RG_PROF == 2 // phase 1 in three parts: 7 the next region's box and segment (LDS), 8 its entry list (one global load), 1 the staging loads; 2 gather
+#if YM_RG_PROF == 2 // phase 1 in three parts: 7 the table words of the next regions (v_readlane of a row read a round ago), 8 the entry list two rounds ahead (one global load), 1 the staging loads; 2 gather
 #define YM_RG_PH(i) do { if ((i) == 7 || (i) == 8 || (i) == 1 || (i) == 2 || (i) == 5) { const uint32_t t_ = (uint32_t)__builtin_amdgcn_s_memtime(); \
     if ((i) != 5) ph[(i) == 7 ? 0 : (i) == 8 ? 1 : (i) == 1 ? 2 : 3] += t_ - pt; pt = t_; } } while (0)
 #else
@@ -459,9 +459,9 @@ __device__ __forceinline__ void rg_odd(uint32_t (&)[8]) {}
 
 // grid (P, B): block (p, item) = NW waves, wave w owns coarse angle p * NW + w.  Lane = 13 x-adjacent hypotheses of one
 // lattice row: row = lane & 31, half = lane >> 5 (nx <= 26, ny <= 32: checked on the host).
-// The walk over the regions is a two-stage pipeline: while region i is gathered, the global loads of region i + 1 are in
-// flight (registers) together with the wave's first 128 entries of it; they go to LDS between the two barriers that end
-// the gather.
+// The walk over the regions is a pipeline: while region i is gathered, the global loads of region i + 1 are in flight
+// (registers) and go to LDS between the two barriers that end the gather; a wave's first 256 entries of a region are loaded two
+// rounds before they are gathered, and what a round needs to know of its regions comes from a table built once (rtab).
 // WIN (round 4, large batches): the regions are staged from the ROW-MAJOR WINDOW, not from its column planes -- a staged row of
 // the two column classes of one row parity is 192 contiguous window bytes (16 bytes = eight class bytes of each parity, split by
 // two v_perm_b32 on their way into LDS) instead of 96 + 96 bytes half a megabyte apart, and the raster of such a call does not
@@ -471,9 +471,13 @@ __global__ __launch_bounds__(64 * NW, NW <= 8 ? (3 * NW + 3) / 4 : 1 /* three bl
     constexpr int NT = 64 * NW;
     constexpr int PER = (YM_RG_ROWS + (NT / 4) / YM_RG_SEGS - 1) / ((NT / 4) / YM_RG_SEGS); // copy tasks per thread (rows of its segment)
     __shared__ __attribute__((aligned(16))) unsigned char region[YM_RG_LDS_BYTES]; // four class images + the zero patch
-    __shared__ int rlist[YM_RG_MAX_REGIONS];
-    __shared__ uint32_t rboxl[YM_RG_MAX_REGIONS];     // per listed region: first row | last row << 8 | first segment << 16 | last << 24 to stage
-    __shared__ unsigned short seginfo[NW][YM_RG_MAX_REGIONS][2]; // per wave and listed region: its first entry and the end
+    // The round table: everything a round needs to know of a listed region, computed once before the walk.  Row i = listed region i:
+    //   [0]      what to stage of it: the copy bands its rows reach (bit q = task q of every thread) | first segment << 16 | last << 24,
+    //            segments counted as the copy threads count them (WIN: half segments);
+    //   [1]      where it starts in the item's window (WIN) or planes, in bytes -- below 2^31, `regular` checks it;
+    //   [2 + w]  wave w's entries of it: first | end << 16 (positions in the query's entry array, below 65536).
+    // The walk reads it with one ds_read_b32 per round (row_read): no division, no multiplication, no second array.
+    __shared__ uint32_t rtab[YM_RG_MAX_REGIONS][2 + NW];
     // (until round 5 a wave's first 256 entries of the region being gathered went through LDS -- uint2 elist[NW][64], a broadcast
     //  ds_read_b64 per four patches; the compiler, seeing a wave-uniform value, put a v_readfirstlane and with it an
     //  s_waitcnt lgkmcnt(0) right behind every such read: one exposed LDS round trip per four patches, behind the queue of every
@@ -529,48 +533,18 @@ __global__ __launch_bounds__(64 * NW, NW <= 8 ? (3 * NW + 3) / 4 : 1 /* three bl
     const uint32_t pt_begin = pt;
     const unsigned long long rt_begin = __builtin_amdgcn_s_memrealtime(); // (100 MHz: against the shader clocks of pt it gives the clock the wave ran at)
 #endif
-    const bool regular = st.regular[0] && a.force_irregular != 1 && rg_part_listed(a, st.qslot, p);
+    // (a region's source offset and a copy task's offset inside the region are 32-bit numbers: the host refuses windows beyond
+    //  2e9 bytes, YM_RG_WINDOW_SLACK past that stays far below 2^32 -- checked here, not assumed: a larger window takes the per-cell path)
+    const bool regular = st.regular[0] && a.force_irregular != 1 && rg_part_listed(a, st.qslot, p) &&
+                         (unsigned long long)a.g.pitch * (unsigned long long)a.g.win_w < (1ull << 31);
     if (regular) {
         const int k_lo = p * NW, k_hi = min(nt, k_lo + NW);
         const int nreg = a.nrx * a.nry;
         for (int i = tid; i < (YM_RG_LDS_BYTES - YM_RG_ZERO) / 4; i += NT) reinterpret_cast<uint32_t *>(region + YM_RG_ZERO)[i] = 0u;
-        // the regions in which a patch of this block's angles starts
-        if (wave == 0) {
-            int n = 0;
-            for (int R0 = 0; R0 < nreg; R0 += 64) {
-                const int R = R0 + lane;
-                const bool has = R < nreg && starts[(size_t)R * NW] != starts[(size_t)R * NW + (k_hi - k_lo)];
-                const unsigned long long mask = __ballot(has);
-                const int at = n + __popcll(mask & ((1ull << lane) - 1ull)); // (its place among the regions with work)
-                if (has && at % rsplit == rsi) rlist[at / rsplit] = R;
-                n += __popcll(mask);
-            }
-            if (lane == 0) rcount = n > rsi ? (n - rsi + rsplit - 1) / rsplit : 0;
-        }
-        __syncthreads();
-        const int nlist = rcount;
-        {
-            // what this block's patches read of a listed region: rows rmin .. rmax + ny - 1, bytes (xmin & ~3) .. xmax + 15 (+ 13 for
-            // the second half of a lattice row)
-            const uint32_t *rb = a.rbox + (size_t)st.qslot * a.rbox_stride;
-            const uint32_t reach = (uint32_t)(nx > YM_RG_G ? 15 + YM_RG_G : 15);
-            for (int i = tid; i < nlist; i += NT) {
-                const uint32_t v = rb[(size_t)rlist[i] * a.parts + p];
-                const uint32_t r0 = v & 0xffu, r1 = min((uint32_t)(YM_RG_ROWS - 1), ((v >> 8) & 0xffu) + (uint32_t)ny - 1u);
-                const uint32_t s0 = ((v >> 16) & 0xfcu) >> 4, s1 = min((uint32_t)(YM_RG_SEGS - 1), ((v >> 24) + reach) >> 4);
-                rboxl[i] = r0 | r1 << 8 | s0 << 16 | s1 << 24;
-            }
-        }
-        if (kvalid)
-            for (int i = lane; i < nlist; i += 64) {
-                const int32_t *srow = starts + (size_t)rlist[i] * NW + wave;
-                seginfo[wave][i][0] = (unsigned short)srow[0]; seginfo[wave][i][1] = (unsigned short)srow[1];
-            }
-        __syncthreads();
         // Copy tasks.  A thread owns one 16-byte segment `seg` of the rows r0, r0 + RSTEP, ... of ONE class image: its source
         // and LDS offsets are a base plus a constant stride per task (two registers instead of one per task), and whether a
-        // task lies inside the box a region's patches read (`bx`: first row | last row << 8 | first segment << 16 | last << 24,
-        // wave-uniform, rboxl) is one segment test per region and two row compares per task.
+        // task lies inside the box a region's patches read (`bx`, wave-uniform: row [0] of the round table) is one segment test
+        // per region and one bit test per task.
         // Nothing is range-checked against the window: rows past it and blocks past a plane row are other bytes of the planes
         // buffer (the host allocates YM_RG_PLANES_SLACK bytes past the last item), and no patch the window holds reads them.
         // (WIN: a thread owns one 16-byte segment of a WINDOW row -- eight class bytes of each column parity -- of one row parity:
@@ -581,6 +555,47 @@ __global__ __launch_bounds__(64 * NW, NW <= 8 ? (3 * NW + 3) / 4 : 1 /* three bl
         constexpr int LPS = TPC / NSEG;                   // rows the threads of a class cover at once
         constexpr int RSTEP = LPS;
         static_assert(LPS >= 1 && LPS * PER >= YM_RG_ROWS, "the copy tasks must cover a class image");
+        static_assert(PER <= 16 && 2 * YM_RG_SEGS + 1 <= 255, "a box word holds a bit per copy task and two 8-bit segment numbers");
+        // The round table, by wave 0 in one pass over the regions: a lane takes a region, finds out from its NW + 1 bin starts
+        // whether a patch of this block's angles starts in it, and if so -- and if the region is this block's of the rsplit that
+        // share the list -- writes the row: the box from the pair lists' rbox (rmin | rmax << 8 | xmin << 16 | xmax << 24), the
+        // region's row and column (the only division by nrx of this kernel) as a byte offset, the eight waves' segments.
+        if (wave == 0) {
+            const uint32_t *rb = a.rbox + (size_t)st.qslot * a.rbox_stride;
+            // what this block's patches read of a listed region: rows rmin .. rmax + ny - 1, bytes (xmin & ~3) .. xmax + 15 (+ 13 for
+            // the second half of a lattice row)
+            const uint32_t reach = (uint32_t)(nx > YM_RG_G ? 15 + YM_RG_G : 15);
+            int n = 0;
+            for (int R0 = 0; R0 < nreg; R0 += 64) {
+                const int R = R0 + lane;
+                const int32_t *srow = starts + (size_t)(R < nreg ? R : 0) * NW;
+                int32_t sv[NW + 1];
+#pragma unroll
+                for (int w = 0; w <= NW; w++) sv[w] = srow[w];
+                const bool has = R < nreg && sv[0] != srow[k_hi - k_lo];
+                const unsigned long long mask = __ballot(has);
+                const int at = n + __popcll(mask & ((1ull << lane) - 1ull)); // (its place among the regions with work)
+                if (has && at % rsplit == rsi) {
+                    uint32_t *trow = rtab[at / rsplit];
+                    const uint32_t v = rb[(size_t)R * a.parts + p];
+                    const uint32_t r0 = v & 0xffu, r1 = min((uint32_t)(YM_RG_ROWS - 1), ((v >> 8) & 0xffu) + (uint32_t)ny - 1u);
+                    const uint32_t s0 = ((v >> 16) & 0xfcu) >> 4, s1 = min((uint32_t)(YM_RG_SEGS - 1), ((v >> 24) + reach) >> 4);
+                    // task q of every thread is one of the rows q * RSTEP .. + RSTEP - 1: the bands from r0's to r1's
+                    const uint32_t bands = (2u << (r1 / RSTEP)) - (1u << (r0 / RSTEP));
+                    trow[0] = (bands & 0xffffu) | (WIN ? 2u * s0 : s0) << 16 | (WIN ? 2u * s1 + 1u : s1) << 24;
+                    const uint32_t RX = (uint32_t)(R % a.nrx), RY = (uint32_t)(R / a.nrx);
+                    trow[1] = WIN ? (2u * RY * YM_RG_H) * (uint32_t)a.g.pitch + RX * (2u * YM_RG_W)
+                                  : (2u * RY * YM_RG_H) * (uint32_t)half_pitch + RX * YM_RG_W;
+#pragma unroll
+                    for (int w = 0; w < NW; w++) // (a wave past the last angle gathers nothing)
+                        trow[2 + w] = k_lo + w < nt ? ((uint32_t)sv[w] & 0xffffu) | (uint32_t)sv[w + 1] << 16 : 0u;
+                }
+                n += __popcll(mask);
+            }
+            if (lane == 0) rcount = n > rsi ? (n - rsi + rsplit - 1) / rsplit : 0;
+        }
+        __syncthreads();
+        const int nlist = __builtin_amdgcn_readfirstlane(rcount);
         const uint32_t cls = WIN ? 2u * ((uint32_t)tid / TPC) : (uint32_t)tid / TPC, j = (uint32_t)tid % TPC;
         const uint32_t seg = j % NSEG, r0 = j / NSEG;
         const bool copier = j < (uint32_t)(LPS * NSEG);
@@ -589,42 +604,34 @@ __global__ __launch_bounds__(64 * NW, NW <= 8 ? (3 * NW + 3) / 4 : 1 /* three bl
         const uint32_t src_step = WIN ? 2u * RSTEP * (uint32_t)a.g.pitch : 2u * RSTEP * (uint32_t)half_pitch;
         const uint32_t dst0 = (cls * YM_RG_ROWS + r0) * YM_RG_PITCH + (WIN ? 8u : 16u) * seg;
         uint4 v[PER];
-        auto in_box = [&](int q, uint32_t bx, bool seg_in) {
-            (void)q; (void)bx;
-            return seg_in; // (rows: whole bands, see band_in -- a per-lane row test costs more vector instructions than the rows it saves)
-        };
-        // task q of every thread is one of the rows q * RSTEP .. + RSTEP - 1: a band the box does not reach is skipped by the
-        // whole block (a scalar branch: no load or store instruction is issued for it)
-        auto band_in = [&](int q, uint32_t bx) {
-            return (uint32_t)(q * RSTEP) <= ((bx >> 8) & 0xffu) && (uint32_t)(q * RSTEP + RSTEP - 1) >= (bx & 0xffu);
-        };
-        const uint8_t *__restrict__ window = a.grid + (size_t)b * a.grid_stride;
-        // (the box names 16-byte segments of a class row; a window segment holds eight class bytes of each parity)
-        auto seg_inside = [&](uint32_t bx) {
-            return WIN ? copier && seg >= 2u * ((bx >> 16) & 0xffu) && seg <= 2u * (bx >> 24) + 1u
-                       : copier && seg >= ((bx >> 16) & 0xffu) && seg <= (bx >> 24);
-        };
-        auto stage_load = [&](int R, uint32_t bx) {
-            const int RX = R % a.nrx, RY = R / a.nrx;
-            const uint8_t *src = WIN ? window + ((size_t)(2 * RY * YM_RG_H) * a.g.pitch + (size_t)RX * (2 * YM_RG_W))
-                                     : planes + ((size_t)(2 * RY * YM_RG_H) * half_pitch + (size_t)RX * YM_RG_W); // (wave-uniform)
-            const bool seg_in = seg_inside(bx);
-            // (a task outside the box loads the region's first bytes -- one line for all of them -- and stores nothing; a load
-            //  under a per-lane predicate costs the kernel 28 bytes of scratch per lane and is slower)
+        // a band the box does not reach is skipped by the whole block (a scalar branch on the band's bit: no load or store
+        // instruction is issued for it); inside a band the rows are not tested -- a per-lane row test costs more vector
+        // instructions than the rows it saves
+        auto band_in = [&](int q, uint32_t bx) { return (bx >> q & 1u) != 0u; };
+        auto seg_inside = [&](uint32_t bx) { return copier && seg >= ((bx >> 16) & 0xffu) && seg <= (bx >> 24); };
+        const uint8_t *__restrict__ source = WIN ? a.grid + (size_t)b * a.grid_stride : planes;
+        // The loads of a region: a wave-uniform 64-bit base (the item's window + the region's offset: two scalar adds per round)
+        // and a 32-bit offset per lane and task -- the global load's scalar-base form, no 64-bit vector arithmetic.
+        auto stage_load = [&](uint32_t region_off, uint32_t bx) {
+            const uint8_t *src = source + region_off; // (wave-uniform)
+            // (a thread whose segment is outside the box loads the first bytes of its task's row -- one line per task for all of
+            //  them, a line the box's own lanes read too -- and stores nothing; a load under a per-lane predicate costs the kernel
+            //  28 bytes of scratch per lane and is slower)
+            const uint32_t off0 = seg_inside(bx) ? src0 : 0u;
 #pragma unroll
             for (int q = 0; q < PER; q++)
 #if YM_RG_ABLATE & 2
-                v[q] = make_uint4((uint32_t)(size_t)src, seg_in, bx, q);
+                v[q] = make_uint4((uint32_t)(size_t)src, off0, bx, q);
 #else
-                if (band_in(q, bx)) v[q] = *reinterpret_cast<const uint4 *>(src + (in_box(q, bx, seg_in) ? src0 + (uint32_t)q * src_step : 0u));
+                if (band_in(q, bx)) v[q] = *reinterpret_cast<const uint4 *>(src + (off0 + (uint32_t)q * src_step));
 #endif
         };
         auto stage_store = [&](uint32_t bx) {
-            const bool seg_in = seg_inside(bx);
+            if (!seg_inside(bx)) return; // (one change of the execution mask for all tasks; the bands are scalar branches inside it)
 #pragma unroll
             for (int q = 0; q < PER; q++) {
                 uint32_t *d = reinterpret_cast<uint32_t *>(region + dst0 + (uint32_t)(q * RSTEP * YM_RG_PITCH)); // class images are contiguous
-                if (band_in(q, bx) && in_box(q, bx, seg_in) && (!(YM_RG_ABLATE & 4) || v[q].x == 0x12345u)) {
+                if (band_in(q, bx) && (!(YM_RG_ABLATE & 4) || v[q].x == 0x12345u)) {
                     if (WIN) { // even window columns -> this image, odd ones -> the next
                         d[0] = __builtin_amdgcn_perm(v[q].y, v[q].x, 0x06040200u); d[1] = __builtin_amdgcn_perm(v[q].w, v[q].z, 0x06040200u);
                         d[YM_RG_CLS / 4] = __builtin_amdgcn_perm(v[q].y, v[q].x, 0x07050301u); d[YM_RG_CLS / 4 + 1] = __builtin_amdgcn_perm(v[q].w, v[q].z, 0x07050301u);
@@ -632,23 +639,28 @@ __global__ __launch_bounds__(64 * NW, NW <= 8 ? (3 * NW + 3) / 4 : 1 /* three bl
                 }
             }
         };
-        // this wave's entries of a region: [t0, t2) (a multiple of four entries)
-        auto segment = [&](int ri, int &t0, int &t2) {
-            t0 = t2 = 0;
-            if (kvalid) {
-                t0 = __builtin_amdgcn_readfirstlane((int)seginfo[wave][ri][0]);
-                t2 = __builtin_amdgcn_readfirstlane((int)seginfo[wave][ri][1]);
-            }
+        // What a wave reads of the round table for one round, in ONE LDS instruction: lane 0 the box of row r, lane 1 its source
+        // offset, every other lane the wave's own segment of row r + 1 (three addresses: two broadcasts and a bank of its own).
+        // The caller takes the three out with v_readlane once the read is back; rows past the list hold nothing and are not used
+        // (the index stays inside the table).
+        auto row_read = [&](int r) {
+            const uint32_t rr = (uint32_t)min(r + (lane >= 2 ? 1 : 0), YM_RG_MAX_REGIONS - 1);
+            return (&rtab[0][0])[__umul24(rr, 2u + NW) + (uint32_t)(lane < 2 ? lane : 2 + wave)];
         };
-        // The first 256 entries of a wave's segment travel like the region itself: loaded into a register pair while the previous
-        // region is gathered (ev), handed over between the barriers (cev), read from there lane by lane (v_readlane).
+        // this wave's entries of a region: [t0, t2) (a multiple of four entries), from its word of the table; none past the list
+        auto segment = [&](uint32_t word, bool listed, int &t0, int &t2) {
+            t0 = listed ? (int)(word & 0xffffu) : 0;
+            t2 = listed ? (int)(word >> 16) : 0;
+        };
+        // The first 256 entries of a wave's segment travel like the region itself, one round further ahead: loaded into a register
+        // pair while the region before the previous one is gathered (ev2), moved up between the barriers of each round (ev, then
+        // cev), read from cev lane by lane (v_readlane).  A load two rounds old has long arrived when it is first read: its wait
+        // is over before the staging loads issued after it are waited for.
         // No vector-memory wait inside the gather: that would also wait for the staging loads in flight.
+        // (A lane past the segment's end loads the list's first element: no branch, no register zeroed under a load in flight.)
         const uint2 *__restrict__ entries4 = reinterpret_cast<const uint2 *>(entries); // four entries per element
-        uint2 ev = make_uint2(0u, 0u), cev = make_uint2(0u, 0u);
-        auto entries_load = [&](int t0, int t2) {
-            ev = make_uint2(0u, 0u);
-            if (t0 + 4 * lane < t2) ev = entries4[(t0 >> 2) + lane];
-        };
+        auto entries_load = [&](int t0, int t2) { return entries4[t0 + 4 * lane < t2 ? (t0 >> 2) + lane : 0]; };
+        uint2 cev = make_uint2(0u, 0u), ev = make_uint2(0u, 0u);
         auto gather = [&](int lo, int hi) { // entries [lo, hi)
             const int lds_hi = min(hi, lo + 256);
 #if YM_RG_PRIO
@@ -692,40 +704,43 @@ __global__ __launch_bounds__(64 * NW, NW <= 8 ? (3 * NW + 3) / 4 : 1 /* three bl
             __builtin_amdgcn_s_setprio(0);
 #endif
         };
-        int s0 = 0, s2 = 0;
+        // The walk is a pipeline three rounds deep.  Round ri gathers region ri from LDS and its entries from cev, while in
+        // registers: region ri + 1 (v, loaded this round) and its entries (ev, loaded a round ago), the entries of region ri + 2
+        // (ev2, loaded this round), and the table words of the round to come (tv, read after the gather: the barrier's own wait
+        // covers it, the top of a round waits for no LDS read).
+        int s0 = 0, s2 = 0, n0 = 0, n2 = 0; // the wave's segment of the region being gathered and of the next one
+        uint32_t tv = 0u;                   // row_read(ri + 1): box and source of region ri + 1, segment of region ri + 2
         if (nlist > 0) {
-            const uint32_t bx = __builtin_amdgcn_readfirstlane(rboxl[0]);
-            segment(0, s0, s2);
-            entries_load(s0, s2);
-            stage_load(rlist[0], bx);
+            const uint32_t t = row_read(0);
+            segment(__builtin_amdgcn_readfirstlane(rtab[0][2 + wave]), true, s0, s2);
+            segment(__builtin_amdgcn_readlane(t, 2), 1 < nlist, n0, n2);
+            const uint32_t bx = __builtin_amdgcn_readlane(t, 0);
+            cev = entries_load(s0, s2);
+            ev = entries_load(n0, n2);
+            stage_load(__builtin_amdgcn_readlane(t, 1), bx);
             stage_store(bx);
-            cev = ev;
+            tv = row_read(1);
         }
         __syncthreads();
         YM_RG_PH(0);
         for (int ri = 0; ri < nlist; ri++) {
-            // two-stage pipeline: the global loads of the next region are in flight (registers) while this one is gathered
             const bool has_next = ri + 1 < nlist;
-            int n0 = 0, n2 = 0;
-            uint32_t nbx = 0u;
-            if (has_next) {
-                nbx = __builtin_amdgcn_readfirstlane(rboxl[ri + 1]);
-                segment(ri + 1, n0, n2);
-                YM_RG_PH(7);
-                entries_load(n0, n2);
-                YM_RG_PH(8);
-                stage_load(rlist[ri + 1], nbx);
-            }
+            const uint32_t nbx = __builtin_amdgcn_readlane(tv, 0), nsrc = __builtin_amdgcn_readlane(tv, 1);
+            int f0, f2; // the wave's segment of region ri + 2
+            segment(__builtin_amdgcn_readlane(tv, 2), ri + 2 < nlist, f0, f2);
+            YM_RG_PH(7);
+            const uint2 ev2 = entries_load(f0, f2);
+            YM_RG_PH(8);
+            if (has_next) stage_load(nsrc, nbx);
             YM_RG_PH(1);
             gather(s0, s2);
             YM_RG_PH(2);
+            tv = row_read(ri + 2);
             __syncthreads(); // every wave is done with region ri
             YM_RG_PH(3);
-            if (has_next) {
-                stage_store(nbx);
-                cev = ev;
-            }
-            s0 = n0; s2 = n2;
+            if (has_next) stage_store(nbx);
+            cev = ev; ev = ev2;
+            s0 = n0; s2 = n2; n0 = f0; n2 = f2;
             YM_RG_PH(4);
             __syncthreads();
             YM_RG_PH(5);
