@@ -165,11 +165,12 @@ def test_batch_matches_single_calls():
     assert best == int(np.argmax([s.response for s in singles]))
 
 
-@pytest.mark.parametrize("finish_form", [0, 1])
-def test_large_batch_matches_single_calls(finish_form):
+@pytest.mark.parametrize("finish_form,finish_threads", [(1, 0), (2, 1024), (2, 256)])
+def test_large_batch_matches_single_calls(finish_form, finish_threads):
     """Batches of 8 or more items take different kernels than a single match (256-thread prepare blocks, the raster's
-    tile work list, the one-block finish kernel; option 6 = 1 forces the per-angle fine/final pair): every result
-    must still be the single call's, bit for bit -- penalty, refinement, ragged and empty chains included."""
+    tile work list) and, from 128 items on, the one-block finish kernel: option 6 = 2 forces it on these 11 items, in both
+    of its block sizes (option 11); option 6 = 1 forces the per-angle fine/final pair.  Every result must still be the
+    single call's, bit for bit -- penalty, refinement, ragged and empty chains included."""
     from yag_slam_amd.scan_matching import ScanMatcher
     from yag_slam_amd import synth
     scene = synth.Scene()
@@ -182,6 +183,7 @@ def test_large_batch_matches_single_calls(finish_form):
     chains = [nb, nb[:3], nb[2:9], far[1], [], nb[::-1], far[2], nb[4:5], far[3], nb[1:], far[4]]
     m = ScanMatcher()
     m.debug_option(6, finish_form)
+    m.debug_option(11, finish_threads)  # (the single calls below take the pair whatever this says)
     for pen, fine in ((True, True), (False, False)):
         per, best = m.match_scan_batch(nq, chains, pen, fine)
         m.debug_option(6, 0)

@@ -184,7 +184,8 @@ struct FinishArgs {
 
 // sum N doubles across the block in one round (2 barriers); result in every thread
 // Floating-point sums that reach the result (tie means, covariances) are accumulated by the first YM_CANON threads
-// only, element e by thread e % YM_CANON in increasing e: the kernels that share this code run with 256, 512 or 1024
+// only, element e by thread e % YM_CANON in increasing e (coarse ties: cell e of each score block, the blocks in
+// ascending order): the kernels that share this code run with 256, 512 or 1024
 // threads and must produce the same bits.  (block_sum_vec adds the waves in order; idle waves contribute exact zeros.)
 #define YM_CANON 256
 template <int N>
@@ -252,7 +253,6 @@ __device__ __forceinline__ double coarse_best_and_mean(const YmLattice &L, const
                                                        int *s_nlist, double2 *s_trig /* L.nt */,
                                                        const double *first_round = nullptr /* [KEEP]: bm[tid + u * NT] or -1, loaded by the caller */) {
     const int tid = threadIdx.x;
-    const int nh = L.nx * L.ny * L.nt;
     const double start_angle = pose[2] - L.angle_off;
     if (tid == 0) *s_nlist = 0;
     double lb = -1.0;
@@ -296,21 +296,22 @@ __device__ __forceinline__ double coarse_best_and_mean(const YmLattice &L, const
         }
         __syncthreads();
     }
+    // One rule for who adds what, whatever NT is and whether the list held: canonical thread t takes cell t of every
+    // candidate block, the blocks in ascending order.  (The walk over ALL blocks below visits the candidates in that order
+    // too, and a block that is none holds no tie and adds nothing: the same additions in the same threads and order.  A walk
+    // over the hypotheses h = t, t + 256, ... would be another grouping wherever nx * ny is no multiple of 256, and the
+    // kernels that share this code have lists of 256, 512 and 1024 entries: one tie set overflows in some of them only.)
     double acc[5] = {0, 0, 0, 0, 0};
     if (tid < YM_CANON) {
-        if (!overflow) {
-            const int nlist = *s_nlist;
-            const int *list = nlist > 1 ? s_list : s_tmp;
-            const int nxy = L.nx * L.ny, ncb = (nxy + YM_SCORE_THREADS - 1) / YM_SCORE_THREADS;
-            for (int w = tid; w < nlist * YM_SCORE_THREADS; w += YM_CANON) {
-                const int bid = list[w / YM_SCORE_THREADS]; // block = (angle k, block cb of cells)
-                const int k = bid / ncb, c = (bid - k * ncb) * YM_SCORE_THREADS + (w % YM_SCORE_THREADS);
-                const int h = k * nxy + c;
-                if (c < nxy && kt_double_equal(resp[h], best)) tie_accumulate(acc, L, h, pose[0], pose[1], s_trig);
-            }
-        } else {
-            for (int h = tid; h < nh; h += YM_CANON)
-                if (kt_double_equal(resp[h], best)) tie_accumulate(acc, L, h, pose[0], pose[1], s_trig);
+        static_assert(YM_CANON == YM_SCORE_THREADS, "one canonical thread per cell of a score block");
+        const int nxy = L.nx * L.ny, ncb = (nxy + YM_SCORE_THREADS - 1) / YM_SCORE_THREADS;
+        const int nlist = overflow ? n_blocks : *s_nlist;
+        const int *list = nlist > 1 ? s_list : s_tmp;
+        for (int j = 0; j < nlist; j++) {
+            const int bid = overflow ? j : list[j]; // block = (angle k, block cb of cells)
+            const int k = bid / ncb, c = (bid - k * ncb) * YM_SCORE_THREADS + tid;
+            const int h = k * nxy + c;
+            if (c < nxy && kt_double_equal(resp[h], best)) tie_accumulate(acc, L, h, pose[0], pose[1], s_trig);
         }
     }
     block_sum_vec_sparse<5>(acc, scratch, acc[4] != 0.0);
