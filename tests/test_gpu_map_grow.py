@@ -177,6 +177,47 @@ def test_many_readings_in_one_cell():
     m.close()
 
 
+def test_one_uncounted_add_of_more_scans_than_two_chunks():
+    """4097 scans of 4 beams (a launch takes 4096, so the second chunk is the last scan alone) in one add_scans call into a map that
+    keeps no counts.  The scans stand on the 17 x 15 lattice of poses of tests/test_gpu_map_forget.py's chunk test and reach 5 to 9
+    cells, so they share a few hundred cells and the restatement is quick."""
+    from yag_slam_amd import models
+    from yag_slam_amd.scan_matching import ScanMatcher
+    _, res, smear, taps, w, h = CONFIGS[0]
+    m = ScanMatcher(dict(resolution=res, smear_deviation=smear, range_threshold=12.0), semantics="yagpy")
+    kernel = R.calculate_kernel(res, smear)
+    assert kernel.shape == (taps, taps) == (5, 5)
+    ox, oy = -0.513 * res / 0.05, 0.237 * res / 0.05
+    cx, cy = ox + 0.5 * w * res, oy + 0.5 * h * res
+    rng = np.random.default_rng(29)
+    n = 4097
+    scans = []
+    for i in range(n):
+        px, py = cx + ((i % 17) - 8.0 + 0.37) * 0.9 * res, cy + ((i // 17 % 15) - 7.0 + 0.29) * 0.9 * res
+        reach = (5.0, 9.0) if i < n - 1 else (11.0, 13.0)
+        scans.append(_scan(rng.uniform(reach[0], reach[1], 4) * res, (px, py, 0.7 * (i % 9))))
+    _guard(scans, ox, oy, res)
+    # the last scan, which is the second chunk, reaches further than the others and puts cells into the map that no other scan
+    # stamps: a second chunk that is skipped, or staged from the wrong place in the list, shows in the map and not only in the counts
+    want, (points, stamped, dropped, cells) = R.build((h, w), kernel, scans, ox, oy, res)
+    assert (points, stamped, dropped) == (4 * n, 4 * n, 0)
+    assert set(cells[-4:]) - set(cells[:-4]), "the last scan stamps no cell of its own: pick another seed"
+    models.native_many(scans, m.device)
+    plain = m.empty_correlation_map(w, h)
+    st = plain.add_scans(ox, oy, scans)
+    assert (st.points, st.stamped, st.dropped) == (points, stamped, dropped)
+    got = plain.to_numpy()
+    _assert_equals_restatement(got, want)
+    changed = np.argwhere(got != 0)
+    assert st.x0 <= changed[:, 1].min() and changed[:, 1].max() < st.x1 and st.y0 <= changed[:, 0].min() and changed[:, 0].max() < st.y1
+    counted = m.empty_correlation_map(w, h, counted=True, ox=ox, oy=oy)
+    counted.add_scans(ox, oy, scans)
+    assert np.array_equal(got, counted.to_numpy())
+    counted.close()
+    plain.close()
+    m.close()
+
+
 def test_adding_onto_an_uploaded_map_keeps_higher_values_and_raises_lower_ones(ctx):
     c = ctx
     half = c.taps // 2

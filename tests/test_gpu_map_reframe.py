@@ -370,3 +370,101 @@ def test_a_scrolling_windowed_builder_walks_the_room_exactly_as_one_on_a_map_of_
     big.close()
     cm.close()
     m.close()
+
+
+# ---- more rows than one launch has rows of blocks -------------------------------------------------------------------------------
+TALL_W, TALL_H = 8, 4 * 65535 + 69  # 262 209 rows: the mark runs in five pieces of 65 535 rows, the gather (tiles of 4 rows) in two
+TALL_BANDS = ((0, 6), (65534, 65538), (262138, 262144), (TALL_H - 4, TALL_H))  # [first, last) rows: each holds stamped cells
+
+
+class _Tall(object):
+    pass
+
+
+@pytest.fixture(scope="module")
+def tall():
+    """the 5 x 5 tap configuration, a map 8 cells wide and 262 209 high, and six scans of 12 beams that look along +y and reach
+    half a cell to five cells: their poses put stamped cells on the first rows, on both sides of the seam between the mark's first
+    two pieces (row 65 535), on both sides of the seam between the gather's two pieces (row 262 140) and on the last rows.  The
+    scans stand near the east side, so that some readings lie beyond it and a scroll by one column has something to stamp."""
+    from yag_slam_amd.scan_matching import ScanMatcher
+    from tests.test_gpu_map_grow import CONFIGS, INC, MIN_ANGLE
+    from tests import mapforget_ref as F
+    _, res, smear, taps, _, _ = CONFIGS[0]
+    t = _Tall()
+    t.res, t.taps, t.w, t.h = res, taps, TALL_W, TALL_H
+    t.kernel = R.calculate_kernel(res, smear)
+    assert t.kernel.shape == (5, 5)
+    t.ox, t.oy = -0.513, 0.237
+    n = 12
+    heading = 0.5 * math.pi - MIN_ANGLE - 0.5 * (n - 1) * INC  # the fan's middle beam points along +y
+    rng = np.random.default_rng(31)
+    t.ranges, t.poses = [], []
+    for row in (0.3, 65532.3, 65534.6, 262136.3, 262139.4, TALL_H - 4.6):
+        t.ranges.append(rng.uniform(0.5, 5.0, n) * res)
+        t.poses.append((t.ox + 6.4 * res, t.oy + row * res, heading))
+    t.fresh_scans = lambda: [_scan(r, p) for r, p in zip(t.ranges, t.poses)]
+    scans = t.fresh_scans()
+    _guard(scans, t.ox, t.oy, res)
+    t.cells = [F.cells_of([s], (t.h, t.w), t.ox, t.oy, res) for s in scans]
+    rows = set(gy for v in t.cells for _, gy in v)
+    for lo, hi in TALL_BANDS:
+        assert rows & set(range(lo, hi)), (lo, hi)
+    assert {65534, 65535} & rows and {65536, 65537} & rows and {262138, 262139} & rows and {262140, 262141, 262142, 262143} & rows
+    assert (TALL_H - 1) in rows and min(rows) <= 3
+    cols = set(gx for v in t.cells for gx, _ in v)
+    assert {5, 6, 7} <= cols and all(len(v) < n for v in t.cells[:1] + t.cells[-1:])  # (the first and last scans: readings beyond the east side or the top)
+    t.m = ScanMatcher(dict(resolution=res, smear_deviation=smear, range_threshold=12.0), semantics="yagpy")
+    yield t
+    t.m.close()
+
+
+def _tall_map(t, scans, window=(0, 0)):
+    cm = t.m.empty_correlation_map(t.w, t.h, counted=True, ox=t.ox, oy=t.oy, window=window)
+    cm.add_scans(cm.origin[0], cm.origin[1], scans)
+    return cm
+
+
+def test_a_removal_whose_released_box_spans_more_tile_rows_than_one_launch_takes(tall):
+    """the first and the last scan go in one call: the released box runs from the first rows to the last, 65 553 rows of tiles, and
+    the gather takes it in two launches"""
+    from tests import mapforget_ref as F
+    t = tall
+    scans = t.fresh_scans()
+    cm = _tall_map(t, scans)
+    st = cm.remove_scans([scans[0], scans[-1]])
+    gone = t.cells[0] + t.cells[-1]
+    assert (st.removed, st.unmatched) == (len(gone), 0) and st.released > 0 and len(cm) == 4
+    assert st.y0 <= 3 and st.y1 == t.h and (st.y1 - st.y0 + 3) // 4 > 65535
+    got, stamps = cm.to_numpy(), cm.stamps()
+    fresh = _tall_map(t, [_clone(s) for s in scans[1:-1]])
+    assert np.array_equal(got, fresh.to_numpy()) and np.array_equal(stamps, fresh.stamps())
+    fresh.close()
+    counts = F.counts_of((t.h, t.w), [x for v in t.cells[1:-1] for x in v])
+    assert np.array_equal(stamps.astype(np.int64), counts)
+    want = F.from_counts(counts, t.kernel)
+    half = t.taps // 2
+    for lo, hi in TALL_BANDS:  # the bands, and what the taps reach from them
+        lo, hi = max(0, lo - half), min(t.h, hi + half)
+        _assert_equals_restatement(got[lo:hi], want[lo:hi])
+    assert not got[:8].any() and not got[-8:].any() and got[65530:65545].any() and got[262134:262150].any()
+    cm.close()
+
+
+def test_a_scroll_by_one_column_of_a_map_with_more_rows_than_one_launch_takes(tall):
+    """reframe(1, 0): the overlap is seven columns of every row, so the mark covers all 262 209 rows in five launches and the gather
+    all 65 553 rows of tiles in two; column 7 of the new window comes from the counts and from the readings the old one dropped"""
+    t = tall
+    scans = t.fresh_scans()
+    cm = _tall_map(t, scans)
+    st = cm.reframe(1, 0)
+    assert (st.kept, st.mismatch) == (7 * t.h, 0) and st.restamped > 0 and st.recomputed > t.h
+    assert cm.window == (1, 0, t.w, t.h) and cm.anchor == (t.ox, t.oy)
+    got, stamps = cm.to_numpy(), cm.stamps()
+    fresh = _tall_map(t, [_clone(s) for s in scans], window=(1, 0))
+    assert fresh.window == cm.window and fresh.origin == cm.origin
+    assert np.array_equal(got, fresh.to_numpy()) and np.array_equal(stamps, fresh.stamps())
+    fresh.close()
+    for lo, hi in TALL_BANDS:
+        assert got[max(0, lo - 2):hi + 2, 7].any(), (lo, hi)  # the new column holds values in and around every band
+    cm.close()

@@ -391,3 +391,22 @@ class _PlainWindowStub(_PlainStubMap):
         self.shape = (self.shape[0] if height is None else height, self.shape[1] if width is None else width)
         self.log.append(("reframe", dx, dy) + self.shape[::-1])
         self.revision += 1
+
+
+# ---- the window's integer arithmetic under the sanitizers, as a program of its own
+def test_map_window_arithmetic_under_the_sanitizers(tmp_path):
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no C++ compiler"
+    exe = str(tmp_path / "map_window_check")
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wextra", "-Werror",
+           "-I", os.path.join(REPO, "yag_slam_amd", "csrc"), "-o", exe, os.path.join(REPO, "tests", "native", "map_window_check.cpp")]
+    # the sanitizers' runtimes inside the program (gcc's spelling, then clang's): it runs whatever else the process environment loads
+    for static in (["-static-libasan", "-static-libubsan"], ["-static-libsan"]):
+        built = subprocess.run(cmd + static, capture_output=True, text=True)
+        if built.returncode == 0:
+            break
+    assert built.returncode == 0, built.stderr[-2000:]
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-2000:])
+    words = run.stdout.split()
+    assert words[0] == "ok" and int(words[1]) > 100000

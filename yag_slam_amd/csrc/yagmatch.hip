@@ -23,6 +23,7 @@
 #include "../../include/yagmatch.h"
 #include "ym_kernels.hpp"
 #include "ym_occlive_window.hpp" // the live occupancy grid's window arithmetic (no HIP in it)
+#include "ym_map_window.hpp"     // a correlation map's window arithmetic (no HIP in it)
 
 // The host runtime in units (one translation unit: the kernels are templates and inline functions of ym_kernels.hpp):
 #include "ym_host_types.hpp"    // error text, device guard, buffers, Call / CallPlan / Slot
@@ -34,6 +35,8 @@ namespace {
 #include "ym_host_plan.hpp"     // the planner of one call
 #include "ym_host_enqueue.hpp"  // the launches of one call
 #include "ym_host_call.hpp"     // launch, collect, scans -> call descriptors
+#include "ym_host_mapgrow.hpp"  // what the calls that change a resident correlation map share
+#include "ym_host_mapscore.hpp" // the scoring tail of the map and set matchers
 }  // namespace
 
 // =================================================================== C ABI (include/yagmatch.h)
@@ -42,6 +45,7 @@ extern "C" {
 #include "ym_abi_scans.hpp"
 #include "ym_abi_match.hpp"
 #include "ym_abi_maps.hpp"
+#include "ym_abi_occupancy.hpp"
 #include "ym_abi_occlive.hpp"
 #include "ym_abi_maptrack.hpp"
 #include "ym_abi_sets.hpp"

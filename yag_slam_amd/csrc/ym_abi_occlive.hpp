@@ -1,5 +1,5 @@
 // ym_abi_occlive.hpp -- C ABI: the live occupancy grid (ym_occmap_*; kernels in ym_k_occupancy.hpp and their launch helpers in
-// ym_abi_maps.hpp, both shared with the full renderer; window and growth arithmetic in ym_occlive_window.hpp)
+// ym_abi_occupancy.hpp, both shared with the full renderer; window and growth arithmetic in ym_occlive_window.hpp)
 // Part of yagmatch.hip (included inside its extern "C" block); not a header of its own.
 // Everything runs on the null stream and every entry returns with its work complete, like occupancy_render: a scan may be destroyed
 // as soon as the call that read it has returned.

@@ -27,47 +27,34 @@ int ym_match_sets_many(ym_matcher *m, const ym_scan *const *queries, const int32
     const double res = m->cfg.resolution;
     std::vector<ym::MapItemDesc> items((size_t)n_items);
     std::vector<double> origin((size_t)2 * n_items), view((size_t)2 * n_items);
-    int max_nq = 1, max_nb = 1;
+    int max_nq = 1, max_nb = 1, rc;
     size_t total_pts = 0;
     for (int b = 0; b < n_items; b++) {
         const int lo = set_offsets[b], nq = set_offsets[b + 1] - lo;
-        double sx = 0, sy = 0;
-        int total = 0;
-        for (int i = 0; i < nq; i++) {
-            const ym_scan *q = queries[lo + i];
-            if (!q || q->device != m->device) return set_err(YM_ERR_INVALID, "item %d: query %d is null or lives on another device", b, i);
-            sx = i == 0 ? q->pose[0] : sx + q->pose[0];
-            sy = i == 0 ? q->pose[1] : sy + q->pose[1];
-            total += q->n;
-            max_nq = std::max(max_nq, q->n);
-        }
+        if ((rc = yag_item_desc(m, queries, q0, lo, nq, b, &items[b], &total_pts, &max_nq))) return rc;
         for (int i = chain_offsets[b]; i < chain_offsets[b + 1]; i++) {
             const ym_scan *s = base[i];
             if (!s || s->device != m->device) return set_err(YM_ERR_INVALID, "item %d: base scan %d is null or lives on another device", b, i - chain_offsets[b]);
             max_nb = std::max(max_nb, s->n);
         }
-        items[b].scan_begin = lo - q0; items[b].n_scans = nq;
-        items[b].out_off = (int64_t)total_pts;
-        items[b].ox_real = sx / (double)nq; items[b].oy_real = sy / (double)nq;
         origin[2 * (size_t)b] = items[b].ox_real - 0.5 * (G - 1) * res;
         origin[2 * (size_t)b + 1] = items[b].oy_real - 0.5 * (G - 1) * res;
         view[2 * (size_t)b] = queries[lo + nq - 1]->pose[0];
         view[2 * (size_t)b + 1] = queries[lo + nq - 1]->pose[1];
-        total_pts += (size_t)std::max(total, 1);
     }
     if (max_nq > YM_MAX_BEAMS || max_nb > YM_MAX_BEAMS)
         return set_err(YM_ERR_UNSUPPORTED, "scan has %d readings; limit is %d", std::max(max_nq, max_nb), YM_MAX_BEAMS);
     const int ks = 2 * g.half_kernel + 1;
     if ((double)G * G > 1.0e9) return set_err(YM_ERR_UNSUPPORTED, "a grid of %d x %d cells per item: at most 10^9", G, G);
-    if ((double)max_nb * ks * ks > 2.0e9) return set_err(YM_ERR_UNSUPPORTED, "%d beams x %d x %d taps: more than one launch holds", max_nb, ks, ks);
+    if ((rc = map_launch_limits(max_nb, ks, false))) return rc;
     // find_best_pose's arguments (scan_matching.py:100-108); the padded lattice holds np.arange's lengths of both passes
-    const double c_search = m->cfg.search_size * 0.5, c_step = res * 2;
-    const double c_tsearch = m->cfg.coarse_search_angle_offset * 0.5, c_tstep = m->cfg.coarse_angle_resolution;
-    const int maxd = std::max({8, (int)std::ceil(2 * c_search / c_step) + 2, (int)std::ceil(4 * res / res) + 2});
-    const int maxt = std::max({13, (int)std::ceil(2 * c_tsearch / c_tstep) + 2});
-    if (maxd > YM_YAG_MAX_DIM || maxt > YM_YAG_MAX_NT)
-        return set_err(YM_ERR_UNSUPPORTED, "search lattice %d x %d x %d exceeds the built-in limit", maxd, maxd, maxt);
-    const size_t vol = (size_t)maxt * maxd * maxd;
+    YagBatch S;
+    std::memset(&S, 0, sizeof S);
+    S.coarse.xy_search = m->cfg.search_size * 0.5; S.coarse.xy_step = res * 2;
+    S.coarse.angle_search = m->cfg.coarse_search_angle_offset * 0.5; S.coarse.angle_step = m->cfg.coarse_angle_resolution;
+    S.coarse.grid_resolution = res; S.coarse.penalize = penalize;
+    if ((rc = yag_lattice_bound(S.coarse, res, "", &S.L))) return rc;
+    const size_t vol = S.L.vol;
     const size_t grid_stride = align_up((size_t)G * G + 64, 256);
     const bool keep_all = n_items <= kMapKeepSumsItems;
     int chunk = (int)std::min<size_t>((size_t)n_items, std::max<size_t>(1, kMapBatchScratchBytes / (16 * vol)));
@@ -78,20 +65,12 @@ int ym_match_sets_many(ym_matcher *m, const ym_scan *const *queries, const int32
     std::vector<int32_t> job_begin((size_t)n_items + 1);
     const size_t n_jobs = (size_t)n_bscans;
     DEV_GUARD(m->device);
-    int rc;
     Slot &slot = m->slots[kAsyncSlots];
     if (slot.in_flight) return set_err(YM_ERR_BUSY, "the synchronous slot is in flight");
-    if ((rc = m->states.ensure((size_t)n_items))) return rc;
-    if ((rc = m->map_pts.ensure(total_pts))) return rc;
-    if ((rc = m->yaxes.ensure((size_t)chunk * 3 * YM_YAG_MAX_DIM))) return rc;
-    if ((rc = m->sums.ensure(2 * sums_items * vol))) return rc;
-    if ((rc = m->resp.ensure((size_t)chunk * vol))) return rc;
-    if ((rc = m->sets_grid.ensure((size_t)chunk * grid_stride))) return rc;
-    if ((rc = m->sets_ktab.ensure((size_t)ks * ks))) return rc;
-    if (!m->yag_counters.p) {
-        if ((rc = m->yag_counters.ensure(8))) return rc;
-        HIP_TRY(hipMemsetAsync(m->yag_counters.p, 0, m->yag_counters.cap * sizeof(unsigned long long), m->stream));
-    }
+    if ((rc = m->states.ensure((size_t)n_items)) || (rc = m->map_pts.ensure(total_pts)) || (rc = m->yaxes.ensure((size_t)chunk * 3 * YM_YAG_MAX_DIM)) ||
+        (rc = m->sums.ensure(2 * sums_items * vol)) || (rc = m->resp.ensure((size_t)chunk * vol)) ||
+        (rc = m->sets_grid.ensure((size_t)chunk * grid_stride)) || (rc = m->sets_ktab.ensure((size_t)ks * ks)) || (rc = yag_counters_ensure(m)))
+        return rc;
     const size_t qscans_bytes = align_up(sizeof(YmScanRef) * (size_t)n_qscans, 16);
     const size_t bscans_bytes = align_up(sizeof(YmScanRef) * (size_t)std::max(n_bscans, 1), 16);
     const size_t items_bytes = align_up(sizeof(ym::MapItemDesc) * (size_t)n_items, 16);
@@ -100,9 +79,8 @@ int ym_match_sets_many(ym_matcher *m, const ym_scan *const *queries, const int32
     const size_t ktab_bytes = align_up((size_t)ks * ks, 16);
     const size_t desc_bytes = qscans_bytes + bscans_bytes + items_bytes + view_bytes + jobs_bytes + ktab_bytes;
     const size_t states_bytes = sizeof(YmItemState) * (size_t)n_items;
-    if ((rc = slot.desc.ensure(desc_bytes + states_bytes))) return rc;
-    if ((rc = slot.result.ensure(states_bytes))) return rc;
-    if ((rc = m->sets_desc.ensure(desc_bytes))) return rc;
+    if ((rc = slot.desc.ensure(desc_bytes + states_bytes)) || (rc = slot.result.ensure(states_bytes)) || (rc = m->sets_desc.ensure(desc_bytes)))
+        return rc;
     slot.desc_live_bytes = 0; // (the slot's pinned descriptor buffer is rewritten here)
     unsigned char *hd = slot.desc.p;
     std::memset(hd, 0, desc_bytes);
@@ -124,12 +102,7 @@ int ym_match_sets_many(ym_matcher *m, const ym_scan *const *queries, const int32
     }
     std::memcpy(hd + desc_bytes - ktab_bytes, m->kernel.data(), (size_t)ks * ks);
     YmItemState *st0 = reinterpret_cast<YmItemState *>(hd + desc_bytes);
-    std::memset(st0, 0, states_bytes);
-    for (int b = 0; b < n_items; b++) {
-        st0[b].pose[0] = st0[b].center[0] = items[b].ox_real; st0[b].pose[1] = st0[b].center[1] = items[b].oy_real;
-        st0[b].off_x = origin[2 * (size_t)b]; st0[b].off_y = origin[2 * (size_t)b + 1];
-        st0[b].ql = m->map_pts.p + items[b].out_off;
-    }
+    yag_init_states(m, items, origin.data(), 2, st0);
     hipStream_t st = m->stream;
     unsigned char *dd = m->sets_desc.p;
     // ym_profile_read: 0 = the integer sums of both passes (yag_map_kernel or the pair-by-pair kernel), 1 = the grids (clearing and
@@ -139,21 +112,18 @@ int ym_match_sets_many(ym_matcher *m, const ym_scan *const *queries, const int32
     HIP_TRY(hipMemcpyAsync(dd, hd, desc_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(m->states.p, st0, states_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(m->sets_ktab.p, hd + desc_bytes - ktab_bytes, (size_t)ks * ks, hipMemcpyHostToDevice, st));
-    ym::MapPointsManyArgs pa;
-    std::memset(&pa, 0, sizeof pa);
-    pa.scans = reinterpret_cast<const YmScanRef *>(dd);
-    pa.items = reinterpret_cast<const ym::MapItemDesc *>(dd + qscans_bytes + bscans_bytes);
-    pa.max_n = max_nq; pa.out = m->map_pts.p; pa.states = m->states.p;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ym::map_points_many_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)YM_PREP_LDS_BYTES(YM_MAX_BEAMS));
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ym::sets_grid_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)YM_PREP_LDS_BYTES(YM_MAX_BEAMS));
-    hipLaunchKernelGGL(ym::map_points_many_kernel, dim3(n_items), dim3(1024), YM_PREP_LDS_BYTES(max_nq), st, pa);
+    enqueue_map_points_many(m, reinterpret_cast<const YmScanRef *>(dd), reinterpret_cast<const ym::MapItemDesc *>(dd + qscans_bytes + bscans_bytes),
+                            n_items, max_nq);
     ym::SetsGridArgs ga;
     std::memset(&ga, 0, sizeof ga);
     ga.scans = reinterpret_cast<const YmScanRef *>(dd + qscans_bytes);
     ga.max_n = max_nb; ga.G = G; ga.res = res; ga.ktab = m->sets_ktab.p; ga.ksize = ks;
     ga.grid = m->sets_grid.p; ga.grid_stride = grid_stride;
+    S.grid = m->sets_grid.p; S.grid_stride = grid_stride; S.map_w = G; S.map_h = G; S.map_sets = 1; // (the states carry each grid's origin)
+    S.penalize = penalize; S.refine = refine; S.sums_items = sums_items; S.keep_all = keep_all;
+    S.need_fast = true; S.fallback = &m->sets_fallback_host; S.profile = true; // option 46 = 0 leaves every item to the rule as written
     const int passes = refine ? 2 : 1;
     int first_kept = 0, first_grid = 0;
     for (int c0 = 0; c0 < n_items; c0 += chunk) {
@@ -173,66 +143,16 @@ int ym_match_sets_many(ym_matcher *m, const ym_scan *const *queries, const int32
             hipLaunchKernelGGL(ym::sets_grid_kernel<256>, dim3(nj, share), dim3(256), YM_PREP_LDS_BYTES(max_nb), st, ga);
         }
         if ((rc = prof_end(m, ev_k))) return rc;
-        for (int pass = 0; pass < passes; pass++) {
-            ym::YagArgs a;
-            std::memset(&a, 0, sizeof a);
-            a.g = m->geom; a.pass = pass; a.refine = refine ? 1 : 0;
-            a.last = (pass == 1 || !refine) ? 1 : 0;
-            a.penalize = penalize ? 1 : 0;
-            if (pass == 0) { // scan_matching.py:100-103
-                a.search_xy = c_search; a.step_xy = c_step; a.search_t = c_tsearch; a.step_t = c_tstep;
-            } else { // scan_matching.py:106-108
-                a.search_xy = res * 2; a.step_xy = res; a.search_t = 0.0349 * 0.5; a.step_t = 0.00349;
-            }
-            a.map_res = res;
-            a.coarse_angle_res = m->cfg.coarse_angle_resolution;
-            a.states = m->states.p + c0; a.host_out = reinterpret_cast<YmItemState *>(slot.result.dp) + c0;
-            a.axes = m->yaxes.p; a.rot = nullptr; // (the kernels rotate the points themselves: the same products and sums)
-            a.sums = m->sums.p + (size_t)pass * sums_items * vol + (keep_all ? (size_t)c0 * vol : 0); a.out = m->resp.p;
-            a.grid = m->sets_grid.p; a.grid_stride = grid_stride; a.vol_stride = vol;
-            a.max_n = 0; a.maxd = maxd; a.maxt = maxt; a.n_items = B;
-            a.map_w = G; a.map_h = G; a.map_sets = 1;
-            a.counters = m->yag_counters.p;
-            // as ym_match_map_many: a pass whose every possible np.arange length fits yag_map_kernel's limit needs no yag_score_kernel,
-            // one whose none does no yag_map_kernel; option 46 = 0 leaves every item to the rule as written
-            const int est = (int)std::ceil(2 * a.search_xy / a.step_xy);
-            const bool run_map = est - 1 <= YM_YAG_MAP_DIM && m->yag_fast != 0, run_score = est + 1 > YM_YAG_MAP_DIM || !run_map;
-            a.map_dim = run_map ? YM_YAG_MAP_DIM : 0;
-            const int split = std::max(1, std::min(32, 1024 / (B * maxt)));
-            a.map_split = split;
-            hipLaunchKernelGGL(ym::yag_setup_kernel, dim3(1, B), dim3(256), 0, st, a);
-            if ((rc = prof_begin(m, 0, &ev_k))) return rc;
-            if (run_map) {
-                if (split > 1) HIP_TRY(hipMemsetAsync(a.sums, 0, (size_t)B * vol * sizeof(uint32_t), st));
-                hipLaunchKernelGGL(ym::yag_map_kernel, dim3(8 * maxt * ((B + 7) / 8) * split), dim3(256), 0, st, a);
-                if (split > 1) hipLaunchKernelGGL(ym::yag_map_score_kernel, dim3((maxd * maxd + 255) / 256, maxt, B), dim3(256), 0, st, a);
-            } else if (pass == 0) m->sets_fallback_host += B;
-            if (run_score) hipLaunchKernelGGL(ym::yag_score_kernel, dim3((maxd * maxd + 255) / 256, maxt, B), dim3(256), 0, st, a);
-            if ((rc = prof_end(m, ev_k))) return rc;
-            hipLaunchKernelGGL(ym::yag_reduce_kernel<1024>, dim3(B), dim3(1024), 0, st, a);
-        }
+        for (int pass = 0; pass < passes; pass++)
+            if ((rc = enqueue_yag_batch_pass(m, slot, S, c0, B, pass))) return rc;
     }
     if ((rc = prof_end(m, ev_call))) return rc;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     const YmItemState *rs = reinterpret_cast<const YmItemState *>(slot.result.p);
-    for (int b = 0; b < n_items; b++) {
-        const YmItemState &r = rs[b];
-        ym_result *out = results + b;
-        std::memset(out, 0, sizeof *out);
-        out->response = r.response;
-        for (int i = 0; i < 3; i++) out->pose[i] = r.mean[i];
-        for (int i = 0; i < 9; i++) out->cov[i] = r.cov[i];
-        out->coarse_response = r.ybest[0][0];
-        for (int i = 0; i < 3; i++) { out->coarse_dims[i] = r.ydims[0][i]; out->fine_dims[i] = refine ? r.ydims[1][i] : 0; }
-        out->hypotheses = (int64_t)r.ydims[0][0] * r.ydims[0][1] * r.ydims[0][2] +
-                          (refine ? (int64_t)r.ydims[1][0] * r.ydims[1][1] * r.ydims[1][2] : 0);
-        out->n_query_points = r.nq;
-        out->status = r.status;
-    }
-    m->last_valid = false; // the debug getters describe this call: the sums through map_last, grids and query points through sets_last
-    m->map_last.valid = true; m->map_last.n_items = n_items; m->map_last.first_kept = first_kept; m->map_last.passes = passes;
-    m->map_last.vol = vol; m->map_last.pass_offset[0] = 0; m->map_last.pass_offset[1] = sums_items * vol;
+    for (int b = 0; b < n_items; b++) yag_unpack_result(rs[b], refine, results + b);
+    // the debug getters describe this call: the sums through map_last, grids and query points through sets_last
+    map_last_set(m, n_items, first_kept, passes, vol, sums_items * vol);
     m->sets_last.valid = true; m->sets_last.G = G; m->sets_last.first_grid = first_grid; m->sets_last.grid_stride = grid_stride;
     return YM_OK;
 }

@@ -139,6 +139,11 @@ int enqueue_raster(ym_matcher *m, const CallPlan &P) {
 int enqueue_correlate(ym_matcher *m, const CallPlan &P);
 void enqueue_score(ym_matcher *m, Slot &slot, const CallPlan &P);
 
+// the reference's hard-coded fine search (scan_matching.py:106-108, :155-157, :211-214): every second find_best_pose pass takes it
+inline void yag_fine_search(ym::YagArgs &a, double res) {
+    a.search_xy = res * 2; a.step_xy = res; a.search_t = 0.0349 * 0.5; a.step_t = 0.00349;
+}
+
 // ---- the Python matcher's two find_best_pose passes (scan_matching.py:204-214)
 int enqueue_yagpy_passes(ym_matcher *m, Slot &slot, const CallPlan &P) {
     const Call &call = slot.call;
@@ -154,7 +159,7 @@ int enqueue_yagpy_passes(ym_matcher *m, Slot &slot, const CallPlan &P) {
             a.search_xy = m->cfg.search_size * 0.5; a.step_xy = g.res * 2;
             a.search_t = m->cfg.coarse_search_angle_offset * 0.5; a.step_t = m->cfg.coarse_angle_resolution;
         } else {
-            a.search_xy = g.res * 2; a.step_xy = g.res; a.search_t = 0.0349 * 0.5; a.step_t = 0.00349;
+            yag_fine_search(a, g.res);
         }
         a.coarse_angle_res = m->cfg.coarse_angle_resolution;
         a.states = m->states.p; a.host_out = reinterpret_cast<YmItemState *>(slot.result.dp);
