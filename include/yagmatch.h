@@ -865,6 +865,8 @@ int ym_debug_pair_lists(ym_matcher *m, int slot, ym_pair_list_info *info, double
  *                                          columns do not fit one 8-byte read)
  *   47      n / 0                          items per chunk of ym_match_map_many whatever its scratch budget says / by the budget
  *   48      n / 0                          items per chunk of ym_match_sets_many whatever its scratch budgets say / by the budgets
+ *   49      1                              the angular covariance gathers the scan again at the mean pose's cell even where that cell
+ *                                          is one of the fine lattice's and the fine pass's sums already hold the answer
  *
  * Options 0, 32, 33, 35, 43 and 44 chose between correlate forms that no longer exist: YM_ERR_INVALID, like any unknown option.
  */

@@ -388,5 +388,64 @@ def test_fine_tail_across_the_wrap(heading):
     _check("26x26x21", vol, heading=heading, refine=True, penalty=True)
 
 
+def _forced_regather_changes_nothing(vol, heading, penalty):
+    """debug option 49: the angular covariance gathers the scan again at the mean pose's cell instead of reading that cell's
+    column of the fine sums.  By the code's own argument the two are the same integers wherever that cell is one of the fine
+    lattice's, so the three forms, each twice, forced and not, give the same bytes"""
+    rig = _rig("26x26x21")
+    query, base, _ = _inputs(heading)
+    probs = vol.max(axis=0)
+    plain = rig.run(vol, probs, query, base, True, penalty)[0]
+    rig.m.debug_option(49, 1)
+    try:
+        forced = rig.run(vol, probs, query, base, True, penalty)[0]
+    finally:
+        rig.m.debug_option(49, 0)
+    assert len(plain) == len(forced) == 6
+    names = ["%s %s" % (f, w) for w in ("as is", "forced") for f in ("pair", "pair again", "finish<1024>", "finish<1024> again", "finish<256>", "finish<256> again")]
+    differ = [n for n, r in zip(names, plain + forced) if r != plain[0]]
+    assert not differ, "records differ from the pair's unforced one in: %s" % ", ".join(differ)
+
+
+@pytest.mark.parametrize("penalty", [True, False])
+@pytest.mark.parametrize("case", sorted(_fine_cases()))
+def test_forced_regather_equals_the_fine_sums(case, penalty):
+    vol = _background("26x26x21")
+    for kc in _fine_cases()[case]:
+        _plant(vol, kc, BEST)
+    _check("26x26x21", vol, refine=True, penalty=penalty)  # (the unforced results are still the reference's)
+    _forced_regather_changes_nothing(vol, 0.0, penalty)
+
+
+@pytest.mark.parametrize("heading", [3.13, -3.13])
+def test_forced_regather_equals_the_fine_sums_across_the_wrap(heading):
+    vol = _background("26x26x21")
+    for kc in [(9, 300), (12, 301), (12, 326)]:
+        _plant(vol, kc, BEST)
+    _check("26x26x21", vol, heading=heading, refine=True, penalty=True)
+    _forced_regather_changes_nothing(vol, heading, True)
+
+
+def test_status_of_a_volume_without_a_best_position_reaches_the_host():
+    """every response NaN: no hypothesis is DoubleEqual to the best, the tie set is empty and the match has status -5,
+    "unable to find best position", from every form (coarse only: there is no mean to refine around)"""
+    import torch
+    from yag_slam_amd import _capi
+    rig = _rig("26x26x21")
+    query, base, _ = _inputs()
+    with torch.cuda.stream(rig.stream):
+        vol_d = torch.full((21 * 26 * 26,), float("nan"), dtype=torch.float64, device="cuda")
+    for form, threads in FORMS:
+        rig.m.debug_option(6, form)
+        rig.m.debug_option(11, threads)
+        rig.m.slice_begin(query, base, True, False, 0, rig.nt, rig.resp.data_ptr(), rig.probs.data_ptr())
+        with torch.cuda.stream(rig.stream):
+            rig.resp.copy_(vol_d)
+            rig.probs.copy_(vol_d[:26 * 26])
+        with pytest.raises(_capi.YmError) as err:
+            rig.m.slice_finish()
+        assert err.value.code == -5, (form, threads)
+
+
 def test_fine_tail_of_the_zero_volume():
     _check("26x26x21", np.zeros((21, 26, 26)), refine=True, penalty=True, expansion=False)

@@ -161,6 +161,7 @@ int ym_debug_pair_lists(ym_matcher *m, int slot, ym_pair_list_info *info, double
 //   36  the raster does not write the row-major window (timing only)
 //   38  unused dynamic LDS bytes per region-correlate block     40  batch size from which batches get raster work lists (48)
 //   42  the region correlate's threshold alone (0 = 48)
+//   49  1 = the angular covariance always gathers the scan again (tests: tabulated in include/yagmatch.h)
 // (0, 32, 33, 35, 43 and 44 chose between correlate forms that are gone: YM_ERR_INVALID)
 int ym_debug_option(ym_matcher *m, int option, int value) {
     if (m) { m->cache_gen++; m->list_key_valid = false; } // (whatever the option changes, no earlier plan or pair list is reused)
@@ -199,6 +200,7 @@ int ym_debug_option(ym_matcher *m, int option, int value) {
     else if (option == 46) m->yag_fast = value < 0 ? 0 : value > 2 ? 1 : value;
     else if (option == 47) m->map_chunk_forced = value > 0 ? value : 0;
     else if (option == 48) m->sets_chunk_forced = value > 0 ? value : 0;
+    else if (option == 49) m->force_regather = value != 0;
     else if (option == 34) m->corr_region_rsplit = value;
     else if (option == 36) m->raster_planes_only = value;
     else if (option == 37) m->raster_no_rowtab = value;

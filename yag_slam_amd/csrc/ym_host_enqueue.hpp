@@ -391,14 +391,14 @@ void enqueue_finish(ym_matcher *m, Slot &slot, const CallPlan &P) {
     const Call &call = slot.call;
     const YmLattice &lc = P.lc, &lf = P.lf;
     ym::FinishArgs a;
-    a.g = P.g; a.lc = lc; a.lf = lf; a.refine = call.refine; a.max_n = P.max_n; a.nt_stride = lf.nt;
+    a.g = P.g; a.lc = lc; a.lf = lf; a.refine = call.refine;
     a.n_blocks = P.score_blocks; a.states = m->states.p;
     a.host_out = reinterpret_cast<YmItemState *>(slot.result.dp);
     a.resp = P.resp; a.sums_stride = P.sums_c; a.blockmax = m->blockmax.p; a.probs = P.probs;
     a.probs_stride = (size_t)lc.nx * lc.ny; a.grid = m->grid.p; a.grid_stride = P.grid_stride;
-    a.qlocal = m->qlocal.p; a.foffsets = m->foffsets.p; a.fsums = m->sums.p + m->sums_pass_offset[1];
+    a.fsums = m->sums.p + m->sums_pass_offset[1];
     a.fsums_stride = P.sums_f; a.stamps = P.stamps;
-    a.host_flag = nullptr; a.serial = 0; a.pad1 = 0;
+    a.host_flag = nullptr; a.serial = 0; a.force_regather = m->force_regather ? 1 : 0;
     a.seq_pose = nullptr; a.seq_prior = nullptr; a.fault = nullptr; a.next_diff[0] = a.next_diff[1] = a.next_diff[2] = 0.0; a.step = 0; a.expansion = 0;
     if (call.chain_step) {
         a.host_out = call.chain_out;

@@ -101,7 +101,6 @@ struct ym_matcher {
     // kept the mode in the signature: one single match between two batches of 4096 cost the second a full raster of all 4096 windows)
     std::vector<unsigned char> planes_stale;
     DevBuf<double2> ctrig;     // (cos, sin) per coarse angle
-    DevBuf<int32_t> foffsets;  // fine lookup tables
     DevBuf<int32_t> hypcell;
     DevBuf<uint16_t> partial;  // per beam-chunk partial sums of the coarse lattice
     DevBuf<uint16_t> rg_entries; // region correlate: per query slot of a call the (beam, angle) pairs sorted by region
@@ -218,6 +217,7 @@ struct ym_matcher {
     int raster_hits_per_tile = 0; // tests: hit slots per entry of the raster's work list (0 = YM_TILE_HITS, -1 = no hit lists)
     int keep_sums = 0;      // development: keep the coarse integer sums of batches too (ym_debug_sums)
     int finish_threads = 0; // development: force the finish kernel's block size (256 / 1024)
+    int force_regather = 0; // tests: the angular covariance gathers the scan again instead of reading the fine sums
     int select_global = 0; // development / tests: always evaluate the order-dependent smear rule with the global-memory kernel
     int select_split_max = 8; // items up to which the rule runs in its split form (tests: 0 = the one-block kernel always)
     DevBuf<double> tmp_ranges;   // device copy of ranges for the descriptor-based entry

@@ -303,7 +303,6 @@ int plan_sizes(ym_matcher *m, Slot &slot, CallPlan &P) {
     if ((rc = m->grid.ensure((size_t)B * P.grid_stride + window_slack))) return rc;
     if ((rc = m->planes.ensure((size_t)B * P.grid_stride + std::max(planes_slack, YM_GA_PLANES_SLACK(g.pitch / 2, std::max(P.ga_rows, P.ga_nry + P.ga_H), lc.ny, P.ga_P))))) return rc;
     if ((rc = m->ctrig.ensure((size_t)B * P.nt_stride))) return rc;
-    if ((rc = m->foffsets.ensure((size_t)B * lf.nt * max_n))) return rc;
     if ((rc = m->hypcell.ensure((size_t)B * 2 * P.dim_stride))) return rc;
     if ((rc = m->partial.ensure((size_t)B * P.partial_stride + 16))) return rc;
     if ((rc = m->sums.ensure((size_t)B * std::max(P.sums_c + P.sums_f, 2 * P.yvol + (yag ? P.sums_c : 0))))) return rc; // (yagpy: [pass 0][pass 1][launch lattice])

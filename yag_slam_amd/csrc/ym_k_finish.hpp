@@ -1,5 +1,19 @@
 // ym_k_finish.hpp -- K5 score_kernel, K6 fine_kernel / final_kernel / finish_kernel, K7 argbest_kernel.
 // Part of ym_kernels.hpp (include that, not this file).
+//
+// The finish stage exists in three forms that must agree bit for bit: fine_kernel<WIDE> + final_kernel (few items),
+// finish_kernel<1024> and finish_kernel<256> (batches).  What they compute is stated once, in __device__ functions they all call:
+//   lattice_cell / lattice_xy / lattice_hyp                      cell and hypothesis indices, a cell's offset (K5 and K6)
+//   cell_partials / chunk_group_sum                              K5: a cell's partial sums in either layout, summed
+//   coarse_best_and_mean, tie_accumulate / tie_mean              arg-max and tie-set mean
+//   positional_covariance                                        ComputePositionalCovariance
+//   no_readings_result                                           MatchScan's early return
+//   fine_lattice_setup                                           the fine lattice's window cells, cleared sums, block3
+//   block3_load / block3_accumulate, generic_gather              a beam's cells into the fine sums
+//   fine_best_and_mean                                           fine responses, arg-max, tie mean
+//   angular_covariance (angular_cov_sums)                        ComputeAngularCovariance, its re-gather included
+//   write_result (chain_next_pose)                               state, host record, completion word, chain pose, fault
+// The kernels keep what differs between them: which thread takes which beam and angle, and where the fine sums live.
 #pragma once
 
 namespace ym {
@@ -52,6 +66,35 @@ __device__ __forceinline__ double hyp_response(const YmGeom &g, int penalize, un
     return hyp_response_dp(g, penalize, sum, nq, dist_penalty(g, sq_dist), angle, center_t);
 }
 
+// ---- lattice cells, stated once for K5 and K6.  Cell c = iy * nx + ix, hypothesis h = k * nx * ny + c, and the offset of
+// cell (ix, iy) from the lattice's centre is -off + i * step: operation for operation what the oracle computes (bit parity).
+__device__ __forceinline__ int2 lattice_cell(const YmLattice &L, int c) { // (ix, iy)
+    const int iy = c / L.nx;
+    return make_int2(c - iy * L.nx, iy);
+}
+__device__ __forceinline__ double2 lattice_xy(const YmLattice &L, int2 ic) {
+    return make_double2(-L.off_x + ic.x * L.step_x, -L.off_y + ic.y * L.step_y);
+}
+__device__ __forceinline__ int2 lattice_hyp(const YmLattice &L, int h) { // (k, c)
+    const int nxy = L.nx * L.ny, k = h / nxy;
+    return make_int2(k, h - k * nxy);
+}
+
+// the partial sums of cell ic at angle k: a pointer to those of chunk group 0, and the strides to the next angle and group
+__device__ __forceinline__ const uint16_t *cell_partials(const ScoreArgs &a, int b, int k, int2 ic, size_t *kstride, size_t *cstride) {
+    *kstride = a.lane_layout ? (size_t)64 * 16 : (size_t)a.lat.ny * a.nx_pad;
+    *cstride = (size_t)a.lat.nt * *kstride;
+    return a.partial + (size_t)b * a.partial_stride + (size_t)k * *kstride +
+           (a.lane_layout ? (size_t)((32 * (ic.x / 13) + ic.y) * 16 + ic.x % 13) : (size_t)ic.y * a.nx_pad + ic.x);
+}
+template <int UNROLL>
+__device__ __forceinline__ unsigned chunk_group_sum(const uint16_t *p, int n_chunks, size_t cstride) {
+    unsigned sum = 0;
+#pragma unroll UNROLL
+    for (int c2 = 0; c2 < n_chunks; c2++) sum += p[(size_t)c2 * cstride];
+    return sum;
+}
+
 // One thread per (x, y) lattice cell, walking the coarse angles [k_begin, k_end): add the chunk-group partials,
 // normalise, penalise, keep the maximum over theta (Karto's search-space probability grid: a plain store, no atomics).
 // Block maxima are kept per (angle, block of YM_SCORE_THREADS cells): blockmax[k * n_cell_blocks + cb] covers the
@@ -61,27 +104,22 @@ __global__ __launch_bounds__(YM_SCORE_THREADS) void score_kernel(ScoreArgs a) {
     __shared__ double scratch[16];
     const int b = blockIdx.y;
     const YmItemState &st = a.states[b];
-    const int nx = a.lat.nx, ny = a.lat.ny, nt = a.lat.nt, nxy = nx * ny;
+    const int nxy = a.lat.nx * a.lat.ny;
     const int c = blockIdx.x * YM_SCORE_THREADS + threadIdx.x;
     const bool live = c < nxy;
-    const int iy = live ? c / nx : 0, ix = live ? c - iy * nx : 0;
-    const double x = -a.lat.off_x + ix * a.lat.step_x, y = -a.lat.off_y + iy * a.lat.step_y;
-    const double sq_dist = x * x + y * y;
+    const int2 ic = live ? lattice_cell(a.lat, c) : make_int2(0, 0);
+    const double2 xy = lattice_xy(a.lat, ic);
+    const double sq_dist = xy.x * xy.x + xy.y * xy.y;
     const double ct = st.center[2];
     const int nq = st.nq;
-    const size_t kstride = a.lane_layout ? (size_t)64 * 16 : (size_t)ny * a.nx_pad;
-    const size_t cstride = (size_t)nt * kstride;
-    const uint16_t *p0 = a.partial + (size_t)b * a.partial_stride +
-                         (a.lane_layout ? (size_t)((32 * (ix / 13) + iy) * 16 + ix % 13) : (size_t)iy * a.nx_pad + ix);
+    size_t kstride, cstride;
+    const uint16_t *p0 = cell_partials(a, b, 0, ic, &kstride, &cstride);
     double best = 0.0;
     YM_STAMP(a, 10);
     for (int k = a.k_begin; k < a.k_end; k++) {
         double r = -1.0;
         if (live) {
-            const uint16_t *p = p0 + (size_t)k * kstride;
-            unsigned sum = 0;
-#pragma unroll 4
-            for (int c2 = 0; c2 < a.n_chunks; c2++) sum += p[(size_t)c2 * cstride];
+            const unsigned sum = chunk_group_sum<4>(p0 + (size_t)k * kstride, a.n_chunks, cstride);
             const double angle = (ct - a.lat.angle_off) + k * a.lat.angle_res;
             r = hyp_response(a.g, a.lat.penalize, sum, nq, sq_dist, angle, ct);
             const size_t h = (size_t)k * nxy + c;
@@ -107,24 +145,18 @@ __global__ __launch_bounds__(YM_SCORE_THREADS) void score_hyp_kernel(ScoreArgs a
     __shared__ double scratch[16];
     const int b = blockIdx.z;
     const YmItemState &st = a.states[b];
-    const int nx = a.lat.nx, ny = a.lat.ny, nt = a.lat.nt, nxy = nx * ny;
+    const int nxy = a.lat.nx * a.lat.ny;
     const int c = blockIdx.x * YM_SCORE_THREADS + threadIdx.x, k = a.k_begin + blockIdx.y;
     double r = -1.0;
     YM_STAMP(a, 10);
     if (c < nxy) {
-        const int iy = c / nx, ix = c - iy * nx;
-        // (lane_layout: the region correlate's sets, [set][angle][lane = 32 * (ix / 13) + iy][ix % 13 of 16])
-        const size_t kstride = a.lane_layout ? (size_t)64 * 16 : (size_t)ny * a.nx_pad;
-        const uint16_t *p = a.partial + (size_t)b * a.partial_stride + (size_t)k * kstride +
-                            (a.lane_layout ? (size_t)((32 * (ix / 13) + iy) * 16 + ix % 13) : (size_t)iy * a.nx_pad + ix);
-        const size_t cstride = (size_t)nt * kstride;
-        unsigned sum = 0;
-#pragma unroll 8
-        for (int c2 = 0; c2 < a.n_chunks; c2++) sum += p[(size_t)c2 * cstride];
-        const double x = -a.lat.off_x + ix * a.lat.step_x, y = -a.lat.off_y + iy * a.lat.step_y;
+        const int2 ic = lattice_cell(a.lat, c);
+        size_t kstride, cstride;
+        const unsigned sum = chunk_group_sum<8>(cell_partials(a, b, k, ic, &kstride, &cstride), a.n_chunks, cstride);
+        const double2 xy = lattice_xy(a.lat, ic);
         const double ct = st.center[2];
         const double angle = (ct - a.lat.angle_off) + k * a.lat.angle_res;
-        r = hyp_response(a.g, a.lat.penalize, sum, st.nq, x * x + y * y, angle, ct);
+        r = hyp_response(a.g, a.lat.penalize, sum, st.nq, xy.x * xy.x + xy.y * xy.y, angle, ct);
         const size_t h = (size_t)k * nxy + c;
         if (a.sums) a.sums[(size_t)b * a.sums_stride + h] = sum;
         a.resp[(size_t)b * a.sums_stride + h] = r;
@@ -153,8 +185,7 @@ __global__ __launch_bounds__(YM_SCORE_THREADS) void blockmax_kernel(const double
 struct FinishArgs {
     YmGeom g;
     YmLattice lc, lf;
-    int32_t refine;
-    int32_t max_n, nt_stride, n_blocks;
+    int32_t refine, n_blocks;
     YmItemState *states;
     YmItemState *host_out;    // pinned host memory, written directly (nullable)
     const double *resp;       // coarse responses [B][nt][ny][nx]
@@ -164,13 +195,12 @@ struct FinishArgs {
     size_t probs_stride;
     const uint8_t *grid;
     size_t grid_stride;
-    const double2 *qlocal;
-    int32_t *foffsets;        // [B][nt_f][max_n] fine lookup table (scratch)
     uint32_t *fsums;          // [B][nt_f*ny_f*nx_f] fine sums (kept for parity tests)
     size_t fsums_stride;
     unsigned long long *stamps;
     uint32_t *host_flag;      // single matches: pinned host word that receives `serial` once host_out[0] is complete (the
-    uint32_t serial, pad1;    // caller polls it instead of waiting for a stream event), or null
+    uint32_t serial;          // caller polls it instead of waiting for a stream event), or null
+    uint32_t force_regather;  // tests: the angular covariance gathers the scan again even where the fine sums hold its answer
     // device-chained sequences (ym_map_sequence): the step's pose goes to seq_pose[0..2] (this scan's row of the segment's
     // pose table) and the next step's odometry prior = that pose (+) next_diff (tiny_tf's Transform composition) to
     // seq_prior[0..2]; a step that Karto would abort or repeat with a wider angle range (response expansion) is a fault
@@ -227,12 +257,19 @@ __device__ __forceinline__ void block_sum_vec_sparse(double (&v)[N], double *scr
 // the loads of the block maxima.
 __device__ __forceinline__ void tie_accumulate(double (&acc)[5], const YmLattice &L, int h, double cxw, double cyw,
                                                const double2 *trig) {
-    const int nxy = L.nx * L.ny;
-    const int k = h / nxy, c = h - k * nxy, iy = c / L.nx, ix = c - iy * L.nx;
-    const double x = -L.off_x + ix * L.step_x, y = -L.off_y + iy * L.step_y;
-    acc[0] += cxw + x; acc[1] += cyw + y;
-    acc[2] += trig[k].x; acc[3] += trig[k].y;
+    const int2 kc = lattice_hyp(L, h);
+    const double2 xy = lattice_xy(L, lattice_cell(L, kc.y));
+    acc[0] += cxw + xy.x; acc[1] += cyw + xy.y;
+    acc[2] += trig[kc.x].x; acc[3] += trig[kc.x].y;
     acc[4] += 1.0;
+}
+// ... and its mean.  false: no hypothesis tied ("Unable to find best position"), mean is left as it was
+__device__ __forceinline__ bool tie_mean(const double (&acc)[5], double mean[3]) {
+    if (!(acc[4] > 0.0)) return false;
+    const double cnt = acc[4]; // exact small integer, same value as Karto's int count
+    mean[0] = acc[0] / cnt; mean[1] = acc[1] / cnt;
+    mean[2] = atan2(acc[3] / cnt, acc[2] / cnt);
+    return true;
 }
 // (a barrier must separate this from the first tie_accumulate)
 template <int NT>
@@ -315,13 +352,9 @@ __device__ __forceinline__ double coarse_best_and_mean(const YmLattice &L, const
         }
     }
     block_sum_vec_sparse<5>(acc, scratch, acc[4] != 0.0);
-    if (acc[4] > 0.0) {
-        const double cnt = acc[4]; // exact small integer, same value as Karto's int count
-        mean[0] = acc[0] / cnt; mean[1] = acc[1] / cnt;
-        mean[2] = atan2(acc[3] / cnt, acc[2] / cnt);
-    } else {
+    if (!tie_mean(acc, mean)) {
         mean[0] = mean[1] = mean[2] = 0.0;
-        *status = -5; // "Unable to find best position"
+        *status = -5;
     }
     return best;
 }
@@ -333,9 +366,8 @@ __device__ __forceinline__ void positional_covariance(const FinishArgs &a, int b
     const int tid = threadIdx.x;
     for (int i = 0; i < 9; i++) cov[i] = (i % 4 == 0) ? 1.0 : 0.0;
     const YmLattice &L = a.lc;
-    const int nx = L.nx, nxy = nx * L.ny;
+    const int nxy = L.nx * L.ny;
     const double cxw = st.pose[0], cyw = st.pose[1];
-    const double start_x = -L.off_x, start_y = -L.off_y;
     double sums[4] = {0, 0, 0, 0};
     const double dx = mean[0] - cxw, dy = mean[1] - cyw;
     if (!(best < YM_KT_TOLERANCE)) {
@@ -354,8 +386,8 @@ __device__ __forceinline__ void positional_covariance(const FinishArgs &a, int b
                     const int c = c0 + u * YM_CANON;
                     const double response = pv[u];
                     if (c < nxy && response >= (best - 0.1)) {
-                        const int iy = c / nx, ix = c - iy * nx;
-                        const double x = start_x + ix * L.step_x, y = start_y + iy * L.step_y;
+                        const double2 xy = lattice_xy(L, lattice_cell(L, c));
+                        const double x = xy.x, y = xy.y;
                         sums[0] += response;
                         sums[1] += ((x - dx) * (x - dx)) * response;
                         sums[2] += ((x - dx) * (y - dy) * response);
@@ -386,6 +418,68 @@ __device__ __forceinline__ void positional_covariance(const FinishArgs &a, int b
         }
         if (kt_double_equal(cov[0], 0.0)) cov[0] = YM_MAX_VARIANCE;
         if (kt_double_equal(cov[4], 0.0)) cov[4] = YM_MAX_VARIANCE;
+    }
+}
+
+// ---- the fine pass's pieces, shared by fine_kernel + final_kernel and finish_kernel
+// a chained step's pose and the next step's odometry prior (ym_map_sequence; yag_slam_amd/transform.py: a + b)
+__device__ __forceinline__ void chain_next_pose(const FinishArgs &a, const double pose[3]) {
+    const double c = cos(pose[2]), s = sin(pose[2]);
+    a.seq_pose[0] = pose[0]; a.seq_pose[1] = pose[1]; a.seq_pose[2] = pose[2];
+    a.seq_prior[0] = pose[0] + c * a.next_diff[0] - s * a.next_diff[1];
+    a.seq_prior[1] = pose[1] + s * a.next_diff[0] + c * a.next_diff[1];
+    a.seq_prior[2] = pose[2] + a.next_diff[2];
+}
+// MatchScan: "scan has no readings; cannot do scan matching" -> pose, maximum covariance, 0  (one thread)
+__device__ __forceinline__ void no_readings_result(const FinishArgs &a, int b, YmItemState &st) {
+    for (int i = 0; i < 9; i++) st.cov[i] = 0.0;
+    st.cov[0] = YM_MAX_VARIANCE; st.cov[4] = YM_MAX_VARIANCE;
+    st.cov[8] = 4 * (a.lc.angle_res * a.lc.angle_res);
+    for (int i = 0; i < 3; i++) { st.mean[i] = st.pose[i]; st.center[i] = st.pose[i]; }
+    st.response = 0.0;
+    st.coarse_response = 1.0; // nothing to retry with a wider angle
+    if (a.host_out) a.host_out[b] = st;
+    if (a.host_flag) { __threadfence_system(); *reinterpret_cast<volatile uint32_t *>(a.host_flag) = a.serial; }
+    if (a.seq_pose) chain_next_pose(a, st.pose);
+}
+
+// the window cells of the fine lattice's columns and rows around the coarse mean and n_sums cleared sums, behind a barrier.
+// Returns block3: Karto's fine lattice, 3 x 3 adjacent cells of a window whose rows lie `pitch` apart -- a beam's nine cells
+// are three 4-byte words
+template <int NT>
+__device__ __forceinline__ bool fine_lattice_setup(const FinishArgs &a, const double cmean[3], double off_x, double off_y, int *s_cx, int *s_cy,
+                                                   unsigned *s_sum, int n_sums) {
+    const YmLattice &L = a.lf;
+    for (int i = threadIdx.x; i < L.nx; i += NT) s_cx[i] = hyp_cell(cmean[0], -L.off_x, i, L.step_x, off_x, a.g);
+    for (int i = threadIdx.x; i < L.ny; i += NT) s_cy[i] = hyp_cell(cmean[1], -L.off_y, i, L.step_y, off_y, a.g);
+    for (int h = threadIdx.x; h < n_sums; h += NT) s_sum[h] = 0u;
+    __syncthreads();
+    return !a.g.kpitch && a.lf.nx == 3 && a.lf.ny == 3 && s_cx[1] == s_cx[0] + 1 && s_cx[2] == s_cx[0] + 2 && s_cy[1] == s_cy[0] + 1 &&
+           s_cy[2] == s_cy[0] + 2;
+}
+// block3: the three words under a beam, and their nine byte lanes added to nine sums (m: 0xff, or 0 for a beam that is none)
+__device__ __forceinline__ void block3_load(uint32_t (&w)[3], const uint8_t *grid, uint32_t idx, int pitch) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) __builtin_memcpy(&w[r], grid + (uint32_t)(idx + r * pitch), 4);
+}
+__device__ __forceinline__ void block3_accumulate(unsigned (&acc)[9], const uint32_t (&w)[3], uint32_t m) {
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        acc[3 * r] += w[r] & m; acc[3 * r + 1] += (w[r] >> 8) & m; acc[3 * r + 2] += (w[r] >> 16) & m;
+    }
+}
+// generic lattice, one fine angle: the beams first, first + stride, ..., every (iy, ix) cell of each into s_sum[iy * nx + ix]
+__device__ __forceinline__ void generic_gather(const FinishArgs &a, const uint8_t *grid, const double2 *ql, int nq, double2 cs, double off_x,
+                                               double off_y, const int *s_cx, const int *s_cy, unsigned *s_sum, int first, int stride) {
+    const int nxy = a.lf.nx * a.lf.ny;
+    const unsigned limit = (unsigned)(a.g.pitch * a.g.win_w);
+    for (int i = first; i < nq; i += stride) {
+        const int off = lookup_offset(ql[i], cs.x, cs.y, off_x, off_y, a.g.scale, lin_pitch(a.g));
+        for (int c = 0; c < nxy; c++) {
+            const int2 ic = lattice_cell(a.lf, c);
+            const unsigned v = cell_value(a.g, grid, limit, (unsigned)(s_cy[ic.y] * lin_pitch(a.g) + s_cx[ic.x] + off));
+            if (v) atomicAdd(&s_sum[c], v);
+        }
     }
 }
 
@@ -436,28 +530,19 @@ __global__ __launch_bounds__(YM_FINE_THREADS) void fine_kernel(FinishArgs a) {
     YM_STAMP(a, 13);
 
     const YmLattice &L = a.lf;
-    const int nx = L.nx, ny = L.ny, nxy = nx * ny;
-    const double start_x = -L.off_x, start_y = -L.off_y;
+    const int nxy = L.nx * L.ny;
     if (tid == 0) {
         const double angle = (mean[2] - L.angle_off) + k * L.angle_res;
         s_cs[0] = cos(angle);
         s_cs[1] = sin(angle);
     }
-    for (int i = tid; i < nx; i += NT) s_cx[i] = hyp_cell(mean[0], start_x, i, L.step_x, off_x, a.g);
-    for (int i = tid; i < ny; i += NT) s_cy[i] = hyp_cell(mean[1], start_y, i, L.step_y, off_y, a.g);
-    for (int h = tid; h < nxy; h += NT) s_sum[h] = 0u;
-    __syncthreads();
+    const bool block3 = fine_lattice_setup<NT>(a, mean, off_x, off_y, s_cx, s_cy, s_sum, nxy);
     YM_STAMP(a, 14);
-    const double cosine = s_cs[0], sine = s_cs[1];
+    const double2 cs = make_double2(s_cs[0], s_cs[1]);
     const uint8_t *grid = a.grid + (size_t)b * a.grid_stride;
-    const unsigned limit = (unsigned)(a.g.pitch * a.g.win_w);
-    int32_t *foff = a.foffsets + ((size_t)b * a.nt_stride + k) * a.max_n;
     const double2 *ql = reinterpret_cast<const double2 *>(st.ql);
-    const bool block3 = !a.g.kpitch && nx == 3 && ny == 3 && s_cx[1] == s_cx[0] + 1 && s_cx[2] == s_cx[0] + 2 &&
-                        s_cy[1] == s_cy[0] + 1 && s_cy[2] == s_cy[0] + 2;
     if (block3) {
-        // Karto's fine lattice is always 3x3 cells: a lane reads the 3x3 cell block under its beam
-        // as three 4-byte words.
+        // a lane reads the 3x3 cell block under its beam as three 4-byte words
         const uint32_t base0 = (uint32_t)(s_cy[0] * a.g.pitch + s_cx[0]);
         unsigned acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int i = tid; i < nq; i += 4 * NT) {
@@ -466,22 +551,11 @@ __global__ __launch_bounds__(YM_FINE_THREADS) void fine_kernel(FinishArgs a) {
             for (int u = 0; u < 4; u++) {
                 const int ii = i + u * NT;
                 int off = 0;
-                if (ii < nq) {
-                    off = lookup_offset(ql[ii], cosine, sine, off_x, off_y, a.g.scale, a.g.pitch);
-                    foff[ii] = off;
-                }
-                const uint32_t idx = base0 + (uint32_t)off;
-#pragma unroll
-                for (int r = 0; r < 3; r++) __builtin_memcpy(&w[u][r], grid + (uint32_t)(idx + r * a.g.pitch), 4);
+                if (ii < nq) off = lookup_offset(ql[ii], cs.x, cs.y, off_x, off_y, a.g.scale, a.g.pitch); // (a branch: whole waves skip it)
+                block3_load(w[u], grid, base0 + (uint32_t)off, a.g.pitch);
             }
 #pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const uint32_t m = (i + u * NT) < nq ? 0xffu : 0u;
-#pragma unroll
-                for (int r = 0; r < 3; r++) {
-                    acc[3 * r] += w[u][r] & m; acc[3 * r + 1] += (w[u][r] >> 8) & m; acc[3 * r + 2] += (w[u][r] >> 16) & m;
-                }
-            }
+            for (int u = 0; u < 4; u++) block3_accumulate(acc, w[u], (i + u * NT) < nq ? 0xffu : 0u);
         }
 #pragma unroll
         for (int j = 0; j < 9; j++) acc[j] = wave_reduce(acc[j], OpAddU());
@@ -489,16 +563,7 @@ __global__ __launch_bounds__(YM_FINE_THREADS) void fine_kernel(FinishArgs a) {
 #pragma unroll
             for (int j = 0; j < 9; j++) atomicAdd(&s_sum[j], acc[j]);
     } else {
-        // generic lattice: per beam, every (iy, ix) cell
-        for (int i = tid; i < nq; i += NT) {
-            const int off = lookup_offset(ql[i], cosine, sine, off_x, off_y, a.g.scale, lin_pitch(a.g));
-            foff[i] = off;
-            for (int c = 0; c < nxy; c++) {
-                const int iy = c / nx, ix = c - iy * nx;
-                const unsigned v = cell_value(a.g, grid, limit, (unsigned)(s_cy[iy] * lin_pitch(a.g) + s_cx[ix] + off));
-                if (v) atomicAdd(&s_sum[c], v);
-            }
-        }
+        generic_gather(a, grid, ql, nq, cs, off_x, off_y, s_cx, s_cy, s_sum, tid, NT);
     }
     __syncthreads();
     uint32_t *fs = a.fsums + (size_t)b * a.fsums_stride + (size_t)k * nxy;
@@ -531,13 +596,113 @@ __device__ __forceinline__ double angular_cov_sums(const unsigned *s_asum, int n
     return accv;
 }
 
-// a chained step's pose and the next step's odometry prior (ym_map_sequence; yag_slam_amd/transform.py: a + b)
-__device__ __forceinline__ void chain_next_pose(const FinishArgs &a, const double pose[3]) {
-    const double c = cos(pose[2]), s = sin(pose[2]);
-    a.seq_pose[0] = pose[0]; a.seq_pose[1] = pose[1]; a.seq_pose[2] = pose[2];
-    a.seq_prior[0] = pose[0] + c * a.next_diff[0] - s * a.next_diff[1];
-    a.seq_prior[1] = pose[1] + s * a.next_diff[0] + c * a.next_diff[1];
-    a.seq_prior[2] = pose[2] + a.next_diff[2];
+// Fine tail of CorrelateScan (doingFineMatch) for one item: the responses of the fine lattice around the coarse mean cmean
+// into s_fresp, the best of them (returned, unclamped) and the mean of its tie set (mean; none: *status = -5 and mean stays).
+// sum_at(h): the integer sum of fine hypothesis h, from wherever the caller keeps it; it is called exactly once per h, by the
+// thread that takes h, and may store (final_kernel keeps the sum in LDS, finish_kernel writes it out).  s_trig: tie_trig_table of the fine
+// lattice, written before a barrier the caller has passed or block_reduce's own.
+template <int NT, class SumAt>
+__device__ __forceinline__ double fine_best_and_mean(const FinishArgs &a, int nq, const double cmean[3], SumAt sum_at, double *s_fresp,
+                                                     const double2 *s_trig, double *scratch, double mean[3], int *status) {
+    const YmLattice &L = a.lf;
+    const int tid = threadIdx.x, nh = L.nx * L.ny * L.nt;
+    const double start_angle = cmean[2] - L.angle_off;
+    double lb = -1.0;
+    for (int h = tid; h < nh; h += NT) {
+        const int2 kc = lattice_hyp(L, h);
+        const double2 xy = lattice_xy(L, lattice_cell(L, kc.y));
+        const double r = hyp_response(a.g, L.penalize, sum_at(h), nq, xy.x * xy.x + xy.y * xy.y, start_angle + kc.x * L.angle_res, cmean[2]);
+        s_fresp[h] = r;
+        lb = r > lb ? r : lb;
+    }
+    const double best = block_reduce(lb, OpMaxD(), -1.0, scratch);
+    double acc[5] = {0, 0, 0, 0, 0};
+    for (int h = tid; h < nh && tid < YM_CANON; h += YM_CANON)
+        if (kt_double_equal(s_fresp[h], best)) tie_accumulate(acc, L, h, cmean[0], cmean[1], s_trig);
+    block_sum_vec_sparse<5>(acc, scratch, acc[4] != 0.0);
+    if (!tie_mean(acc, mean)) *status = -5;
+    return best;
+}
+
+// ComputeAngularCovariance: every fine angle re-scored at the cell of the mean pose; returns cov[8].  GetResponse(angle k,
+// that cell) uses the fine pass's own lookup offsets, so when the cell is one of the fine lattice's cells (always, unless fp
+// rounding puts the tie mean outside) the sum IS the fine pass's integer sum s_sum[(k, that cell)]: taken instead of
+// gathering the scan again.  Lane i of every wave looks at lattice column i and row i (at most 64 of each) and a ballot
+// tells all of them: no memory, no barrier; the last match wins, as in a loop over i (the cells increase with i).
+// Otherwise, or with force_regather, wave w gathers angles w, w + NW, ... again with (cos, sin) of fine angle k from s_cs --
+// CS_READY: the caller has them there; if not they are computed here, inside the branch (it is block-uniform), so that the
+// ordinary path sees no fp64 trigonometry.  s_asum: nt words, tmp: 2 * nt doubles, both free.
+template <int NT, bool CS_READY>
+__device__ __forceinline__ double angular_covariance(const FinishArgs &a, const YmItemState &st, int nq, const uint8_t *grid, double off_x,
+                                                     double off_y, const double cmean[3], const double mean[3], double best,
+                                                     const unsigned *s_sum, double2 *s_cs, unsigned *s_asum, double *tmp) {
+    const YmLattice &L = a.lf;
+    const int tid = threadIdx.x, lane = tid & 63, nx = L.nx, ny = L.ny, nt = L.nt, nxy = nx * ny;
+    const double ct = cmean[2], start_angle = ct - L.angle_off;
+    const double best_angle = kt_normalize_angle_difference(mean[2], ct);
+    const int gx = world_to_grid(mean[0], off_x, a.g.scale) + a.g.border - a.g.win_origin;
+    const int gy = world_to_grid(mean[1], off_y, a.g.scale) + a.g.border - a.g.win_origin;
+    const unsigned long long mx = __ballot(lane < nx && hyp_cell(cmean[0], -L.off_x, lane, L.step_x, off_x, a.g) == gx);
+    const unsigned long long my = __ballot(lane < ny && hyp_cell(cmean[1], -L.off_y, lane, L.step_y, off_y, a.g) == gy);
+    const int hit_x = mx && !a.force_regather ? 63 - __clzll(mx) : -1, hit_y = my ? 63 - __clzll(my) : -1;
+    if (hit_x >= 0 && hit_y >= 0) {
+        for (int k = tid; k < nt; k += NT) s_asum[k] = s_sum[k * nxy + hit_y * nx + hit_x];
+    } else {
+        if (!CS_READY) {
+            for (int k = tid; k < nt; k += NT) {
+                const double angle = start_angle + k * L.angle_res;
+                s_cs[k] = make_double2(cos(angle), sin(angle));
+            }
+            __syncthreads();
+        }
+        const int base = gy * lin_pitch(a.g) + gx;
+        const unsigned limit = (unsigned)(a.g.pitch * a.g.win_w);
+        const double2 *ql = reinterpret_cast<const double2 *>(st.ql);
+        for (int k = tid >> 6; k < nt; k += NT / 64) { // wave-uniform
+            unsigned v = 0;
+            for (int i = lane; i < nq; i += 64)
+                v += cell_value(a.g, grid, limit, (unsigned)(base + lookup_offset(ql[i], s_cs[k].x, s_cs[k].y, off_x, off_y, a.g.scale, lin_pitch(a.g))));
+            v = wave_reduce(v, OpAddU());
+            if (lane == 0) s_asum[k] = v;
+        }
+    }
+    __syncthreads();
+    double norm = 0.0;
+    double accv = angular_cov_sums<NT>(s_asum, nt, nq, start_angle, L.angle_res, best, best_angle, tmp, &norm);
+    if (norm > YM_KT_TOLERANCE) {
+        if (accv < YM_KT_TOLERANCE) accv = L.angle_res * L.angle_res;
+        accv /= norm;
+    } else {
+        accv = 1000 * (L.angle_res * L.angle_res);
+    }
+    return accv;
+}
+
+// An item's result (one thread): its state; what the host reads of a result (state_to_result and finish_call read these
+// fields and no others), straight from registers -- copying `st` would first read the whole state back from device memory,
+// one more round trip at the very end of the chain; the word a single match polls; and a chained step's pose, or its fault:
+// a step that Karto would abort or repeat with a wider angle range.
+__device__ __forceinline__ void write_result(const FinishArgs &a, int b, YmItemState &st, int nq, const double (&cov)[9], const double (&mean)[3],
+                                             double response, double coarse_response, int status) {
+    for (int i = 0; i < 9; i++) st.cov[i] = cov[i];
+    for (int i = 0; i < 3; i++) { st.mean[i] = mean[i]; st.center[i] = mean[i]; }
+    st.response = response;
+    st.coarse_response = coarse_response;
+    st.status = status;
+    if (a.host_out) {
+        YmItemState *ho = a.host_out + b;
+        for (int i = 0; i < 9; i++) ho->cov[i] = cov[i];
+        for (int i = 0; i < 3; i++) { ho->mean[i] = mean[i]; ho->center[i] = mean[i]; }
+        ho->response = response;
+        ho->coarse_response = coarse_response;
+        ho->nq = nq;
+        ho->status = status;
+    }
+    if (a.host_flag) { __threadfence_system(); *reinterpret_cast<volatile uint32_t *>(a.host_flag) = a.serial; }
+    if (a.seq_pose) {
+        if (status != 0 || (a.expansion && kt_double_equal(coarse_response, 0.0))) atomicCAS(a.fault, 0, a.step);
+        chain_next_pose(a, mean);
+    }
 }
 
 // ---- K6b final: grid (B), 256 threads: fine arg-max / mean, angular covariance, result.
@@ -547,150 +712,36 @@ __global__ __launch_bounds__(YM_FINISH_THREADS) void final_kernel(FinishArgs a) 
     __shared__ double s_fresp[YM_MAX_FINE_HYP];
     __shared__ unsigned s_fsum[YM_MAX_FINE_HYP]; // the fine sums as loaded (the angular covariance reads one column of them)
     __shared__ unsigned s_asum[YM_MAX_FINE_NT];
-    __shared__ double2 s_trig[YM_MAX_FINE_NT];
-    __shared__ int s_hit[2];
+    __shared__ double2 s_trig[YM_MAX_FINE_NT];   // the fine tie table; a re-gather's (cos, sin) after it
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int lane = tid & 63;
     YM_STAMP(a, 16);
     // (the first fine sums leave together with the item's state, not a round trip after it)
     const uint32_t f0 = (a.refine && tid < a.lf.nx * a.lf.ny * a.lf.nt) ? a.fsums[(size_t)b * a.fsums_stride + tid] : 0u;
     YmItemState &st = a.states[b];
     const int nq = st.nq;
     if (nq == 0) {
-        // MatchScan: "scan has no readings; cannot do scan matching" -> pose, maximum covariance, 0
-        if (tid == 0) {
-            for (int i = 0; i < 9; i++) st.cov[i] = 0.0;
-            st.cov[0] = YM_MAX_VARIANCE; st.cov[4] = YM_MAX_VARIANCE;
-            st.cov[8] = 4 * (a.lc.angle_res * a.lc.angle_res);
-            for (int i = 0; i < 3; i++) { st.mean[i] = st.pose[i]; st.center[i] = st.pose[i]; }
-            st.response = 0.0;
-            st.coarse_response = 1.0; // nothing to retry with a wider angle
-            if (a.host_out) a.host_out[b] = st;
-            if (a.host_flag) { __threadfence_system(); *reinterpret_cast<volatile uint32_t *>(a.host_flag) = a.serial; }
-            if (a.seq_pose) chain_next_pose(a, st.pose);
-        }
+        if (tid == 0) no_readings_result(a, b, st);
         return;
     }
-    const uint8_t *grid = a.grid + (size_t)b * a.grid_stride;
-    const unsigned limit = (unsigned)(a.g.pitch * a.g.win_w);
     const double off_x = st.off_x, off_y = st.off_y;
-    double cov[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    double mean[3] = {st.center[0], st.center[1], st.center[2]}; // coarse mean (fine_kernel, block 0)
-    double best = st.coarse_response;                             // coarse best, unclamped
+    const double cmean[3] = {st.center[0], st.center[1], st.center[2]}; // coarse mean (fine_kernel's extra block)
+    double mean[3] = {cmean[0], cmean[1], cmean[2]};
+    double best = st.coarse_response;                                   // coarse best, unclamped
     int status = st.status;
-
-    // positional covariance of the coarse pass: computed by fine_kernel's extra block
+    double cov[9]; // positional covariance of the coarse pass: computed by fine_kernel's extra block
     for (int i = 0; i < 9; i++) cov[i] = st.cov[i];
     const double coarse_response = best > 1.0 ? 1.0 : best;
     double response = coarse_response;
-
-    // ------------------------------------------------------------- fine tail (CorrelateScan, doingFineMatch)
     if (a.refine) {
-        const YmLattice &L = a.lf;
-        const int nx = L.nx, ny = L.ny, nt = L.nt, nxy = nx * ny, nh = nxy * nt;
-        const double cxw = mean[0], cyw = mean[1], ct = mean[2];
-        const double start_x = -L.off_x, start_y = -L.off_y, start_angle = ct - L.angle_off;
         const uint32_t *fs = a.fsums + (size_t)b * a.fsums_stride;
-        double lb = -1.0;
-        tie_trig_table<NT>(L, start_angle, s_trig);
-        for (int h = tid; h < nh; h += NT) {
-            const int k = h / nxy, c = h - k * nxy, iy = c / nx, ix = c - iy * nx;
-            const double x = start_x + ix * L.step_x, y = start_y + iy * L.step_y;
-            const uint32_t fsum = h == tid ? f0 : fs[h];
-            const double r = hyp_response(a.g, L.penalize, fsum, nq, x * x + y * y, start_angle + k * L.angle_res, ct);
-            s_fresp[h] = r;
-            s_fsum[h] = fsum;
-            lb = r > lb ? r : lb;
-        }
-        for (int k = tid; k < nt; k += NT) s_asum[k] = 0u;
-        if (tid < 2) s_hit[tid] = -1;
-        best = block_reduce(lb, OpMaxD(), -1.0, scratch);
-        double acc[5] = {0, 0, 0, 0, 0};
-        for (int h = tid; h < nh && tid < YM_CANON; h += YM_CANON)
-            if (kt_double_equal(s_fresp[h], best)) tie_accumulate(acc, L, h, cxw, cyw, s_trig);
-        block_sum_vec_sparse<5>(acc, scratch, acc[4] != 0.0);
-        if (acc[4] > 0.0) {
-            const double cnt = acc[4];
-            mean[0] = acc[0] / cnt; mean[1] = acc[1] / cnt;
-            mean[2] = atan2(acc[3] / cnt, acc[2] / cnt);
-        } else {
-            status = -5;
-        }
+        tie_trig_table<NT>(a.lf, cmean[2] - a.lf.angle_off, s_trig);
+        best = fine_best_and_mean<NT>(a, nq, cmean, [&](int h) { const unsigned v = h == tid ? f0 : fs[h]; s_fsum[h] = v; return v; }, s_fresp, s_trig, scratch, mean, &status);
         YM_STAMP(a, 17);
-        // ComputeAngularCovariance: re-score every fine angle at the cell of the mean pose
-        const double best_angle = kt_normalize_angle_difference(mean[2], ct);
-        const int gx = world_to_grid(mean[0], off_x, a.g.scale) + a.g.border - a.g.win_origin;
-        const int gy = world_to_grid(mean[1], off_y, a.g.scale) + a.g.border - a.g.win_origin;
-        const int base = gy * lin_pitch(a.g) + gx;
-        const int32_t *foff = a.foffsets + (size_t)b * a.nt_stride * a.max_n;
-        // GetResponse(angle k, cell of the mean pose) uses the fine pass's own lookup offsets, so when that cell is one
-        // of the fine lattice's cells (always, unless fp rounding puts the tie mean outside) the sum IS the fine
-        // pass's integer sum for (k, that cell): take it instead of gathering the scan again.  Lattice column i is looked
-        // at by thread i, row i by thread 64 + i (the last match wins, as in a loop over i: the cells increase with i).
-        if (tid < nx && hyp_cell(cxw, start_x, tid, L.step_x, off_x, a.g) == gx) atomicMax(&s_hit[0], tid);
-        if (tid >= 64 && tid - 64 < ny && hyp_cell(cyw, start_y, tid - 64, L.step_y, off_y, a.g) == gy) atomicMax(&s_hit[1], tid - 64);
-        __syncthreads(); // s_asum cleared above, the hits in
-        const int hit_x = s_hit[0], hit_y = s_hit[1];
-        if (hit_x >= 0 && hit_y >= 0) {
-            for (int k = tid; k < nt; k += NT) s_asum[k] = s_fsum[k * nxy + hit_y * nx + hit_x];
-        } else {
-            // work item = (angle, beam); beams padded to whole waves so that a wave shares one angle
-            const int nq_pad = (nq + 63) & ~63;
-            const int total = nt * nq_pad;
-            for (int w0 = 0; w0 < total; w0 += 8 * NT) {
-                int kk[8];
-                unsigned idx[8], v[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const int w = w0 + u * NT + tid;
-                    kk[u] = w < total ? w / nq_pad : -1; // wave-uniform
-                    const int i = w - kk[u] * nq_pad;
-                    idx[u] = (kk[u] >= 0 && i < nq) ? (unsigned)(base + foff[(size_t)kk[u] * a.max_n + i]) : 0xffffffffu; // (never a cell)
-                }
-#pragma unroll
-                for (int u = 0; u < 8; u++) v[u] = cell_value(a.g, grid, limit, idx[u]);
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const unsigned sum = wave_reduce(v[u], OpAddU());
-                    if (lane == 0 && kk[u] >= 0) atomicAdd(&s_asum[kk[u]], sum);
-                }
-            }
-        }
-        __syncthreads();
-        double norm = 0.0;
-        double accv = angular_cov_sums<NT>(s_asum, nt, nq, start_angle, L.angle_res, best, best_angle, s_fresp, &norm);
-        if (norm > YM_KT_TOLERANCE) {
-            if (accv < YM_KT_TOLERANCE) accv = L.angle_res * L.angle_res;
-            accv /= norm;
-        } else {
-            accv = 1000 * (L.angle_res * L.angle_res);
-        }
-        cov[8] = accv;
+        cov[8] = angular_covariance<NT, false>(a, st, nq, a.grid + (size_t)b * a.grid_stride, off_x, off_y, cmean, mean, best, s_fsum, s_trig,
+                                               s_asum, s_fresp);
         response = best > 1.0 ? 1.0 : best;
     }
-    if (tid == 0) {
-        for (int i = 0; i < 9; i++) st.cov[i] = cov[i];
-        for (int i = 0; i < 3; i++) { st.mean[i] = mean[i]; st.center[i] = mean[i]; }
-        st.response = response;
-        st.coarse_response = coarse_response;
-        st.status = status;
-        if (a.host_out) {
-            // what the host reads of a result (state_to_result), straight from registers: copying `st` would first read
-            // the whole state back from device memory -- one more round trip at the very end of the chain
-            YmItemState *ho = a.host_out + b;
-            for (int i = 0; i < 9; i++) ho->cov[i] = cov[i];
-            for (int i = 0; i < 3; i++) { ho->mean[i] = mean[i]; ho->center[i] = mean[i]; }
-            ho->response = response;
-            ho->coarse_response = coarse_response;
-            ho->nq = nq;
-            ho->status = status;
-        }
-        if (a.host_flag) { __threadfence_system(); *reinterpret_cast<volatile uint32_t *>(a.host_flag) = a.serial; }
-        if (a.seq_pose) {
-            if (status != 0 || (a.expansion && kt_double_equal(coarse_response, 0.0))) atomicCAS(a.fault, 0, a.step);
-            chain_next_pose(a, mean);
-        }
-    }
+    if (tid == 0) write_result(a, b, st, nq, cov, mean, response, coarse_response, status);
     YM_STAMP(a, 19);
 }
 
@@ -722,16 +773,7 @@ __global__ __launch_bounds__(NT, NT == 256 ? YM_FINISH_OCC : 4 /* NT = 256: eigh
     YmItemState &st = a.states[b];
     const int nq = st.nq;
     if (nq == 0) {
-        // MatchScan: "scan has no readings; cannot do scan matching" -> pose, maximum covariance, 0
-        if (tid == 0) {
-            for (int i = 0; i < 9; i++) st.cov[i] = 0.0;
-            st.cov[0] = YM_MAX_VARIANCE; st.cov[4] = YM_MAX_VARIANCE;
-            st.cov[8] = 4 * (a.lc.angle_res * a.lc.angle_res);
-            for (int i = 0; i < 3; i++) { st.mean[i] = st.pose[i]; st.center[i] = st.pose[i]; }
-            st.response = 0.0;
-            st.coarse_response = 1.0; // nothing to retry with a wider angle
-            if (a.host_out) a.host_out[b] = st;
-        }
+        if (tid == 0) no_readings_result(a, b, st);
         return;
     }
     const double pose[3] = {st.pose[0], st.pose[1], st.pose[2]};
@@ -744,28 +786,21 @@ __global__ __launch_bounds__(NT, NT == 256 ? YM_FINISH_OCC : 4 /* NT = 256: eigh
     const double coarse_response = best > 1.0 ? 1.0 : best;
     const double cmean[3] = {mean[0], mean[1], mean[2]};
     double response = coarse_response;
-    const uint8_t *grid = a.grid + (size_t)b * a.grid_stride;
-    const unsigned limit = (unsigned)(a.g.pitch * a.g.win_w);
 
     if (a.refine) { // ------------------------------------------------ fine pass (CorrelateScan, doingFineMatch)
         const YmLattice &L = a.lf;
-        const int nx = L.nx, ny = L.ny, nt = L.nt, nxy = nx * ny, nh = nxy * nt;
-        const double cxw = cmean[0], cyw = cmean[1], ct = cmean[2];
-        const double start_x = -L.off_x, start_y = -L.off_y, start_angle = ct - L.angle_off;
+        const int nt = L.nt, nxy = L.nx * L.ny;
+        const double start_angle = cmean[2] - L.angle_off;
         for (int k = tid; k < nt; k += NT) {
             const double angle = start_angle + k * L.angle_res;
             s_cs[k] = make_double2(cos(angle), sin(angle));
         }
         tie_trig_table<NT>(L, start_angle, s_trig); // (the coarse table is done with: positional_covariance ends with barriers)
-        for (int i = tid; i < nx; i += NT) s_cx[i] = hyp_cell(cxw, start_x, i, L.step_x, off_x, a.g);
-        for (int i = tid; i < ny; i += NT) s_cy[i] = hyp_cell(cyw, start_y, i, L.step_y, off_y, a.g);
-        for (int h = tid; h < nh; h += NT) s_sum[h] = 0u;
-        __syncthreads();
+        const bool block3 = fine_lattice_setup<NT>(a, cmean, off_x, off_y, s_cx, s_cy, s_sum, nxy * nt);
+        const uint8_t *grid = a.grid + (size_t)b * a.grid_stride;
         const double2 *ql = reinterpret_cast<const double2 *>(st.ql);
-        const bool block3 = !a.g.kpitch && nx == 3 && ny == 3 && s_cx[1] == s_cx[0] + 1 && s_cx[2] == s_cx[0] + 2 &&
-                            s_cy[1] == s_cy[0] + 1 && s_cy[2] == s_cy[0] + 2;
         if (block3) {
-            // Karto's fine lattice is always 3x3 cells: a lane reads the 3x3 cell block under its beam as three 4-byte words.
+            // A lane reads the 3x3 cell block under its beam as three 4-byte words.
             // Round 5: the four lanes of a QUAD take the same beam at four consecutive fine angles -- 0.0035 rad apart, their
             // blocks lie a cell or two apart along the beam's arc, i.e. mostly in the same 128-byte line of a row, and the vector L1
             // charges a quad one clock per line it touches (this loop was the kernel: 0.63 line visits per CU and clock with
@@ -785,18 +820,10 @@ __global__ __launch_bounds__(NT, NT == 256 ? YM_FINISH_OCC : 4 /* NT = 256: eigh
                     for (int u = 0; u < 4; u++) {
                         const int ii = i0 + u * 16 + bl;
                         const int off = (ii < i_hi && kin) ? lookup_offset(ql[ii], cosine, sine, off_x, off_y, a.g.scale, a.g.pitch) : 0;
-                        const uint32_t idx = base0 + (uint32_t)off;
-#pragma unroll
-                        for (int r = 0; r < 3; r++) __builtin_memcpy(&w[u][r], grid + (uint32_t)(idx + r * a.g.pitch), 4);
+                        block3_load(w[u], grid, base0 + (uint32_t)off, a.g.pitch);
                     }
 #pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const uint32_t m = ((i0 + u * 16 + bl) < i_hi && kin) ? 0xffu : 0u;
-#pragma unroll
-                        for (int r = 0; r < 3; r++) {
-                            acc[3 * r] += w[u][r] & m; acc[3 * r + 1] += (w[u][r] >> 8) & m; acc[3 * r + 2] += (w[u][r] >> 16) & m;
-                        }
-                    }
+                    for (int u = 0; u < 4; u++) block3_accumulate(acc, w[u], ((i0 + u * 16 + bl) < i_hi && kin) ? 0xffu : 0u);
                 }
 #pragma unroll
                 for (int j = 0; j < 9; j++) {
@@ -806,86 +833,17 @@ __global__ __launch_bounds__(NT, NT == 256 ? YM_FINISH_OCC : 4 /* NT = 256: eigh
                 }
             }
         } else {
-            for (int k = wave; k < nt; k += NW) { // wave-uniform
-                const double cosine = s_cs[k].x, sine = s_cs[k].y;
-                // generic lattice: per beam, every (iy, ix) cell
-                for (int i = lane; i < nq; i += 64) {
-                    const int off = lookup_offset(ql[i], cosine, sine, off_x, off_y, a.g.scale, lin_pitch(a.g));
-                    for (int c = 0; c < nxy; c++) {
-                        const int iy = c / nx, ix = c - iy * nx;
-                        const unsigned v = cell_value(a.g, grid, limit, (unsigned)(s_cy[iy] * lin_pitch(a.g) + s_cx[ix] + off));
-                        if (v) atomicAdd(&s_sum[k * nxy + c], v);
-                    }
-                }
-            }
+            for (int k = wave; k < nt; k += NW) // wave-uniform
+                generic_gather(a, grid, ql, nq, s_cs[k], off_x, off_y, s_cx, s_cy, s_sum + k * nxy, lane, 64);
         }
         __syncthreads();
         uint32_t *fs = a.fsums + (size_t)b * a.fsums_stride; // kept for the parity tests
-        double lb = -1.0;
-        for (int h = tid; h < nh; h += NT) {
-            const int k = h / nxy, c = h - k * nxy, iy = c / nx, ix = c - iy * nx;
-            const double x = start_x + ix * L.step_x, y = start_y + iy * L.step_y;
-            const double r = hyp_response(a.g, L.penalize, s_sum[h], nq, x * x + y * y, start_angle + k * L.angle_res, ct);
-            s_fresp[h] = r;
-            fs[h] = s_sum[h];
-            lb = r > lb ? r : lb;
-        }
-        best = block_reduce(lb, OpMaxD(), -1.0, scratch);
-        double acc[5] = {0, 0, 0, 0, 0};
-        for (int h = tid; h < nh && tid < YM_CANON; h += YM_CANON)
-            if (kt_double_equal(s_fresp[h], best)) tie_accumulate(acc, L, h, cxw, cyw, s_trig);
-        block_sum_vec_sparse<5>(acc, scratch, acc[4] != 0.0);
-        if (acc[4] > 0.0) {
-            const double cnt = acc[4];
-            mean[0] = acc[0] / cnt; mean[1] = acc[1] / cnt;
-            mean[2] = atan2(acc[3] / cnt, acc[2] / cnt);
-        } else {
-            status = -5;
-        }
-        // ComputeAngularCovariance: GetResponse(angle k, cell of the mean pose) with the fine pass's lookup offsets is the
-        // fine pass's own sum whenever that cell is a cell of the fine lattice (always, unless fp rounding puts the
-        // tie mean outside); otherwise gather again.
-        const double best_angle = kt_normalize_angle_difference(mean[2], ct);
-        const int gx = world_to_grid(mean[0], off_x, a.g.scale) + a.g.border - a.g.win_origin;
-        const int gy = world_to_grid(mean[1], off_y, a.g.scale) + a.g.border - a.g.win_origin;
-        int hit_x = -1, hit_y = -1;
-        for (int i = 0; i < nx; i++) if (s_cx[i] == gx) hit_x = i;
-        for (int i = 0; i < ny; i++) if (s_cy[i] == gy) hit_y = i;
-        unsigned *s_asum = reinterpret_cast<unsigned *>(s_list); // free by now
-        __syncthreads();
-        if (hit_x >= 0 && hit_y >= 0) {
-            for (int k = tid; k < nt; k += NT) s_asum[k] = s_sum[k * nxy + hit_y * nx + hit_x];
-        } else {
-            const int base = gy * lin_pitch(a.g) + gx;
-            for (int k = wave; k < nt; k += NW) {
-                const double cosine = s_cs[k].x, sine = s_cs[k].y;
-                unsigned v = 0;
-                for (int i = lane; i < nq; i += 64)
-                    v += cell_value(a.g, grid, limit, (unsigned)(base + lookup_offset(ql[i], cosine, sine, off_x, off_y, a.g.scale, lin_pitch(a.g))));
-                v = wave_reduce(v, OpAddU());
-                if (lane == 0) s_asum[k] = v;
-            }
-        }
-        __syncthreads();
-        double norm = 0.0;
-        double accv = angular_cov_sums<NT>(s_asum, nt, nq, start_angle, L.angle_res, best, best_angle, s_fresp, &norm);
-        if (norm > YM_KT_TOLERANCE) {
-            if (accv < YM_KT_TOLERANCE) accv = L.angle_res * L.angle_res;
-            accv /= norm;
-        } else {
-            accv = 1000 * (L.angle_res * L.angle_res);
-        }
-        cov[8] = accv;
+        best = fine_best_and_mean<NT>(a, nq, cmean, [&](int h) { const unsigned v = s_sum[h]; fs[h] = v; return v; }, s_fresp, s_trig, scratch, mean, &status);
+        cov[8] = angular_covariance<NT, true>(a, st, nq, grid, off_x, off_y, cmean, mean, best, s_sum, s_cs,
+                                              reinterpret_cast<unsigned *>(s_list) /* free by now */, s_fresp);
         response = best > 1.0 ? 1.0 : best;
     }
-    if (tid == 0) {
-        for (int i = 0; i < 9; i++) st.cov[i] = cov[i];
-        for (int i = 0; i < 3; i++) { st.mean[i] = mean[i]; st.center[i] = mean[i]; }
-        st.response = response;
-        st.coarse_response = coarse_response;
-        st.status = status;
-        if (a.host_out) a.host_out[b] = st;
-    }
+    if (tid == 0) write_result(a, b, st, nq, cov, mean, response, coarse_response, status);
 }
 
 // ================================================================== K7 arg-best over the items of a call

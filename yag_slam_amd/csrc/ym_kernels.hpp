@@ -11,7 +11,10 @@
 //   score_kernel      partial sums -> sums -> response (+ penalty), per-block maxima
 //   finish_kernel     coarse arg-max / tie mean / positional covariance, then the whole fine pass
 //                     (offsets, 3x3xN correlate, arg-max, angular covariance) in one block per item
-//                     (CorrelateScan tail, ComputePositionalCovariance, ComputeAngularCovariance)
+//                     (CorrelateScan tail, ComputePositionalCovariance, ComputeAngularCovariance); for few items
+//                     fine_kernel (a block per fine angle) + final_kernel.  Both forms are made of the same pieces,
+//                     each stated once in ym_k_finish.hpp: coarse_best_and_mean, positional_covariance,
+//                     fine_lattice_setup, generic_gather, fine_best_and_mean, angular_covariance, write_result
 // All fp64 arithmetic is written operation-for-operation like oracle/ym_oracle.c and the library is
 // compiled with -ffp-contract=off, so responses are bit-identical to the oracle's.
 #pragma once
