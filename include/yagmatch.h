@@ -822,6 +822,31 @@ typedef struct ym_pair_list_info {
 int ym_debug_pair_lists(ym_matcher *m, int slot, ym_pair_list_info *info, double *ctrig, int32_t *starts, int32_t *flags,
                         uint16_t *entries, uint32_t *rbox);
 
+/* test hook: what find_best_pose pass `pass` (0 coarse, 1 fine) of item `item` of the last synchronous YM_SEM_YAGPY call computed with --
+ * the last call being a chain call (ym_match_scans, ym_match_batch, ym_match_pairs; kind 0), a map call (ym_match_map,
+ * ym_match_map_many, ym_map_track; kind 1) or a set call (ym_match_sets, ym_match_sets_many; kind 2).  With it the rule
+ * np.round(((xvals[i] + r) - o) / res) can be restated on the host from the device's own operands (tests/yag_ties_ref.py): everything
+ * after the cosines, the sines and the points is IEEE arithmetic.  It reads only and changes no result.  With the three arrays NULL
+ * only *info is filled (the sizes to allocate); otherwise all three are written, and nothing is written when the call fails:
+ *   axes    [nx + ny + nt]  xvals, yvals, tvals: numpy.arange's values as the device computes them, computed again from the item's state
+ *   trig    [nt][2]         cos, sin of tvals[k] as the kernels of the pass take them (the same functions on the same operand)
+ *   points  [nq][2]         the item's point set: sensor-frame readings (kind 0), the world readings moved by the set's centre (1, 2) */
+typedef struct ym_yag_frame {
+    int32_t kind, pass;
+    int32_t nx, ny, nt, nq;
+    int32_t grid_w, grid_h;          /* the grid of the rule's bounds test: cells (0 .. grid_w, 0 .. grid_h) count */
+    int32_t roi_w;                   /* the matcher's grid side G (the lattice guard's M = |ox| + |oy| + 2 G res) */
+    int32_t win_origin, win_w, pitch; /* the device window inside that grid (kind 0; the whole grid otherwise) and its row pitch */
+    int32_t lat_nx, lat_ny, lat_nt;  /* kind 0, pass 0: the lattice the production correlate kernels were launched on (0: they were not) */
+    int32_t step_cells;              /* ... and its step in cells */
+    int32_t regular;                 /* kind 0: the lattice proof's decision for the item */
+    int32_t map_split;               /* kinds 1, 2: blocks that shared an (item, angle) of the coarse pass */
+    double ox, oy, res;              /* the corner and the cell size the pass indexed with */
+    double search_xy, step_xy, search_t, step_t; /* find_best_pose's arguments */
+    double centre[3];                /* ... and its search centre */
+} ym_yag_frame;
+int ym_debug_yag_frame(ym_matcher *m, int item, int pass, ym_yag_frame *info, double *axes, double *trig, double *points);
+
 /* Switches of the parity tests: every row names a path the tests force so that each kernel and each host decision is compared with
  * the oracle (or with the default path) bit for bit.  None changes a result.  Development and timing switches that no test uses
  * (2 - 5, 9, 23, 26, 29, 34, 36, 38, 40, 42) are described where they are implemented, yag_slam_amd/csrc/ym_abi_debug.hpp.

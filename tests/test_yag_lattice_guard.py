@@ -9,7 +9,9 @@ form the lattice c(0) + 2 i.  It proves that per pair from hypothesis 0 alone: |
 guard = 8 (n + 8) 2^-53 M / res + 2^-40, M = |ox| + |oy| + 2 G res.  This file restates that predicate in numpy and attacks it:
 readings are placed so that u(0) lands within 1e-15 .. 1e-8 cells of a rounding tie, at poses up to 10 km from the origin.
 Whenever the predicate holds the lattice must hold for every i; and the attack must be real -- some of the pairs it rejects are
-indeed irregular.  (No device code runs here; the device's own decision is tested in tests/test_gpu_parity.py.)"""
+indeed irregular.  (No device code runs here: this is a numpy copy of the predicates.  The device's own decision, pair counts and sums on readings
+aimed at its own operands -- inside the guard, just outside it, on genuinely irregular ties, and where yag_rint_div's product and quotient part --
+are tested in tests/test_gpu_yag_ties.py against tests/yag_ties_ref.py.)"""
 import numpy as np
 import pytest
 

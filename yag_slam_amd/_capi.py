@@ -20,7 +20,7 @@ EXPORTS = (
     "ym_match_scans_async", "ym_wait", "ym_match_batch", "ym_batch_create", "ym_batch_destroy", "ym_batch_size",
     "ym_match_pairs", "ym_pairs_create",
     "ym_batch_run_async", "ym_batch_wait", "ym_debug_grid_info",
-    "ym_debug_grid", "ym_debug_sums", "ym_debug_query_local", "ym_debug_cells", "ym_debug_pair_lists", "ym_debug_option", "ym_debug_stamps", "ym_debug_live_bytes",
+    "ym_debug_grid", "ym_debug_sums", "ym_debug_query_local", "ym_debug_cells", "ym_debug_pair_lists", "ym_debug_yag_frame", "ym_debug_option", "ym_debug_stamps", "ym_debug_live_bytes",
     "ym_profile_enable",
     "ym_profile_read", "ym_cache_stats", "ym_debug_counters",
     "ym_coarse_dims", "ym_match_slice_begin", "ym_match_slice_finish",
@@ -150,6 +150,12 @@ class YmPairListInfo(C.Structure):
         ("entries_pstride", C.c_int64), ("off_x", C.c_double), ("off_y", C.c_double), ("ylat", C.c_double * 2)]
 
 
+class YmYagFrame(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kind", "pass_", "nx", "ny", "nt", "nq", "grid_w", "grid_h", "roi_w", "win_origin", "win_w", "pitch",
+                                        "lat_nx", "lat_ny", "lat_nt", "step_cells", "regular", "map_split")] + [
+        (n, C.c_double) for n in ("ox", "oy", "res", "search_xy", "step_xy", "search_t", "step_t")] + [("centre", C.c_double * 3)]
+
+
 class YmOptParams(C.Structure):
     _fields_ = [("iters", C.c_int32), ("exact", C.c_int32), ("max_cg_iters", C.c_int32), ("band", C.c_int32),
                 ("lambda0", C.c_double), ("cg_tol", C.c_double)]
@@ -273,6 +279,7 @@ def lib():
     L.ym_debug_query_local.argtypes = [vp, C.c_int, dp, C.c_int32, ip]
     L.ym_debug_cells.argtypes = [vp, C.c_int, ip, C.c_int64, ip]
     L.ym_debug_pair_lists.argtypes = [vp, C.c_int, C.POINTER(YmPairListInfo), dp, ip, ip, C.POINTER(C.c_uint16), C.POINTER(C.c_uint32)]
+    L.ym_debug_yag_frame.argtypes = [vp, C.c_int, C.c_int, C.POINTER(YmYagFrame), dp, dp, dp]
     L.ym_debug_option.argtypes = [vp, C.c_int, C.c_int]
     L.ym_debug_stamps.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64), C.c_int32]
     L.ym_debug_live_bytes.argtypes = [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

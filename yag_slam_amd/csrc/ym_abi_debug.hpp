@@ -152,6 +152,68 @@ int ym_debug_pair_lists(ym_matcher *m, int slot, ym_pair_list_info *info, double
     return YM_OK;
 }
 
+// what find_best_pose pass `pass` of item `item` of the last YM_SEM_YAGPY call computed with (include/yagmatch.h).  Reads only.
+int ym_debug_yag_frame(ym_matcher *m, int item, int pass, ym_yag_frame *info, double *axes, double *trig, double *points) {
+    if (!m || !info || pass < 0 || pass > 1) return set_err(YM_ERR_INVALID, "bad argument");
+    if (m->cfg.semantics != YM_SEM_YAGPY) return set_err(YM_ERR_UNSUPPORTED, "ym_debug_yag_frame needs a YM_SEM_YAGPY matcher");
+    const ym_matcher::YagFrameLast &fl = m->yag_frame_last;
+    const bool chain = m->last_valid, sets = sets_debug(m);
+    const int kind = chain ? 0 : sets ? 2 : 1;
+    if ((!chain && !m->map_last.valid) || fl.kind != kind) return set_err(YM_ERR_INVALID, "the last call left no frame");
+    if (item < 0 || item >= (chain ? m->last_B : m->map_last.n_items)) return set_err(YM_ERR_INVALID, "no such item in the last call");
+    if (pass >= fl.passes) return set_err(YM_ERR_INVALID, "pass %d did not run", pass);
+    const int n_out = (axes != nullptr) + (trig != nullptr) + (points != nullptr);
+    if (n_out != 0 && n_out != 3) return set_err(YM_ERR_INVALID, "all three arrays or none");
+    const ym_matcher::YagFrameLast::Pass &fp = fl.pass[pass];
+    YmItemState s;
+    DEV_GUARD(m->device);
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    HIP_TRY(hipMemcpy(&s, m->states.p + item, sizeof s, hipMemcpyDeviceToHost));
+    ym_yag_frame o;
+    std::memset(&o, 0, sizeof o);
+    o.kind = kind; o.pass = pass; o.nx = s.ydims[pass][0]; o.ny = s.ydims[pass][1]; o.nt = s.ydims[pass][2]; o.nq = s.nq;
+    o.grid_w = fp.grid_w; o.grid_h = fp.grid_h; o.roi_w = fl.roi_w; o.win_origin = fl.win_origin; o.win_w = fl.win_w; o.pitch = fl.pitch;
+    o.lat_nx = fl.lat_nx; o.lat_ny = fl.lat_ny; o.lat_nt = fl.lat_nt; o.step_cells = fl.step_cells;
+    o.regular = s.regular[0]; o.map_split = fl.map_split;
+    o.ox = fp.own_origin ? s.off_x : fp.ox; o.oy = fp.own_origin ? s.off_y : fp.oy; o.res = fp.res;
+    o.search_xy = fp.search_xy; o.step_xy = fp.step_xy; o.search_t = fp.search_t; o.step_t = fp.step_t;
+    for (int i = 0; i < 3; i++) o.centre[i] = pass ? s.ybest[0][1 + i] : s.pose[i];
+    if (o.nx < 0 || o.ny < 0 || o.nt < 0 || o.nx > YM_YAG_MAX_DIM || o.ny > YM_YAG_MAX_DIM || o.nt > YM_YAG_MAX_DIM || o.nq < 0)
+        return set_err(YM_ERR_HIP, "item %d has an impossible lattice (a fault of the library)", item);
+    if (n_out == 0) { *info = o; return YM_OK; }
+    const size_t n_axes = (size_t)o.nx + o.ny + o.nt;
+    DevBuf<double> d_axes;
+    DevBuf<double2> d_trig;
+    int rc;
+    if ((rc = d_axes.alloc(std::max<size_t>(n_axes, 1))) || (rc = d_trig.alloc((size_t)std::max(o.nt, 1)))) return rc;
+    ym::YagFrameArgs a;
+    a.state = m->states.p + item; a.pass = pass;
+    a.search_xy = fp.search_xy; a.step_xy = fp.step_xy; a.search_t = fp.search_t; a.step_t = fp.step_t;
+    a.axes = d_axes.p; a.trig = d_trig.p;
+    hipLaunchKernelGGL(ym::yag_frame_kernel, dim3(1), dim3(256), 0, m->stream, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    // (into buffers of the library's own first: a copy that fails leaves the caller's arrays as they were)
+    std::vector<double> h_axes(n_axes), h_trig((size_t)2 * o.nt), h_pts((size_t)2 * o.nq);
+    if (n_axes) HIP_TRY(hipMemcpy(h_axes.data(), d_axes.p, sizeof(double) * n_axes, hipMemcpyDeviceToHost));
+    if (o.nt) HIP_TRY(hipMemcpy(h_trig.data(), d_trig.p, sizeof(double2) * o.nt, hipMemcpyDeviceToHost));
+    if (o.nq) HIP_TRY(hipMemcpy(h_pts.data(), s.ql, sizeof(double2) * o.nq, hipMemcpyDeviceToHost));
+    if (chain && pass == fl.passes - 1) {
+        // the axes buffer still holds this pass's axes of every item of a chain call: the recomputed ones must be those, bit for bit
+        std::vector<double> live((size_t)3 * YM_YAG_MAX_DIM);
+        HIP_TRY(hipMemcpy(live.data(), m->yaxes.p + (size_t)item * 3 * YM_YAG_MAX_DIM, sizeof(double) * live.size(), hipMemcpyDeviceToHost));
+        const int n[3] = {o.nx, o.ny, o.nt};
+        for (int ax = 0, at = 0; ax < 3; at += n[ax], ax++)
+            if (std::memcmp(live.data() + (size_t)ax * YM_YAG_MAX_DIM, h_axes.data() + at, sizeof(double) * n[ax]))
+                return set_err(YM_ERR_HIP, "item %d: the recomputed axes of pass %d are not the ones the pass used (a fault of the library)", item, pass);
+    }
+    *info = o;
+    std::memcpy(axes, h_axes.data(), sizeof(double) * n_axes);
+    std::memcpy(trig, h_trig.data(), sizeof(double) * h_trig.size());
+    std::memcpy(points, h_pts.data(), sizeof(double) * h_pts.size());
+    return YM_OK;
+}
+
 // The options the parity tests use are tabulated in include/yagmatch.h.  The others -- development and timing switches:
 //    2  rasterise every tile of the window                      3  beams in flight per lane in the direct correlate (16 / 32 / 48)
 //    4  extra dynamic LDS bytes per direct-correlate block        5  beam chunks per angle of the direct correlate

@@ -144,6 +144,22 @@ inline void yag_fine_search(ym::YagArgs &a, double res) {
     a.search_xy = res * 2; a.step_xy = res; a.search_t = 0.0349 * 0.5; a.step_t = 0.00349;
 }
 
+// what a pass indexed with, kept for ym_debug_yag_frame (ym_abi_debug.hpp).  kind: 0 chain call, 1 map call, 2 set call
+inline void yag_frame_record(ym_matcher *m, const ym::YagArgs &a, int kind) {
+    ym_matcher::YagFrameLast &f = m->yag_frame_last;
+    const bool map = a.map_w > 0;
+    f.kind = kind; f.passes = a.pass + 1;
+    ym_matcher::YagFrameLast::Pass &p = f.pass[a.pass];
+    p.search_xy = a.search_xy; p.step_xy = a.step_xy; p.search_t = a.search_t; p.step_t = a.step_t;
+    p.res = map ? a.map_res : a.g.res; p.ox = a.map_ox; p.oy = a.map_oy;
+    p.own_origin = !map || a.map_sets; // (the corner is the item state's off_x, off_y)
+    p.grid_w = map ? a.map_w : a.g.roi_w; p.grid_h = map ? a.map_h : a.g.roi_w;
+    if (a.pass == 0) {
+        f.roi_w = a.g.roi_w; f.win_origin = map ? 0 : a.g.win_origin; f.win_w = map ? a.map_w : a.g.win_w; f.pitch = map ? a.map_w : a.g.pitch;
+        f.lat_nx = a.lat_nx; f.lat_ny = a.lat_ny; f.lat_nt = a.lat_nt; f.step_cells = a.step_cells; f.map_split = a.map_split;
+    }
+}
+
 // ---- the Python matcher's two find_best_pose passes (scan_matching.py:204-214)
 int enqueue_yagpy_passes(ym_matcher *m, Slot &slot, const CallPlan &P) {
     const Call &call = slot.call;
@@ -187,6 +203,7 @@ int enqueue_yagpy_passes(ym_matcher *m, Slot &slot, const CallPlan &P) {
             if (P.B >= 64) hipLaunchKernelGGL(ym::yag_fine_kernel<64>, dim3(8 * P.ymaxt * ((P.B + 7) / 8)), dim3(64), 0, m->stream, a);
             else hipLaunchKernelGGL(ym::yag_fine_kernel<256>, dim3(8 * P.ymaxt * ((P.B + 7) / 8)), dim3(256), 0, m->stream, a);
         }
+        yag_frame_record(m, a, 0);
         hipLaunchKernelGGL(ym::yag_score_kernel, dim3((P.ymaxd * P.ymaxd + 255) / 256, P.ymaxt, P.B), dim3(256), 0, m->stream, a);
         if (P.B >= 16) hipLaunchKernelGGL(ym::yag_reduce_kernel<256>, dim3(P.B), dim3(256), 0, m->stream, a);
         else hipLaunchKernelGGL(ym::yag_reduce_kernel<1024>, dim3(P.B), dim3(1024), 0, m->stream, a);

@@ -137,6 +137,7 @@ int enqueue_yag_batch_pass(ym_matcher *m, Slot &slot, const YagBatch &S, int c0,
     // a few items alone leave the device empty: their (item, angle) blocks are split until about four blocks per CU exist
     const int split = std::max(1, std::min(32, 1024 / (B * maxt)));
     a.map_split = split;
+    yag_frame_record(m, a, S.map_sets ? 2 : 1);
     hipLaunchKernelGGL(ym::yag_setup_kernel, dim3(1, B), dim3(256), 0, st, a);
     hipEvent_t ev_k = nullptr;
     int rc;

@@ -173,6 +173,14 @@ struct ym_matcher {
     // what the debug getters need of the last set call (valid only while map_last is, and only for a set call): the grid's side, the
     // bytes between two items' grids, the first item whose grid is still there (the last chunk's)
     struct SetsLast { bool valid = false; int G = 0, first_grid = 0; size_t grid_stride = 0; } sets_last;
+    // what ym_debug_yag_frame needs of the last "yagpy" call (a chain call, a map call or a set call): per find_best_pose pass the
+    // search it ran, the cell size and corner it indexed with and the grid its bounds test used; the launch lattice of a chain
+    // call's coarse pass.  A few numbers copied per pass; nothing reads them but that hook.
+    struct YagFrameLast {
+        int kind = -1, passes = 0; // 0 chain call, 1 map call, 2 set call
+        struct Pass { double search_xy, step_xy, search_t, step_t, res, ox, oy; int own_origin, grid_w, grid_h; } pass[2];
+        int roi_w = 0, win_origin = 0, win_w = 0, pitch = 0, lat_nx = 0, lat_ny = 0, lat_nt = 0, step_cells = 0, map_split = 0;
+    } yag_frame_last;
     DevBuf<double2> yrot;      // yagpy: points rotated per angle
     DevBuf<double> seq_pose;   // device-chained sequences: [0..2] the next step's odometry prior, [4 + 3k ..] the pose step k of the segment found
     DevBuf<int32_t> seq_fault; // ... and the first step the host has to repeat (0: none)

@@ -100,6 +100,32 @@ __global__ __launch_bounds__(256) void yag_setup_kernel(YagArgs a) {
     for (int l = tid; l < st.nq; l += 256) rot[l] = yag_rotate(ql[l], c, s);
 }
 
+// Test hook (ym_debug_yag_frame): the axes of one pass of one finished item, computed again from its state as yag_setup_kernel computed
+// them (yag_arange_at on the same operands; the pass's lengths are the state's), and the (cos, sin) of every angle as the kernels of the
+// pass take them: cos and sin of tvals[k], the value yag_arange_at gives and the axes buffer holds.  One block; reads the state only.
+struct YagFrameArgs {
+    const YmItemState *state;
+    int32_t pass;
+    double search_xy, step_xy, search_t, step_t;
+    double *axes;  // xvals[nx], yvals[ny], tvals[nt]
+    double2 *trig; // [nt]
+};
+__global__ __launch_bounds__(256) void yag_frame_kernel(YagFrameArgs a) {
+    const YmItemState &st = *a.state;
+    const int tid = threadIdx.x;
+    const double cx = a.pass ? st.ybest[0][1] : st.pose[0];
+    const double cy = a.pass ? st.ybest[0][2] : st.pose[1];
+    const double ct = a.pass ? st.ybest[0][3] : st.pose[2];
+    const int nx = st.ydims[a.pass][0], ny = st.ydims[a.pass][1], nt = st.ydims[a.pass][2];
+    for (int i = tid; i < nx; i += 256) a.axes[i] = yag_arange_at(-a.search_xy + cx, a.step_xy, i);
+    for (int i = tid; i < ny; i += 256) a.axes[nx + i] = yag_arange_at(-a.search_xy + cy, a.step_xy, i);
+    for (int k = tid; k < nt; k += 256) {
+        const double t = yag_arange_at(-a.search_t + ct, a.step_t, k);
+        a.axes[nx + ny + k] = t;
+        a.trig[k] = make_double2(cos(t), sin(t));
+    }
+}
+
 // When do the roundings of the coarse pass form a lattice?  (helpers.py:149-153 with x = xvals[i] + xx, helpers.py:194-196.)
 // For a (point, angle) pair with rotated coordinate r, hypothesis i of an axis reads cell
 //     c(i) = rint(u(i)),   u(i) = fl(fl(fl(xv[i] + r) - o) / res),   xv[i] = numpy.arange's i-th value (yag_arange_at).

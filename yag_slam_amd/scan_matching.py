@@ -723,6 +723,24 @@ class ScanMatcher(object):
                    rbox=np.stack([rbox & 255, (rbox >> 8) & 255, (rbox >> 16) & 255, rbox >> 24], axis=-1).astype(np.int32))
         return out
 
+    def debug_yag_frame(self, item=0, pass_=0):
+        """What find_best_pose pass `pass_` of item `item` of the last "yagpy" call computed with (include/yagmatch.h,
+        ym_debug_yag_frame): a dict of the pass's geometry, `xvals`, `yvals`, `tvals`, `trig` [nt][2] = the device's (cos, sin) of
+        every angle and `points` [nq][2] = the item's point set."""
+        info = _capi.YmYagFrame()
+        _capi.check(self._lib.ym_debug_yag_frame(self._m, int(item), int(pass_), C.byref(info), None, None, None))
+        axes = np.zeros(info.nx + info.ny + info.nt)
+        trig = np.zeros((info.nt, 2))
+        pts = np.zeros((info.nq, 2))
+        dp = C.POINTER(C.c_double)
+        _capi.check(self._lib.ym_debug_yag_frame(self._m, int(item), int(pass_), C.byref(info), axes.ctypes.data_as(dp),
+                                                 trig.ctypes.data_as(dp), pts.ctypes.data_as(dp)))
+        out = {n: (int if t is C.c_int32 else float)(getattr(info, n)) for n, t in _capi.YmYagFrame._fields_[:-1]}
+        out["pass"] = out.pop("pass_")
+        out.update(centre=tuple(info.centre), xvals=axes[:info.nx].copy(), yvals=axes[info.nx:info.nx + info.ny].copy(),
+                   tvals=axes[info.nx + info.ny:].copy(), trig=trig, points=pts)
+        return out
+
     def debug_option(self, option, value):
         _capi.check(self._lib.ym_debug_option(self._m, int(option), int(value)))
 
