@@ -581,7 +581,21 @@ void ym_raymap_destroy(ym_raymap *rm);
  *                        n_angles * W * H must stay below 2^40 (YM_ERR_UNSUPPORTED).  Synchronous; never throws.
  *                        YM_ERR_INVALID: a null argument, n_queries outside [1, 64], a query that is null or on another device,
  *                        n_angles outside [1, 65536], top_k outside [1, 64], point_stride < 1 or no valid reading, min_response < 0.
- *                        On an error nothing is written. */
+ *                        On an error nothing is written.
+ *   ym_locator_locate_places  the n_places best DISTINCT places (1 .. 16) under the same definition, point set, offsets, S, floor
+ *                        ceil(min_response * 100 * nq) and total order.  Hypothesis (k, x, y) is NEAR a pick (k', x', y') iff
+ *                        (x - x')^2 + (y - y')^2 <= sep_cells2 AND dk <= sep_headings, dk = |k - k'| and, with circular = 1,
+ *                        dk = min(dk, n_angles - dk) (integers only).  Place 1 is the best hypothesis; place i + 1 the best one
+ *                        that is near none of places 1 .. i; the list ends after n_places entries or when no hypothesis is left
+ *                        -- exactly this list whatever `levels`, max_nodes or the launch order are.  Both separations 0: the
+ *                        top n_places of ym_locator_locate.  n_places = 1: its top 1.  Every place is a search of its own
+ *                        (branch and bound with top_k = 1 and the picks so far excluded), which is why n_places stops at 16.
+ *                        out holds n_places entries; points_out as above; stats (nullable): nq, rounds = searches run (the places
+ *                        found, + 1 if the last search found none), chunks, nodes the exact passes and the probes scored, summed
+ *                        over the rounds and per round (round_nodes[i] = exact-pass + probe nodes of round i), and the leaves
+ *                        (level 0) and nodes (above) the exact passes dropped unscored because all they cover is near a pick.
+ *                        Checks, limits and codes are ym_locator_locate's; YM_ERR_INVALID besides: opts null, n_places outside
+ *                        [1, 16], sep_cells2 < 0, sep_headings < 0, circular not 0 or 1.  On an error nothing is written. */
 typedef struct ym_locator ym_locator;
 typedef struct ym_locator_info {
     int32_t width, height, levels, reserved;
@@ -610,6 +624,21 @@ int ym_locator_read_level(const ym_locator *lc, int level, uint8_t *out, int64_t
 int ym_locator_locate(ym_locator *lc, double ox, double oy, const ym_scan *const *queries, int n_queries, const double *dir_cs,
                       int n_angles, const ym_locate_opts *opts, ym_locate_candidate *out, int *n_found, double *points_out,
                       ym_locate_stats *stats);
+typedef struct ym_locate_places_opts {
+    int32_t n_places, point_stride;      /* 1 .. 16; >= 1 */
+    double  min_response;                /* >= 0 */
+    int64_t sep_cells2;                  /* >= 0 */
+    int32_t sep_headings, circular;      /* >= 0; 0 or 1 */
+} ym_locate_places_opts;
+typedef struct ym_locate_places_stats {
+    int32_t nq, rounds;                  /* rounds = searches run (places found, + 1 if the last found none) */
+    int64_t chunks, nodes, probe_nodes;  /* summed over the rounds */
+    int64_t excluded_leaves, excluded_nodes;
+    int64_t round_nodes[16];             /* exact-pass + probe nodes scored in each round */
+} ym_locate_places_stats;
+int ym_locator_locate_places(ym_locator *lc, double ox, double oy, const ym_scan *const *queries, int n_queries, const double *dir_cs,
+                             int n_angles, const ym_locate_places_opts *opts /* not null */, ym_locate_candidate *out /* n_places entries */,
+                             int *n_found, double *points_out, ym_locate_places_stats *stats);
 void ym_locator_destroy(ym_locator *lc);
 
 /* ---- the segment graph of a prior map from its label image: the rest of map_to_graph (yag_slam/splicing.py:57-80 of the

@@ -34,7 +34,7 @@ EXPORTS = (
     "ym_map_create_counted", "ym_map_update_scans", "ym_map_counted", "ym_map_read_stamps",
     "ym_map_reframe", "ym_map_window", "ym_map_create_counted_window",
     "ym_raymap_create", "ym_raymap_trace", "ym_raymap_trace_each", "ym_raymap_destroy",
-    "ym_locator_create", "ym_locator_get_info", "ym_locator_read_level", "ym_locator_locate", "ym_locator_destroy",
+    "ym_locator_create", "ym_locator_get_info", "ym_locator_read_level", "ym_locator_locate", "ym_locator_locate_places", "ym_locator_destroy",
     "ym_segments_create", "ym_segments_label_range", "ym_segments_stats", "ym_segments_boundaries", "ym_segments_pairs",
     "ym_segments_destroy", "ym_map_free_space", "ym_segments_from_map", "ym_segments_labels",
     "ym_graph_create", "ym_graph_destroy", "ym_graph_add_nodes", "ym_graph_add_constraints", "ym_graph_size", "ym_graph_set_poses",
@@ -193,6 +193,16 @@ class YmLocateCandidate(C.Structure):
 class YmLocateStats(C.Structure):
     _fields_ = [("nq", C.c_int32), ("chunks", C.c_int32), ("nodes", C.c_int64 * 9), ("survivors", C.c_int64 * 9),
                 ("probe_nodes", C.c_int64)]
+
+
+class YmLocatePlacesOpts(C.Structure):
+    _fields_ = [("n_places", C.c_int32), ("point_stride", C.c_int32), ("min_response", C.c_double), ("sep_cells2", C.c_int64),
+                ("sep_headings", C.c_int32), ("circular", C.c_int32)]
+
+
+class YmLocatePlacesStats(C.Structure):
+    _fields_ = [("nq", C.c_int32), ("rounds", C.c_int32), ("chunks", C.c_int64), ("nodes", C.c_int64), ("probe_nodes", C.c_int64),
+                ("excluded_leaves", C.c_int64), ("excluded_nodes", C.c_int64), ("round_nodes", C.c_int64 * 16)]
 
 
 SEGMENT_STAGES = {"final": 0, "assigned": 1}
@@ -360,6 +370,8 @@ def lib():
     L.ym_locator_read_level.argtypes = [vp, C.c_int, C.POINTER(C.c_uint8), C.c_int64]
     L.ym_locator_locate.argtypes = [vp, C.c_double, C.c_double, C.POINTER(vp), C.c_int, dp, C.c_int, C.POINTER(YmLocateOpts),
                                     C.POINTER(YmLocateCandidate), C.POINTER(C.c_int), dp, C.POINTER(YmLocateStats)]
+    L.ym_locator_locate_places.argtypes = [vp, C.c_double, C.c_double, C.POINTER(vp), C.c_int, dp, C.c_int, C.POINTER(YmLocatePlacesOpts),
+                                           C.POINTER(YmLocateCandidate), C.POINTER(C.c_int), dp, C.POINTER(YmLocatePlacesStats)]
     L.ym_locator_destroy.argtypes = [vp]
     L.ym_locator_destroy.restype = None
     lp = C.POINTER(C.c_int64)

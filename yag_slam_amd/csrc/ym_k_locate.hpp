@@ -17,6 +17,7 @@ namespace ym {
 
 constexpr int kLocMaxLevels = 8;
 constexpr int kLocMaxTop = 64;
+constexpr int kLocMaxExcl = 15;    // picks a places search excludes (ym_locator_locate_places: at most 16 places)
 constexpr int kLocTile = 8192;     // points of one heading staged in LDS at a time (32 KB)
 constexpr int kLocThreads = 256;
 constexpr uint64_t kLocIndexMask = (1ull << 40) - 1;
@@ -37,6 +38,9 @@ struct LocState {
     uint64_t top[kLocMaxTop]; // keys, best first
     uint64_t beam[kLocMaxTop]; // the probe: keys (bound, position in the probed frontier) of the nodes it follows
     int32_t n_beam, pad2;
+    // a places search: the picks so far (k, cx, cy, 0) and what the exact pass dropped because it was near one of them
+    unsigned long long excluded_leaves, excluded_nodes;
+    int32_t excl[kLocMaxExcl][4];
 };
 
 __device__ __forceinline__ uint64_t loc_node(uint32_t k, uint32_t x, uint32_t y) { return (uint64_t)k << 32 | (uint64_t)y << 16 | x; }
@@ -105,7 +109,28 @@ struct LocScoreArgs {
     int32_t level, W, H;
     int32_t s_min;
     LocState *st;
+    // the exclusion of a places search (read by the EXCL instantiations only): st->excl[0 .. n_excl)
+    int32_t n_excl, sep_headings, circular, n_angles;
+    int64_t sep_cells2;
 };
+
+// Is every hypothesis of node (k, X, Y) of level a.level near one pick?  Near: dk <= sep_headings (dk = |k - k'|, on a circle
+// of n_angles headings when `circular`) and (x - x')^2 + (y - y')^2 <= sep_cells2.  The node's square is clipped to the map;
+// its farthest corner from the pick decides.  At level 0 this is the leaf test itself.  Integers only; at most kLocMaxExcl turns.
+__device__ __forceinline__ bool loc_excluded(const LocScoreArgs &a, int k, int X, int Y) {
+    const int side = 1 << a.level;
+    const int x1 = min(X + side, a.W) - 1, y1 = min(Y + side, a.H) - 1;
+    const int n = min(a.n_excl, kLocMaxExcl);
+    bool hit = false;
+    for (int e = 0; e < n; e++) {
+        const int pk = a.st->excl[e][0], px = a.st->excl[e][1], py = a.st->excl[e][2];
+        int dk = abs(k - pk);
+        if (a.circular) dk = min(dk, a.n_angles - dk);
+        const int64_t dx = max(abs(X - px), abs(x1 - px)), dy = max(abs(Y - py), abs(y1 - py));
+        hit |= dk <= a.sep_headings && dx * dx + dy * dy <= a.sep_cells2;
+    }
+    return hit;
+}
 
 __device__ __forceinline__ int loc_wave_scan(int v, int lane, int &total) { // exclusive prefix sum over the wave
     int s = v;
@@ -127,7 +152,11 @@ __device__ __forceinline__ int loc_wave_scan(int v, int lane, int &total) { // e
 // writes the upper row of children, then the lower, each in lane order, which keeps rows together for the next level.
 // MODE 0: a level above the map (prune, expand).  MODE 1: level 0 (prune, keys for the merge).  MODE 2: the probe -- every
 // node's key (bound, position in the frontier) is written, nothing is pruned or counted.
-template <int MODE>
+// EXCL (a places search): a node that is wholly near a pick is not scored.  The exact pass drops and
+// counts it -- at level 0 that is the leaf test, which alone keeps the result exact; above, it only saves work -- and the probe
+// gives it the key score 0, so that neither the beam nor tau follows an excluded hypothesis.  Without EXCL the kernel is what
+// ym_locator_locate has always launched.
+template <int MODE, bool EXCL>
 __global__ __launch_bounds__(kLocThreads) void loc_score_kernel(LocScoreArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char loc_lds_raw[];
     uint32_t *s_off = reinterpret_cast<uint32_t *>(loc_lds_raw);
@@ -136,8 +165,10 @@ __global__ __launch_bounds__(kLocThreads) void loc_score_kernel(LocScoreArgs a) 
     const uint32_t i = blockIdx.x * kLocThreads + tid;
     const bool valid = i < a.n_in;
     const uint64_t node = valid ? a.in[i] : 0;
-    const int k = valid ? (int)(node >> 32) : INT_MAX;
     const int X = (int)(node & 0xffff), Y = (int)((node >> 16) & 0xffff);
+    bool excluded = false;
+    if (EXCL) excluded = valid && loc_excluded(a, (int)(node >> 32), X, Y);
+    const int k = valid && !excluded ? (int)(node >> 32) : INT_MAX; // (INT_MAX: no heading's turn scores this lane)
     const int bx = X + a.margin, by = Y + a.margin;
     const uint8_t *lvl = a.lvl;
     const unsigned pitch = (unsigned)a.pitch, rows = (unsigned)a.rows;
@@ -176,8 +207,12 @@ __global__ __launch_bounds__(kLocThreads) void loc_score_kernel(LocScoreArgs a) 
         if (valid) a.out[i] = (uint64_t)sum << 40 | (kLocIndexMask - i);
         return;
     }
+    if (EXCL) {
+        const int n_excluded = __popcll(__ballot(excluded));
+        if (lane == 0 && n_excluded) atomicAdd(MODE == 1 ? &a.st->excluded_leaves : &a.st->excluded_nodes, (unsigned long long)n_excluded);
+    }
     const int tau = a.st->tau;
-    const bool keep = valid && sum >= (tau > a.s_min ? tau : a.s_min);
+    const bool keep = valid && !excluded && sum >= (tau > a.s_min ? tau : a.s_min);
     const unsigned long long kept = __ballot(keep);
     const int n_kept = __popcll(kept);
     if (lane == 0 && n_kept) atomicAdd(&a.st->survivors[a.level], (unsigned long long)n_kept);
@@ -214,6 +249,14 @@ __global__ __launch_bounds__(kLocThreads) void loc_score_kernel(LocScoreArgs a) 
             }
         }
     }
+}
+
+// ---- (host) the launch of the node scoring kernel of one level: the instantiations without exclusion are those ym_locator_locate has always launched
+template <int MODE>
+static void loc_launch_score(const LocScoreArgs &a, size_t lds, hipStream_t st) {
+    const dim3 grid((a.n_in + kLocThreads - 1) / kLocThreads), block(kLocThreads);
+    if (a.n_excl > 0) hipLaunchKernelGGL((loc_score_kernel<MODE, true>), grid, block, lds, st, a);
+    else hipLaunchKernelGGL((loc_score_kernel<MODE, false>), grid, block, lds, st, a);
 }
 
 // ---- the top-K merge: a radix select of the K-th largest key, eight 8-bit digits from the top.  Keys are unique, so

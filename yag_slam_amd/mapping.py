@@ -424,21 +424,57 @@ class MapLocalizer(object):
     correction is not applied and the scan keeps its odometry prior (dead reckoning).
 
     `last` is the last scan processed (its `corrected_pose` is the robot's pose in the map), `lost` the number of
-    consecutive steps whose correction was not applied, `results` every step's result."""
+    consecutive steps whose correction was not applied, `results` every step's result.
 
-    def __init__(self, matcher, cmap, ox, oy, coarse=None, min_response=0.0):
+    Alternatives.  `start(scan, places=K)` with K > 1 keeps one `MapAlternative` per distinct place the map offers
+    (`ScanMatcher.locate_in_map(places=K)`) and follows them all, one `track_in_map` call per step, until the evidence
+    leaves one: `alternatives` (alive, in place order), `ambiguous` (more than one alive), `leader`.  Per step, in this
+    order: (1) every alternative's `evidence` grows by its step's response and its `lost` is counted as `MapLocalizer.lost`
+    is; (2) the leader is the alternative with the largest evidence, a tie going to the lower place; (3) an alternative
+    whose evidence trails the leader's by `evidence_gap` or more, or whose `lost` reached `max_lost`, is dropped -- never the
+    leader; (4) an alternative within both merge[0] metres and merge[1] radians (modulo 2 pi) of one with more evidence is
+    dropped; (5) the caller's scan takes the leader's pose, and `lost` and `results` follow the leader's.  With one
+    alternative left, every later step is the single-track step on the caller's own scans.  The three defaults are policy,
+    not measurements."""
+
+    def __init__(self, matcher, cmap, ox, oy, coarse=None, min_response=0.0, evidence_gap=0.5, max_lost=3, merge=(0.2, 0.1)):
         self.matcher, self.cmap, self.ox, self.oy = matcher, cmap, ox, oy
         self.coarse, self.min_response = coarse, min_response
+        self.evidence_gap, self.max_lost, self.merge = float(evidence_gap), int(max_lost), (float(merge[0]), float(merge[1]))
         self.last = None
         self.lost = 0
         self.results = []
+        self._alts = []
 
-    def start(self, scan, **locate_kw):
+    @property
+    def alternatives(self):
+        """the alternatives still alive, in place order (empty when the localizer was started without `places`)"""
+        return list(self._alts)
+
+    @property
+    def ambiguous(self):
+        return len(self._alts) > 1
+
+    @property
+    def leader(self):
+        """the alternative with the largest evidence, a tie going to the lower place (None without alternatives)"""
+        best = None
+        for a in self._alts:
+            if best is None or a.evidence > best.evidence:
+                best = a
+        return best
+
+    def start(self, scan, places=None, min_separation=(1.0, 0.5), **locate_kw):
         """The first scan.  With its pose known (`corrected_pose` and `odom_pose` set by the caller) it only becomes `last`;
         with keywords for `ScanMatcher.locate_in_map` it is located in the map first (`relocalize`) and both poses are set
-        to the located, polished pose.  Returns the locate result, or None."""
+        to the located, polished pose.  Returns the locate result, or None.
+        places = K > 1: K distinct places (at least `min_separation` = (metres, radians) apart) are located and polished, one
+        alternative is kept per place found, and the scan gets the best polished place's pose."""
+        self._alts = []
+        if places is not None and int(places) > 1:
+            return self._start_places(scan, int(places), min_separation, locate_kw)
         res = None
-        if locate_kw:
+        if locate_kw or places is not None:
             res = self.matcher.locate_in_map(self.cmap, self.ox, self.oy, [scan], **locate_kw)
             p = res.best_pose[0]
             scan.odom_pose = Transform(p.x, p.y, 0.0, p.euler[-1])
@@ -462,6 +498,10 @@ class MapLocalizer(object):
             self.start(scans.pop(0))
         if not scans:
             return []
+        if self.ambiguous:
+            if len(scans) > 1:
+                raise ValueError("MapLocalizer: while alternatives are alive (`ambiguous`) process_scans takes one scan at a time")
+            return [self._step_alternatives(scans[0])]
         res, done = self.matcher.track_in_map(self.cmap, self.ox, self.oy, [self.last] + scans, 1, True, True, self.coarse,
                                               self.min_response)
         got = res[1:done]
@@ -473,6 +513,72 @@ class MapLocalizer(object):
             raise ValueError("MapLocalizer: scan %d of the call could not be matched (no valid reading or an empty lattice); "
                              "it keeps its odometry prior" % (done - 1))
         return got
+
+    def _start_places(self, scan, places, min_separation, locate_kw):
+        res = self.matcher.locate_in_map(self.cmap, self.ox, self.oy, [scan], places=places, min_separation=min_separation, **locate_kw)
+        if "places" not in res.meta:
+            raise ValueError("MapLocalizer.start(places=K) needs the polished places: leave refine=True")
+        p = res.best_pose[0]
+        scan.odom_pose = Transform(p.x, p.y, 0.0, p.euler[-1])
+        scan.corrected_pose = Transform(p.x, p.y, 0.0, p.euler[-1])
+        for i, polished in enumerate(res.meta["places"]):
+            q = polished.best_pose[0]
+            own = scan.copy()
+            own.corrected_pose = Transform(q.x, q.y, 0.0, q.euler[-1])  # (its odometry stays the caller's: increments are shared)
+            self._alts.append(MapAlternative(i, own))
+        self.last, self.lost = scan, 0
+        self._results_before = list(self.results)
+        return res
+
+    def _step_alternatives(self, scan):
+        """one step of every alive alternative in one `track_in_map` call, then the five-step rule of the class docstring"""
+        alts = self._alts
+        copies = []
+        for a in alts:
+            c = scan.copy()
+            c.odom_pose = scan.odom_pose
+            copies.append(c)
+        out = self.matcher.track_in_map(self.cmap, self.ox, self.oy, [[a.last, c] for a, c in zip(alts, copies)], 1, True, True,
+                                        self.coarse, self.min_response)
+        served = {}
+        for a, c, (res, done) in zip(alts, copies, out):
+            a.last = c
+            r = res[1] if done > 1 else None
+            if r is None:  # the matcher could not serve the scan: it keeps its prior, as a step that was not applied
+                a.lost += 1
+                continue
+            a.evidence += r.response
+            a.lost = 0 if r.meta["accepted"] else a.lost + 1
+            a.results.append(r)
+            served[a.place] = r
+        lead = self.leader
+        alive = [a for a in alts if a is lead or not (lead.evidence - a.evidence >= self.evidence_gap or a.lost >= self.max_lost)]
+        kept = []
+        for a in alive:
+            pa = a.last.corrected_pose
+            for b in alive:
+                pb = b.last.corrected_pose
+                da = (pa.euler[-1] - pb.euler[-1] + math.pi) % (2 * math.pi) - math.pi
+                if b.evidence > a.evidence and math.hypot(pa.x - pb.x, pa.y - pb.y) <= self.merge[0] and abs(da) <= self.merge[1]:
+                    break
+            else:
+                kept.append(a)
+        self._alts = kept
+        p = lead.last.corrected_pose
+        scan.corrected_pose = Transform(p.x, p.y, 0.0, p.euler[-1])
+        self.last, self.lost = scan, lead.lost
+        self.results = self._results_before + list(lead.results)
+        return served.get(lead.place)
+
+
+class MapAlternative(object):
+    """One place a `MapLocalizer` started with `places=K` still follows: `place` (its index in the located order), `last`
+    (its own copy of the last scan, at this alternative's pose), `evidence` (the sum of its steps' responses), `lost`
+    (consecutive steps whose correction was not applied) and `results` (its steps' results)."""
+
+    def __init__(self, place, last):
+        self.place, self.last = place, last
+        self.evidence, self.lost, self.results = 0.0, 0, []
 
 
 class MapBuilder(object):

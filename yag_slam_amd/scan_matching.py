@@ -599,7 +599,7 @@ class ScanMatcher(object):
         levels: pyramid levels above the map (None: by the map's size); max_nodes: frontier entries per buffer (None: 2^25)."""
         return MapLocator(self, cmap, levels, max_nodes)
 
-    def locate_in_map(self, cmap, ox, oy, query_scans, refine=True, polish_top=1, **kw):
+    def locate_in_map(self, cmap, ox, oy, query_scans, refine=True, polish_top=1, places=None, min_separation=(1.0, 0.5), **kw):
         """One shot: where in the map `cmap` (cell (0, 0) at world (ox, oy)) were `query_scans` taken, as one rigid set?
         The exact best hypothesis over all cells and headings (`MapLocator.locate`, keywords passed on), then, with `refine`,
         polished: copies of the scans are moved to the located poses and matched with `match_scan_sets_with_map` (coarse
@@ -609,9 +609,18 @@ class ScanMatcher(object):
         reference does, is meta["wrapper_poses"]).  Raises ValueError when no hypothesis reaches min_response.
         polish_top = K > 1: the first K located candidates are polished in one `match_map_batch`; the best polished response
         wins, a tie going to the earlier candidate, and all K polished results are meta["polished"] (best_pose of each: its
-        rigid pose list)."""
+        rigid pose list).
+        places = K (1 .. 16): the candidates are the K best distinct places (`MapLocator.locate_places` with
+        `min_separation` = (metres, radians) and the keywords), not the top of one list.  With `refine`, all places found are
+        polished in one `match_map_batch` and the best polished response wins, as with polish_top; meta["places"] holds the
+        polished results in place order and meta["ambiguity"] the second-best polished response over the best (0.0 with one
+        place): near 1, the map has another place that explains the scans as well."""
         with self.map_locator(cmap) as loc:
-            cands = loc.locate(query_scans, ox, oy, **kw)
+            if places is not None:
+                cands = loc.locate_places(query_scans, ox, oy, n_places=int(places), min_separation=min_separation, **kw)
+                polish_top = max(2, len(cands))  # every place found goes through the batch polish
+            else:
+                cands = loc.locate(query_scans, ox, oy, **kw)
             stats, step = loc.last_stats, loc.last_heading_step
         if not cands:
             raise ValueError("locate_in_map: no hypothesis reaches min_response = %g" % kw.get("min_response", 0.0))
@@ -632,7 +641,12 @@ class ScanMatcher(object):
             rs = self.match_map_batch(cmap, ox, oy, sets, True, True,
                                       coarse=dict(xy_search=2 * res, xy_step=res / 4, angle_search=step, angle_step=step / 20,
                                                   grid_resolution=res))
-            return _pick_polished(rs, meta)
+            r = _pick_polished(rs, meta)
+            if places is not None:
+                ranked = sorted(p.response for p in rs)
+                r.meta["places"] = r.meta["polished"]
+                r.meta["ambiguity"] = float(ranked[-2] / ranked[-1]) if len(ranked) > 1 and ranked[-1] > 0 else 0.0
+            return r
         moved = []
         for q, p in zip(query_scans, best.poses):
             c = q.copy()
@@ -1087,7 +1101,7 @@ class MapLocator(object):
         info = _capi.YmLocatorInfo()
         _capi.check(matcher._lib.ym_locator_get_info(self._h, C.byref(info)))
         self.shape, self.levels, self.max_nodes, self.bytes = (info.height, info.width), info.levels, info.max_nodes, info.bytes
-        self.last_stats, self.last_points, self.last_heading_step = None, None, None
+        self.last_stats, self.last_points, self.last_heading_step, self.last_separation = None, None, None, None
         # the pyramid holds a copy of the map as it is now: a map that takes scans afterwards leaves it stale
         self._cmap, self._revision = cmap, getattr(cmap, "revision", 0)
 
@@ -1103,12 +1117,11 @@ class MapLocator(object):
         centre, poses = every query scan's pose after the rigid motion that takes the centre -- the mean query position,
         heading 0 -- to `pose`), best first, ties by ascending index.  headings: explicit angles (default 2 pi k / n_angles).
         min_separation = (metres, radians): the device's best 64 are filtered greedily (filter_min_separation) before the
-        first top_k are returned.  `.last_stats`: dict(nq, chunks, nodes and survivors per level, probe_nodes); `.last_points`: the point set."""
+        first top_k are returned.  That only THINS the best 64, which are nearly always neighbours of the best in cell and
+        heading: a runner-up place that scores below the best place's own halo is not among them.  For the K best distinct
+        places over the whole volume use `locate_places`.  `.last_stats`: dict(nq, chunks, nodes and survivors per level, probe_nodes); `.last_points`: the point set."""
         self._check_revision()
-        if headings is None:
-            headings = 2.0 * np.pi * np.arange(int(n_angles)) / float(int(n_angles))
-        headings = np.ascontiguousarray(headings, dtype=np.float64).reshape(-1)
-        dir_cs = np.ascontiguousarray(np.stack([np.cos(headings), np.sin(headings)], axis=1))
+        headings, dir_cs = self._heading_table(n_angles, headings)
         want = 64 if min_separation is not None else int(top_k)
         if min_separation is not None and not 1 <= int(top_k) <= 64:
             raise ValueError("top_k must be in [1, 64]")
@@ -1124,17 +1137,74 @@ class MapLocator(object):
         self.last_stats = dict(nq=stats.nq, chunks=stats.chunks, nodes=list(stats.nodes), survivors=list(stats.survivors),
                                probe_nodes=stats.probe_nodes)
         self.last_points = pts[:stats.nq].copy()
-        self.last_heading_step = float(2.0 * np.pi / len(headings)) if len(headings) < 2 else float(abs(headings[1] - headings[0]))
+        self.last_heading_step = self._heading_step(headings)
+        cands = self._candidates(query_scans, out[:n_found.value])
+        if min_separation is not None:
+            cands = filter_min_separation(cands, float(min_separation[0]), float(min_separation[1]))[:int(top_k)]
+        return cands
+
+    def locate_places(self, query_scans, ox, oy, n_places=4, min_separation=(1.0, 0.5), separation_cells=None, n_angles=360,
+                      headings=None, min_response=0.0, point_stride=1):
+        """The `n_places` (1 .. 16) best DISTINCT places, as LocateCandidates in place order: place 1 is the best hypothesis
+        of all, place i + 1 the best one that is near none of places 1 .. i -- exact over every cell and heading, not a
+        thinning of a top list (`ym_locator_locate_places`; one search per place).  Two hypotheses
+        are near when BOTH their cells lie within the cell separation and their heading indices within the heading
+        separation.  separation_cells = (sep_cells2, sep_headings): the squared cell distance and the heading steps, taken
+        as they are; otherwise from min_separation = (metres, radians): sep_cells2 = int((metres / res) ** 2 + 1e-6),
+        sep_headings = int(radians / step + 1e-6), step = the heading table's step (`last_heading_step`).  Heading indices
+        are compared on a circle exactly when `headings` is None (the full turn 2 pi k / n_angles).
+        `.last_separation`: (sep_cells2, sep_headings, circular) as used; `.last_stats`: dict(nq, rounds, chunks, nodes,
+        probe_nodes, excluded_leaves, excluded_nodes, round_nodes); `.last_points`: the point set."""
+        self._check_revision()
+        circular = 1 if headings is None else 0
+        headings, dir_cs = self._heading_table(n_angles, headings)
+        step = self._heading_step(headings)
+        if separation_cells is not None:
+            sep_cells2, sep_headings = int(separation_cells[0]), int(separation_cells[1])
+        else:
+            sep_cells2 = int((float(min_separation[0]) / float(self.m.config.resolution)) ** 2 + 1e-6)
+            sep_headings = int(float(min_separation[1]) / step + 1e-6)
+        want = int(n_places)
+        hs = (C.c_void_p * max(1, len(query_scans)))(*[self.m._require_native(q) for q in query_scans])
+        opts = _capi.YmLocatePlacesOpts(want, int(point_stride), float(min_response), sep_cells2, sep_headings, circular)
+        out = (_capi.YmLocateCandidate * max(1, want))()
+        n_found, stats = C.c_int(0), _capi.YmLocatePlacesStats()
+        cap = sum(len(q.ranges) for q in query_scans)
+        pts = np.zeros((max(1, cap), 2))
+        _capi.check(self.m._lib.ym_locator_locate_places(self._h, float(ox), float(oy), hs, len(query_scans),
+                                                         dir_cs.ctypes.data_as(C.POINTER(C.c_double)), dir_cs.shape[0], C.byref(opts), out,
+                                                         C.byref(n_found), pts.ctypes.data_as(C.POINTER(C.c_double)), C.byref(stats)))
+        self.last_stats = dict(nq=stats.nq, rounds=stats.rounds, chunks=stats.chunks, nodes=stats.nodes, probe_nodes=stats.probe_nodes,
+                               excluded_leaves=stats.excluded_leaves, excluded_nodes=stats.excluded_nodes,
+                               round_nodes=list(stats.round_nodes)[:stats.rounds])
+        self.last_points = pts[:stats.nq].copy()
+        self.last_heading_step = step
+        self.last_separation = (sep_cells2, sep_headings, circular)
+        return self._candidates(query_scans, out[:n_found.value])
+
+    @staticmethod
+    def _heading_table(n_angles, headings):
+        """(headings, their (cos, sin) rows) -- by default the full turn 2 pi k / n_angles"""
+        if headings is None:
+            headings = 2.0 * np.pi * np.arange(int(n_angles)) / float(int(n_angles))
+        headings = np.ascontiguousarray(headings, dtype=np.float64).reshape(-1)
+        return headings, np.ascontiguousarray(np.stack([np.cos(headings), np.sin(headings)], axis=1))
+
+    @staticmethod
+    def _heading_step(headings):
+        return float(2.0 * np.pi / len(headings)) if len(headings) < 2 else float(abs(headings[1] - headings[0]))
+
+    @staticmethod
+    def _candidates(query_scans, found):
+        """the library's candidates as LocateCandidates: every query scan moved rigidly with the set's centre"""
         xs = [float(q.corrected_pose.x) for q in query_scans]
         ys = [float(q.corrected_pose.y) for q in query_scans]
         cx, cy = sum(xs) / float(len(xs)), sum(ys) / float(len(ys))
         cands = []
-        for c in out[:n_found.value]:
+        for c in found:
             pose = Transform(c.pose[0], c.pose[1], 0.0, c.pose[2])
             cands.append(LocateCandidate(c.score, c.response, c.index, c.k, c.cx, c.cy, pose,
                                          _move_rigidly([q.corrected_pose for q in query_scans], cx, cy, pose.x, pose.y, c.pose[2])))
-        if min_separation is not None:
-            cands = filter_min_separation(cands, float(min_separation[0]), float(min_separation[1]))[:int(top_k)]
         return cands
 
     def _check_revision(self):
