@@ -356,6 +356,36 @@ int ym_map_reframe(ym_matcher *m, ym_map *map, int dx, int dy, int width, int he
                    int n_held, ym_map_reframe_stats *stats /* or null */);
 int ym_map_window(const ym_map *map, int *x0, int *y0, int *width, int *height);
 ym_map *ym_map_create_counted_window(ym_matcher *m, int width, int height, double ax, double ay, int x0, int y0);
+/* ---- maps that notice change: which held readings do newer scans look straight through?
+ *   ym_map_seen_through  held[i] at held_poses[i] -- the poses they were added at, ym_map_update_scans' convention; any subset of
+ *                        what the map holds -- are counted against the viewers at their CURRENT poses.  Cells are the map's own
+ *                        (rint((x - ax) / res) - x0, likewise y; a quotient that is not finite or does not fit an int32 yields no
+ *                        cell), readings are valid by !(r > range_threshold || isnan(r)).  Every valid viewer reading gives a ray from
+ *                        the viewer's sensor cell to the reading's cell (either may lie outside the window; a viewer without a sensor
+ *                        cell walks no ray), over the cells of Grid::TraceLine: axes swapped if steep, walked from the lower major
+ *                        coordinate, the minor coordinate floor((2 k dm + dM) / (2 dM)) cells on after k of dM major steps.  A cell
+ *                        of the window is SWEPT when its distance to the reading's end of the walk (dM - k, or k where the walk
+ *                        started there) is greater than `clearance` -- clearance 0 sweeps all but the end cell -- unless it lies
+ *                        within Chebyshev distance `protect` of the end cell of ANY valid viewer reading (protect 0: the end cells
+ *                        themselves).  A ray of 32768 major steps or more sweeps nothing (only a reading no sensor gives is that
+ *                        long once the matcher is admitted, below).  counts[i] = (inside, seen): held[i]'s valid readings whose
+ *                        cell lies in the window, and those of them whose cell is swept; flags (or null) [n_held][max_n], max_n the
+ *                        longest held scan: 1 exactly for the readings counted in seen, 0 elsewhere; mask (or null, a test hook)
+ *                        [height][width]: the swept cells after protection; stats (or null): the viewer rays and the sums of
+ *                        both counts.  A viewer may be held: no special case.  Changes no byte of the map or its counts.  Runs on
+ *                        the matcher's stream, synchronous, never throws.  n_held == 0 or n_viewers == 0 are fine (nothing swept).
+ * YM_ERR_INVALID: a null argument that is not nullable, a negative count, clearance or protect, a null scan, a scan or a map on
+ * another device.  YM_ERR_UNSUPPORTED: a map that is not counted, a matcher that is not YM_SEM_YAGPY or whose
+ * range_threshold / resolution + 2 reaches 32768 cells (the walk is 32-bit), a protect neighbourhood times the longest viewer
+ * beyond 2 * 10^9 lanes. */
+typedef struct ym_map_seen_stats { int64_t rays; int64_t inside; int64_t seen; } ym_map_seen_stats;
+int ym_map_seen_through(ym_matcher *m, const ym_map *map,
+                        const ym_scan *const *held, const double *held_poses /* [n_held][3] */, int n_held,
+                        const ym_scan *const *viewers, int n_viewers, int clearance, int protect,
+                        int32_t *counts /* [n_held][2]: inside, seen */,
+                        uint8_t *flags /* nullable, [n_held][max_n], max_n = the longest held scan */,
+                        uint8_t *mask /* nullable test hook, [height][width]: the swept cells after protection */,
+                        ym_map_seen_stats *stats /* nullable */);
 /* one find_best_pose_non_symmetric pass (/root/reference/yag_slam/helpers.py:434-573) */
 typedef struct ym_map_search {
     double xy_search, xy_step;       /* +- metres around the centre, lattice step */

@@ -32,7 +32,7 @@ EXPORTS = (
     "ym_match_map_many", "ym_map_track", "ym_debug_map_sums", "ym_match_sets", "ym_match_sets_many",
     "ym_map_create_empty", "ym_map_add_scans", "ym_map_clear",
     "ym_map_create_counted", "ym_map_update_scans", "ym_map_counted", "ym_map_read_stamps",
-    "ym_map_reframe", "ym_map_window", "ym_map_create_counted_window",
+    "ym_map_reframe", "ym_map_window", "ym_map_create_counted_window", "ym_map_seen_through",
     "ym_raymap_create", "ym_raymap_trace", "ym_raymap_trace_each", "ym_raymap_destroy",
     "ym_locator_create", "ym_locator_get_info", "ym_locator_read_level", "ym_locator_locate", "ym_locator_locate_places", "ym_locator_destroy",
     "ym_segments_create", "ym_segments_label_range", "ym_segments_stats", "ym_segments_boundaries", "ym_segments_pairs",
@@ -136,6 +136,10 @@ class YmMapUpdateStats(C.Structure):
 class YmMapReframeStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("kept", "restamped", "dropped", "recomputed", "mismatch")] + [
         (n, C.c_int32) for n in ("x0", "y0", "width", "height")]
+
+
+class YmMapSeenStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("rays", "inside", "seen")]
 
 
 class YmGridInfo(C.Structure):
@@ -355,6 +359,8 @@ def lib():
     L.ym_map_counted.argtypes = [vp]
     L.ym_map_read_stamps.argtypes = [vp, C.POINTER(C.c_uint32), C.c_int64]
     L.ym_map_reframe.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), dp, C.c_int, C.POINTER(YmMapReframeStats)]
+    L.ym_map_seen_through.argtypes = [vp, vp, C.POINTER(vp), dp, C.c_int, C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(YmMapSeenStats)]
     L.ym_map_window.argtypes = [vp, ip, ip, ip, ip]
     L.ym_map_create_counted_window.restype = vp
     L.ym_map_create_counted_window.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int]

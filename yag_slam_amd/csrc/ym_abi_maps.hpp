@@ -207,6 +207,83 @@ int ym_map_update_scans(ym_matcher *m, ym_map *mp, const ym_scan *const *remove,
     return map_update(m, mp, remove, remove_poses, n_remove, add, n_add, stats);
 }
 
+// ---- maps that notice change (ym_k_seenthrough.hpp): which held readings do the viewers look through
+int ym_map_seen_through(ym_matcher *m, const ym_map *mp, const ym_scan *const *held, const double *held_poses, int n_held,
+                        const ym_scan *const *viewers, int n_viewers, int clearance, int protect, int32_t *counts, uint8_t *flags,
+                        uint8_t *mask, ym_map_seen_stats *stats) {
+    if ((n_held != 0 && (!held || !held_poses || !counts)) || (n_viewers != 0 && !viewers)) return set_err(YM_ERR_INVALID, "null argument");
+    if (n_held < 0 || n_viewers < 0) return set_err(YM_ERR_INVALID, "n_held and n_viewers must not be negative");
+    if (clearance < 0 || protect < 0) return set_err(YM_ERR_INVALID, "clearance and protect must not be negative");
+    int rc;
+    if ((rc = map_call_check(m, mp, "ym_map_seen_through"))) return rc;
+    if (!mp->counted) return set_err(YM_ERR_UNSUPPORTED, "this map keeps no counts and holds no scans: use ym_map_create_counted");
+    // the sweep's 32-bit walk: 2 k dm + dM stays below 2^31 while a ray has fewer than 2^15 major steps
+    if (!(m->cfg.range_threshold / m->cfg.resolution + 2.0 < 32768.0))
+        return set_err(YM_ERR_UNSUPPORTED, "a range threshold of %g m at %g m per cell: rays of 32768 cells or more", m->cfg.range_threshold,
+                       m->cfg.resolution);
+    int held_n = 1, view_n = 1;
+    if ((rc = map_scan_list(m, held, n_held, "held scan", &held_n)) || (rc = map_scan_list(m, viewers, n_viewers, "viewer", &view_n))) return rc;
+    const double side = 2.0 * protect + 1.0;
+    if ((double)view_n * side * side > 2.0e9)
+        return set_err(YM_ERR_UNSUPPORTED, "%d beams x %.0f x %.0f protected cells: more than one launch holds", view_n, side, side);
+    DEV_GUARD(m->device);
+    hipStream_t st = m->stream;
+    const size_t n_cells = (size_t)mp->width * mp->height;
+    ym::SeenArgs s;
+    std::memset(&s, 0, sizeof s);
+    s.width = mp->width; s.height = mp->height; s.ox = mp->ox; s.oy = mp->oy; s.res = m->cfg.resolution; s.wx0 = mp->x0; s.wy0 = mp->y0;
+    s.clearance = clearance; s.protect = protect;
+    if ((rc = m->seen_mask.ensure(n_cells))) return rc;
+    s.mask = m->seen_mask.p;
+    HIP_TRY(hipMemsetAsync(s.mask, 0, n_cells, st));
+    // the viewers at their current poses: every sweep, then every protect launch (a protected cell stays clear of all rays)
+    std::vector<YmScanRef> vrefs((size_t)n_viewers); // (the copies below read these until the stream wait)
+    std::vector<int32_t> walked;
+    const unsigned sweep_x = (unsigned)((view_n + ym::kSeenRaysPerBlock - 1) / ym::kSeenRaysPerBlock);
+    if (n_viewers > 0) {
+        walked.assign((size_t)n_viewers * sweep_x, 0);
+        if ((rc = m->seen_viewers.ensure((size_t)n_viewers)) || (rc = m->seen_walked.ensure(walked.size()))) return rc;
+        for (int i = 0; i < n_viewers; i++) vrefs[(size_t)i] = scan_ref(viewers[i]);
+        HIP_TRY(hipMemcpyAsync(m->seen_viewers.p, vrefs.data(), sizeof(YmScanRef) * (size_t)n_viewers, hipMemcpyHostToDevice, st));
+        s.max_n = view_n;
+        const unsigned protect_x = (unsigned)(((size_t)view_n * (size_t)(side * side) + 255) / 256);
+        for (int stage = 0; stage < 2; stage++) {
+            for (int c0 = 0; c0 < n_viewers; c0 += kMapGrowChunk) {
+                const int B = std::min(kMapGrowChunk, n_viewers - c0);
+                s.scans = m->seen_viewers.p + c0;
+                s.walked = m->seen_walked.p + (size_t)c0 * sweep_x;
+                if (stage == 0) hipLaunchKernelGGL(ym::seen_sweep_kernel, dim3(sweep_x, B), dim3(256), 0, st, s);
+                else hipLaunchKernelGGL(ym::seen_protect_kernel, dim3(protect_x, B), dim3(256), 0, st, s);
+            }
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(walked.data(), m->seen_walked.p, sizeof(int32_t) * walked.size(), hipMemcpyDeviceToHost, st));
+    }
+    // the held scans at the poses they were added at: map_grow_cells_kernel's cells (no exclusion rectangle), then the counts
+    MapJob job; // (lives until the stream wait below)
+    if (n_held > 0) {
+        if ((rc = map_workspace(m, n_held, held_n)) || (rc = job.begin(m, n_held, 1, false)) || (rc = m->seen_counts.ensure(2 * (size_t)n_held)) ||
+            (flags && (rc = m->seen_flags.ensure((size_t)n_held * held_n))))
+            return rc;
+        const MapTarget target = {nullptr, nullptr, nullptr, nullptr, mp->width, mp->height, mp->ox, mp->oy, mp->x0, mp->y0, ymm::Box()};
+        MapPassArgs pa = map_pass_args(m, target, held_n);
+        s.scans = nullptr; s.walked = nullptr;
+        s.max_n = held_n; s.cells = m->grow_cells.p; s.counts = m->seen_counts.p; s.flags = flags ? m->seen_flags.p : nullptr;
+        pa.s = s;
+        if ((rc = map_stamp_pass(m, job, pa, held, held_poses, n_held, kMapCountSeen, false, 0))) return rc;
+        HIP_TRY(hipMemcpyAsync(counts, m->seen_counts.p, sizeof(int32_t) * 2 * (size_t)n_held, hipMemcpyDeviceToHost, st));
+        if (flags) HIP_TRY(hipMemcpyAsync(flags, m->seen_flags.p, (size_t)n_held * held_n, hipMemcpyDeviceToHost, st));
+    }
+    if (mask) HIP_TRY(hipMemcpyAsync(mask, s.mask, n_cells, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (stats) {
+        stats->rays = stats->inside = stats->seen = 0;
+        for (int32_t w : walked) stats->rays += w;
+        for (int i = 0; i < n_held; i++) { stats->inside += counts[2 * (size_t)i]; stats->seen += counts[2 * (size_t)i + 1]; }
+    }
+    return YM_OK;
+}
+
 int ym_map_add_scans(ym_matcher *m, ym_map *mp, double ox, double oy, const ym_scan *const *scans, int n_scans, ym_map_add_stats *stats) {
     if (!scans && n_scans != 0) return set_err(YM_ERR_INVALID, "null argument");
     if (n_scans < 0) return set_err(YM_ERR_INVALID, "n_scans must not be negative");

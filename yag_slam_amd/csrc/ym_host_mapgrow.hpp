@@ -1,6 +1,7 @@
 // ym_host_mapgrow.hpp -- host runtime: what every call that changes a resident correlation map is made of (ym_abi_maps.hpp:
-// ym_map_add_scans, ym_map_update_scans, ym_map_reframe).  The kernels are those of ym_k_mapgrow.hpp, the window's integer
-// arithmetic that of ym_map_window.hpp; DESIGN.md sections 15 to 17.
+// ym_map_add_scans, ym_map_update_scans, ym_map_reframe), and the one that only asks it a question (ym_map_seen_through).  The
+// kernels are those of ym_k_mapgrow.hpp and ym_k_seenthrough.hpp, the window's integer arithmetic that of ym_map_window.hpp;
+// DESIGN.md sections 15 to 17 and 19.
 // Part of yagmatch.hip (included inside its anonymous namespace); not a header of its own.
 
 // scans of one launch: the cells of every beam take 4 bytes, grid.y stays far below its limit
@@ -66,7 +67,7 @@ struct MapTarget {
     ymm::Box exclude; // ym_map_reframe: the overlap, whose counts were copied; empty for every other caller
 };
 
-struct MapPassArgs { ym::MapGrowArgs a; ym::MapForgetArgs f; };
+struct MapPassArgs { ym::MapGrowArgs a; ym::MapForgetArgs f; ym::SeenArgs s; }; // (s: ym_map_seen_through fills it, zero elsewhere)
 
 // (after map_workspace and map_taps_upload: the structs hold the workspace's pointers)
 MapPassArgs map_pass_args(const ym_matcher *m, const MapTarget &t, int max_n) {
@@ -120,7 +121,8 @@ struct MapJob {
 
 // ---- the stamp pass: `n` scans (at `poses`, [n][3], or at their own) through cells -> count -> smear, a chunk at a time.
 // grow_block: the kMgStatSlots block of the job's statistics this pass counts in.
-enum MapCount { kMapCountNone, kMapCountAdd, kMapCountRemove };
+// kMapCountSeen changes nothing: seen_count_kernel reads the mask at the cells and writes scan c0 + i's counts and flags (pa.s).
+enum MapCount { kMapCountNone, kMapCountAdd, kMapCountRemove, kMapCountSeen };
 
 int map_stamp_pass(ym_matcher *m, MapJob &job, MapPassArgs pa, const ym_scan *const *scans, const double *poses, int n, MapCount count,
                    bool smear, int grow_block) {
@@ -141,6 +143,12 @@ int map_stamp_pass(ym_matcher *m, MapJob &job, MapPassArgs pa, const ym_scan *co
         hipLaunchKernelGGL(ym::map_grow_cells_kernel, dim3(B), dim3(1024), 0, st, a);
         if (count == kMapCountRemove) hipLaunchKernelGGL(ym::map_count_kernel<true>, dim3(beams.x, B), dim3(256), 0, st, pa.f);
         if (count == kMapCountAdd) hipLaunchKernelGGL(ym::map_count_kernel<false>, dim3(beams.x, B), dim3(256), 0, st, pa.f);
+        if (count == kMapCountSeen) {
+            ym::SeenArgs s = pa.s;
+            s.counts += 2 * (size_t)c0;
+            if (s.flags) s.flags += (size_t)c0 * (size_t)s.max_n;
+            hipLaunchKernelGGL(ym::seen_count_kernel, dim3(B), dim3(256), 0, st, s);
+        }
         if (smear) {
             hipLaunchKernelGGL(ym::map_grow_smear_kernel<false>, dim3(taps.x, B), dim3(256), 0, st, a);
             hipLaunchKernelGGL(ym::map_grow_smear_kernel<true>, dim3(taps.x, B), dim3(256), 0, st, a);

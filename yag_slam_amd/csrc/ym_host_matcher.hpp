@@ -73,6 +73,11 @@ struct ym_matcher {
     DevBuf<int32_t> grow_cells;   // ... the cell of every beam (ym_k_mapgrow.hpp) ...
     DevBuf<unsigned long long> grow_stats; // ... and the counts and the box of the call
     DevBuf<int32_t> grow_released; // ym_map_update_scans: the cells whose count fell to zero
+    DevBuf<uint8_t> seen_mask;     // ym_map_seen_through (ym_k_seenthrough.hpp): the swept cells of the call's window, ...
+    DevBuf<YmScanRef> seen_viewers; // ... its viewers, ...
+    DevBuf<int32_t> seen_walked;   // ... the rays each sweep block walked, ...
+    DevBuf<int32_t> seen_counts;   // ... (inside, seen) per held scan ...
+    DevBuf<uint8_t> seen_flags;    // ... and, where asked for, a flag per held beam
     int z2max = 0;               // largest squared cell distance whose kernel value is 100
     DevBuf<uint8_t> ktab;
     DevBuf<uint8_t> rowtab;   // the raster's row-pass tables (upload_lut)

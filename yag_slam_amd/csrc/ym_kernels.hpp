@@ -35,6 +35,7 @@
 #include "ym_k_yagmap.hpp"
 #include "ym_k_sets.hpp"
 #include "ym_k_mapgrow.hpp"
+#include "ym_k_seenthrough.hpp"
 #include "ym_k_occupancy.hpp"
 #include "ym_k_raytrace.hpp"
 #include "ym_k_locate.hpp"

@@ -9,7 +9,9 @@ scan resident on the device (one upload per new scan, poses written through).
 """
 import math
 
-from .models import LocalizedRangeScan, set_corrected_poses
+import numpy as np
+
+from .models import LocalizedRangeScan, native_many, set_corrected_poses
 from .transform import Transform
 
 
@@ -608,9 +610,20 @@ class MapBuilder(object):
     that is the map's own `origin`).  On a map that keeps no counts a reframe keeps the overlap and nothing else: readings that
     were dropped beyond a side do not come back when the window moves over them.
 
+    forget_seen_through=min_readings (None: off; an integer of at least 1, which needs a counted map as `window` does) lets the
+    map notice that the world changed (`CorrelationMap.seen_through`): after a keyframe has been added,
+    every other scan of `added` is counted against that one viewer with `clearance` and `protect`, and each scan of which the
+    keyframe looks through at least `min_readings` readings is replaced -- all of them in one `CorrelationMap.update_scans` call
+    -- by its `blanked(flags)` copy, which takes the old scan's place in `added` (the order and the window's idea of "oldest"
+    stay).  Readings go, not scans: the walls an old scan saw stay in the map.  A copy with no valid reading left is only removed
+    and goes to `dropped`.  The map stays, bit for bit, the fresh counted map of the scans in `added`.  The defaults of
+    `clearance` and `protect` come from a numpy prototype on one synthetic room, not from a device or a
+    real log.
+
     `last` is the last scan processed, `last_added` the last one added, `added` every scan in the map (in order), `dropped`
     the scans the window has taken out again (in order), `lost` the number of consecutive steps whose correction was not
-    applied, `results` every step's result, `reframes` the MapReframeStats of every move of the window."""
+    applied, `results` every step's result, `reframes` the MapReframeStats of every move of the window, `blanked` the
+    (old, new) pairs `forget_seen_through` has swapped (in order)."""
 
     # rebuild() on a counted map: above this share of moved keyframes the map is cleared and filled again.  Measured with 2000
     # scans of 1081 beams (DESIGN.md section 16, profiles/map_forget_time.json): with 5 x 5 taps moving costs as much as clearing
@@ -618,7 +631,7 @@ class MapBuilder(object):
     REBUILD_SHARE = 0.2
 
     def __init__(self, matcher, cmap, ox, oy, coarse=None, min_response=0.0, min_distance=0.0, min_rotation=0.0, window=None,
-                 extent="fixed", margin=None, step=32):
+                 extent="fixed", margin=None, step=32, forget_seen_through=None, clearance=2, protect=1):
         if extent not in ("fixed", "scroll", "grow"):
             raise ValueError("MapBuilder: extent %r: \"fixed\", \"scroll\" or \"grow\"" % (extent,))
         if extent != "fixed":
@@ -632,8 +645,17 @@ class MapBuilder(object):
             if not getattr(cmap, "counted", False):
                 raise ValueError("MapBuilder: a window needs a map that can forget: "
                                  "matcher.empty_correlation_map(w, h, counted=True, ox=ox, oy=oy)")
+        if forget_seen_through is not None:
+            for name, v, least in (("forget_seen_through", forget_seen_through, 1), ("clearance", clearance, 0), ("protect", protect, 0)):
+                if isinstance(v, bool) or not isinstance(v, int) or v < least:
+                    raise ValueError("MapBuilder: %s %r: an integer of at least %d" % (name, v, least))
+            if not getattr(cmap, "counted", False):
+                raise ValueError("MapBuilder: a window needs a map that can forget: "
+                                 "matcher.empty_correlation_map(w, h, counted=True, ox=ox, oy=oy)")
         self.matcher, self.cmap, self.ox, self.oy = matcher, cmap, ox, oy
         self.coarse, self.min_response = coarse, min_response
+        self.forget_seen_through, self.clearance, self.protect = forget_seen_through, clearance, protect
+        self.blanked = []
         self.min_distance, self.min_rotation = min_distance, min_rotation
         self.window = window
         self.extent, self.margin, self.step = extent, margin, step
@@ -664,7 +686,37 @@ class MapBuilder(object):
             stats = self.cmap.add_scans(self.ox, self.oy, [scan])
         self.added.append(scan)
         self.last_added = scan
+        if self.forget_seen_through is not None:
+            self._forget_seen_through(scan)
         return stats
+
+    def _forget_seen_through(self, keyframe):
+        """the readings of the other added scans that `keyframe` looks through go: one count, one swap"""
+        others = [s for s in self.added if s is not keyframe]
+        if not others:
+            return
+        st = self.cmap.seen_through([keyframe], scans=others, clearance=self.clearance, protect=self.protect, flags=True)
+        olds, news = [], []
+        for old, seen, flags in zip(st.scans, st.seen, st.flags):
+            if seen >= self.forget_seen_through:
+                new = old.blanked(flags)
+                olds.append(old)
+                with np.errstate(invalid="ignore"):
+                    blind = bool(np.all((new.ranges > new.range_threshold) | np.isnan(new.ranges)))  # (no point reading left)
+                news.append(None if blind else new)
+        if not olds:
+            return
+        kept = [n for n in news if n is not None]
+        native_many(kept, self.matcher.device)  # (the copies' device twins in one library call)
+        self.cmap.update_scans(olds, kept)
+        place = {id(s): i for i, s in enumerate(self.added)}
+        for old, new in zip(olds, news):
+            if new is not None:
+                self.added[place[id(old)]] = new
+                self.blanked.append((old, new))
+        gone = {id(o) for o, n in zip(olds, news) if n is None}
+        self.dropped.extend(s for s in self.added if id(s) in gone)
+        self.added = [s for s in self.added if id(s) not in gone]
 
     def _follow(self, scan):
         """extent "scroll" / "grow": move the window if the scan's pose is nearer than `margin` to a side; the reframe's stats or None"""

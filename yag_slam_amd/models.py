@@ -261,3 +261,16 @@ class LocalizedRangeScan:
         pose = self.corrected_pose
         sensor = [getattr(self, k) for k in self._SENSOR_KEYS]
         return type(self)(self.ranges, *sensor, pose.x, pose.y, pose.euler[-1])
+
+    def blanked(self, flags):
+        """A detached copy whose flagged readings are NaN -- no reading at all, to every consumer -- with the same sensor, `num`,
+        odometry and corrected poses (`CorrelationMap.seen_through`'s flags: what a newer scan saw through); it gets its own
+        device twin on first use.  This scan is left as it is."""
+        flags = np.asarray(flags, dtype=bool)
+        if flags.shape != self.ranges.shape:
+            raise ValueError("blanked: %r flags for %d readings" % (flags.shape, self.ranges.shape[0]))
+        out = self.copy()
+        out.ranges[flags] = np.nan
+        out.num = self.num
+        out.odom_pose = self.odom_pose
+        return out

@@ -790,6 +790,7 @@ class ScanMatcher(object):
 MapAddStats = namedtuple("MapAddStats", ["points", "stamped", "dropped", "x0", "y0", "x1", "y1"])
 MapUpdateStats = namedtuple("MapUpdateStats", ["removed", "added", "dropped", "unmatched", "released", "gained", "x0", "y0", "x1", "y1"])
 MapReframeStats = namedtuple("MapReframeStats", ["kept", "restamped", "dropped", "recomputed", "mismatch", "x0", "y0", "width", "height"])
+SeenThrough = namedtuple("SeenThrough", ["scans", "inside", "seen", "flags"])
 
 
 class CorrelationMap(object):
@@ -942,6 +943,46 @@ class CorrelationMap(object):
         if len({id(q) for q in add}) != len(add):
             raise ValueError("update_scans (add): a scan is in the list twice")
         return self._update(remove, add)
+
+    # ---- noticing change (ym_map_seen_through)
+    def seen_through(self, viewers, scans=None, clearance=2, protect=1, flags=False):
+        """Which held readings do the `viewers` (scans at their current poses, held or not) look straight through?  A viewer's
+        ray from its sensor cell to a reading's cell sweeps the cells it crosses more than `clearance` cells before its end; a
+        cell within `protect` cells of any viewer reading's end is never swept (DESIGN.md section 19 states the rule).  `scans`:
+        a subset of the held scans (None: all, in held order), counted at the poses they were added at; one that is not held
+        raises ValueError before the library is touched.  Returns SeenThrough(scans, inside, seen, flags): per scan the valid
+        readings whose cell lies in the window and those of them whose cell is swept (int arrays), and -- with flags=True -- a
+        boolean array per scan, True exactly for the readings counted in `seen` (else None).  The map does not change.  The
+        defaults come from a numpy prototype on one synthetic room, not from a device or a real log."""
+        self._need_counted("seen_through")
+        viewers = list(viewers)
+        scans = [e[0] for e in self._held.values()] if scans is None else list(scans)
+        self._distinct(scans, "seen_through", held=True)
+        for name, v in (("clearance", clearance), ("protect", protect)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+                raise ValueError("seen_through: %s %r: an integer of at least 0" % (name, v))
+        n, max_n = len(scans), max([len(q.ranges) for q in scans] + [1])
+        hs = (C.c_void_p * max(1, n))(*[self.m._require_native(q) for q in scans])
+        vs = (C.c_void_p * max(1, len(viewers)))(*[self.m._require_native(q) for q in viewers])
+        poses = np.array([self._held[id(q)][1] for q in scans], dtype=np.float64).reshape(n, 3)
+        counts = np.zeros((n, 2), dtype=np.int32)
+        fl = np.zeros((n, max_n), dtype=np.uint8) if flags else None
+        _capi.check(self.m._lib.ym_map_seen_through(
+            self.m._m, self._h, hs, poses.ctypes.data_as(C.POINTER(C.c_double)), n, vs, len(viewers), int(clearance), int(protect),
+            counts.ctypes.data_as(C.POINTER(C.c_int32)), fl.ctypes.data_as(C.POINTER(C.c_uint8)) if flags else None, None, None))
+        per_scan = [fl[i, :len(q.ranges)].astype(bool) for i, q in enumerate(scans)] if flags else None
+        return SeenThrough(scans, counts[:, 0].astype(np.int64), counts[:, 1].astype(np.int64), per_scan)
+
+    def debug_swept_mask(self, viewers, clearance=2, protect=1):
+        """test hook: the cells the viewers sweep after protection, uint8 of the map's shape (`ym_map_seen_through`'s mask)"""
+        self._need_counted("debug_swept_mask")
+        viewers = list(viewers)
+        vs = (C.c_void_p * max(1, len(viewers)))(*[self.m._require_native(q) for q in viewers])
+        mask = np.zeros(self.shape, dtype=np.uint8)
+        st = _capi.YmMapSeenStats()
+        _capi.check(self.m._lib.ym_map_seen_through(self.m._m, self._h, None, None, 0, vs, len(viewers), int(clearance), int(protect), None,
+                                                    None, mask.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(st)))
+        return mask, int(st.rays)
 
     # ---- the window (ym_map_reframe, DESIGN.md section 17)
     @property
